@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ray-surface intersections/s on MI355X (BASELINE.json metric), one JSON line on stdout.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config relay4|C2|C3|C4|C5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config relay4|C2|C3|C4|C5] [--dump-outputs DIR]
 
 Default workload ("relay4", the headline BASELINE.json's metric is quoted on): a point source (half-angle 20 mrad) of
 1e7 rays per GPU through 4 toroidal mirrors (two f-x-f relays with the C3 scene's toroid: f = 600 mm, 80 deg, 200 x 30 mm),
@@ -94,7 +94,12 @@ def main(argv=None):
                     help="N > 1 launcher: wall-clock limit in seconds after which all workers are killed (exit code 4)")
     ap.add_argument("--pg-timeout", type=float, default=float(os.environ.get("ART_PG_TIMEOUT", "300")),
                     help="N > 1 worker: timeout in seconds of the process group's collectives")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (every bundle and read-out, a fixed "
+                         "seeded sample of slots, <= 64 MB) as DIR/<name>.npy (float64), to compare two builds output for output")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_sample < 0:
         # a bounded sample of the same workload: ~5 s of the single-threaded oracle, so that the GPU part is a visible share
         # of the driver's run (round 4: 2e6 rays = 20 s of a 24-s run)

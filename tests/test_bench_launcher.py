@@ -205,3 +205,27 @@ def test_bench_as_torchrun_workers():
     assert j["n_gpus"] == 2 and j["config"]["world_size_seen"] == 2 and j["scaling"] == "weak"
     assert j["steps"] == 3 and j["warmup"] == 1
     assert j["value"] == j["value_full_gather"] > 0 and j["value_stats_exchange"] > 0
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs DIR: the last timed step's bundles and read-outs as float64 .npy files, a seeded sample of slots when
+    the step's outputs exceed 64 MB; the same arguments give the same inputs, hence the same files, run after run."""
+    import numpy as np
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        p = _run(["--steps", "2", "--warmup", "1", "--config", "C3", "--rays", "30000", "--cpu-sample", "0",
+                  "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        j = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
+        assert j["steps"] == 2 and j["ms_per_step"] > 0
+    names = sorted(f.name for f in dirs[0].iterdir())
+    assert names == sorted(f.name for f in dirs[1].iterdir())
+    assert {"sample_slots.npy", "c9_e2_point.npy", "c9_det_X.npy", "c9_det_stats.npy"} <= set(names)
+    assert sum((dirs[0] / f).stat().st_size for f in names) <= 64 << 20
+    slots = np.load(dirs[0] / "sample_slots.npy")
+    assert 0 < len(slots) < 30000 and np.all(np.diff(slots) > 0)          # sampled: 10 chains x 3 bundles exceed the budget
+    for f in names:
+        a, b = np.load(dirs[0] / f), np.load(dirs[1] / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b, equal_nan=True), f
+    alive = np.load(dirs[0] / "c9_e2_alive.npy").astype(bool)
+    assert 0 < alive.sum() < len(alive) and np.isnan(np.load(dirs[0] / "c9_det_X.npy")[~alive]).all()

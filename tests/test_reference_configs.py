@@ -1,17 +1,20 @@
-"""CPU: the reference's shipped CONFIG_*.py scripts, read from /root/reference/examples (never copied), run
-UNMODIFIED on this package through `ARTmain` (CPU twin of the kernels as backend).  Skipped where the reference
-tree is absent (GPU box).  Numbers are compared with the golden fixtures / survey anchors of the same scenes."""
-import importlib.util
+"""CPU: the scenes of the reference's shipped CONFIG_*.py scripts, run on this package through `ARTmain` (CPU twin of
+the kernels as backend).  Each scene is rebuilt here with the package's own classes, the way the script builds it
+(same optics, distances, angles, loop lists and post-placement moves); the scripts' SourceProperties / DetectorOptions /
+AnalysisOptions dictionaries are the fixture tests/golden/reference_configs.json
+(tests/golden/generate_reference_configs.py).  Numbers are compared with the golden
+fixtures / survey anchors of the same scenes."""
+import json
 import os
-import sys
+import types
 
 import numpy as np
 import pytest
 
-from conftest import load_golden
+from conftest import GOLDEN_DIR, load_golden
 
-EXAMPLES = "/root/reference/examples"
-pytestmark = pytest.mark.skipif(not os.path.isdir(EXAMPLES), reason="reference tree not present")
+with open(os.path.join(GOLDEN_DIR, "reference_configs.json")) as _f:
+    OPTIONS = json.load(_f)
 
 
 @pytest.fixture()
@@ -29,12 +32,89 @@ def twin(monkeypatch, tmp_path):
         getattr(D, k).update(v)
 
 
+def _singleparabola(SP, ns):
+    import ART.ModuleMirror as mmirror, ART.ModuleSupport as msupp, ART.ModuleProcessing as mp
+    Parabola = mmirror.MirrorParabolic(100, 90, msupp.SupportRoundHole(30, 5, 10, 5))
+    chain = mp.OEPlacement(SP, [Parabola], [200], [0.00], Description="single parabola")
+    chain.optical_elements[0].rotate_roll_by(np.rad2deg(50e-6))        # misaligned out of the incidence plane
+    ns.OpticalChainList = chain
+
+
+def _two_toroids(SP, ns, mask, support, focal, distances, planes, label):
+    """mask -> toroid -> toroid with a loop list in one entry; the scripts pass a 7th positional `render` argument."""
+    import ART.ModuleMirror as mmirror, ART.ModuleMask as mmask, ART.ModuleProcessing as mp
+    R, r = mmirror.ReturnOptimalToroidalRadii(focal, 80)
+    Tor = mmirror.MirrorToroidal(R, r, support)
+    ns.OpticalChainList = mp.OEPlacement(SP, [mmask.Mask(mask), Tor, Tor], distances, [0, 80, -80], planes, label, False)
+
+
+def _fxf(SP, ns):
+    import ART.ModuleSupport as msupp
+    _two_toroids(SP, ns, msupp.SupportRoundHole(Radius=20, RadiusHole=14 / 2, CenterHoleX=0, CenterHoleY=0),
+                 msupp.SupportRectangle(150, 32), 500, [400, 500 - 400, np.linspace(500 - 200, 500 + 200, 11)], [0, 0, 0],
+                 "two toroids f-x-f")
+
+
+def _twisted(SP, ns):
+    import ART.ModuleSupport as msupp
+    _two_toroids(SP, ns, msupp.SupportRoundHole(30, 41e-3 / 2 * 500, 0, 0), msupp.SupportRectangle(200, 30), 600,
+                 [500, 600 - 500, 600], [0, 0, np.linspace(-90, 90, 10)], "two toroids, twisted")
+
+
+def _toroidal_2f2f(SP, ns):
+    import ART.ModuleMirror as mmirror, ART.ModuleSupport as msupp, ART.ModuleProcessing as mp
+    R, r = mmirror.ReturnOptimalToroidalRadii(500, 80)
+    Mirror = mmirror.MirrorToroidal(R, r, msupp.SupportRectangle(300, 50))
+    aligned = mp.OEPlacement(SP, [Mirror], [2 * 500], [80], Description="toroid 2f-2f")
+    ns.OpticalChainList = aligned.get_OE_loop_list(0, "roll", np.linspace(-0.5, 0.5, 11))
+
+
+def _toroidal_2f2f_byhand(SP, ns):
+    """The mirror at the origin, the source placed by hand at 2 f along the incidence direction."""
+    import ART.ModuleMirror as mmirror, ART.ModuleSupport as msupp, ART.ModuleSource as msource
+    import ART.ModuleOpticalElement as moe, ART.ModuleOpticalChain as moc
+    focal, incidence, misalign = 300, 80, 0.00
+    R, r = mmirror.ReturnOptimalToroidalRadii(focal, incidence)
+    Mirror = mmirror.MirrorToroidal(R, r, msupp.SupportRectangle(120, 30))
+    Element1 = moe.OpticalElement(Mirror, np.array([0, 0, 0]), np.array([0, 0, 1]), np.array([1, 0, 0]))
+    S = np.array([2 * focal * np.sqrt(1 - np.cos(np.deg2rad(incidence + misalign)) ** 2), 0,
+                  2 * focal * np.cos(np.deg2rad(incidence + misalign))])
+    rays = msource.PointSource(S, -S, SP["Divergence"], SP["NumberRays"])
+    rays = msource.ApplyGaussianIntensityToRayList(rays, 1 / np.e ** 2)
+    ns.OpticalChainList = moc.OpticalChain(rays, [Element1], "toroid 2f-2f, placed by hand",
+                                           loop_variable_name="incidence misalignment (deg)", loop_variable_value=misalign)
+
+
+def _collimating_telescope(SP, ns):
+    import ART.ModuleMirror as mmirror, ART.ModuleSupport as msupp, ART.ModuleProcessing as mp
+    MirrorCX = mmirror.MirrorSpherical(-1500, msupp.SupportRound(25))
+    MirrorCC = mmirror.MirrorSpherical(2500, msupp.SupportRound(25))
+    Parabola = mmirror.MirrorParabolic(100, 90, msupp.SupportRound(25))
+    ns.OpticalChainList = mp.OEPlacement(SP, [MirrorCX, MirrorCC, Parabola], [5000, 598, 1000], [5, 3.4, 0.04],
+                                         Description="collimating telescope")
+
+
+def _deformed(SP, ns):
+    import ART.ModuleMirror as mmirror, ART.ModuleSupport as msupp, ART.ModuleProcessing as mp, ART.ModuleDefects as mdef
+    Support = msupp.SupportRectangle(40, 40)
+    Mirror = mmirror.MirrorParabolic(25.4, 0, Support)
+    Defect = mdef.Fourrier(Support, RMS=1e-1, smallest=0.01)
+    ns.DeformedMirror = mmirror.DeformedMirror(Mirror, [Defect])
+    ns.OpticalChainList = mp.OEPlacement(SP, [ns.DeformedMirror], [15], [0], Description="deformed parabola")
+
+
+SCENES = {"CONFIG_singleparabola.py": _singleparabola, "CONFIG_2toroidals_f-x-f.py": _fxf,
+          "CONFIG_2toroidals_twisted.py": _twisted, "CONFIG_toroidal2f-2f.py": _toroidal_2f2f,
+          "CONFIG_toroidal2f-2f_byhand.py": _toroidal_2f2f_byhand,
+          "CONFIG_CollimatingTelescope.py": _collimating_telescope, "CONFIG_deformed.py": _deformed}
+
+
 def _load(name):
-    path = os.path.join(EXAMPLES, name)
-    spec = importlib.util.spec_from_file_location(name[:-3], path)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    """A stand-in for the imported CONFIG module: its chain(s) and its three option dictionaries."""
+    opts = json.loads(json.dumps(OPTIONS[name]))       # fresh dictionaries: ARTmain completes them in place
+    ns = types.SimpleNamespace(**opts)
+    SCENES[name](ns.SourceProperties, ns)
+    return ns
 
 
 def _run(mod):
@@ -101,8 +181,7 @@ def test_other_configs_run(twin, name):
 
 def test_config_deformed(twin):
     """CONFIG_deformed.py: a Fourrier height map with smallest = 0.01 mm on a 40 x 40 mm support = 8000 x 8000
-    samples (0.5 GB as fp64, synthesised with a 4001 x 8000 complex FFT).  Runs unmodified; slow-ish on CPU."""
-    import numpy as np
+    samples (0.5 GB as fp64, synthesised with a 4001 x 8000 complex FFT).  Slow-ish on CPU."""
     np.random.seed(1)
     mod = _load("CONFIG_deformed.py")
     D = mod.DeformedMirror.DeformationList[0]

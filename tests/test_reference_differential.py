@@ -1,13 +1,17 @@
-"""CPU, only where the reference tree is present: the product's host shell against the reference ITSELF on seeded
+"""CPU: the product's host shell against the reference ITSELF on seeded
 random chains (1-4 optics of every mirror class + masks, random distances, incidence angles and incidence-plane
 rotations, point and plane-wave sources):
   * `OEPlacement` -> poses and exception types;
   * `FindOptimalDistance`, `GetResultSummary`, `getETransmission` on the traced bundles;
   * random sequences of `OpticalChain` operations and the loop-list generators.
 The reference runs in a subprocess (its package is also called `ART`) and reports its results as JSON; both sides
-build their scenes from the same generator text below.  Seeds per test: ART_FUZZ_PLACEMENTS / ART_FUZZ_FOCUS /
+build their scenes from the same generator text below.  Its results for the default seeds are recorded in
+tests/golden/reference_differential.json.gz (tests/golden/generate_reference_differential.py); with ART_REFERENCE naming
+a reference tree the scripts run live there instead, for any seed range.  Seeds per test: ART_FUZZ_PLACEMENTS / ART_FUZZ_FOCUS /
 ART_FUZZ_OPS / ART_FUZZ_METHODS / ART_FUZZ_DETECTOR / ART_FUZZ_GEOMETRY / ART_FUZZ_MAIN (defaults keep the suite short;
 4000 / 700 / 1500 / 3000 / 1500 / 5000 / 500 were run offline)."""
+import gzip
+import hashlib
 import json
 import os
 import subprocess
@@ -18,8 +22,36 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+RECORDED = os.path.join(ROOT, "tests", "golden", "reference_differential.json.gz")
+
+
+def script_key(script, stdin):
+    """Identifies what a recorded result was computed from: the reference-side script and the text fed to it."""
+    return hashlib.sha256((script + "\0" + stdin).encode()).hexdigest()
+
+
+def run_reference(ref_tree, script, stdin, lo, hi):
+    """Run one of the scripts below on the reference tree `ref_tree`; returns its JSON result."""
+    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
+    argv = [sys.executable, "-c", script, ROOT, ref_tree] + ([] if lo is None else [str(lo), str(hi)])
+    r = subprocess.run(argv, input=stdin, capture_output=True, text=True, timeout=3000, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    return json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+
+
+def reference_results(key, script, stdin, lo, hi):
+    """The reference's results for one test on the seeds [lo, hi): run live on the tree ART_REFERENCE names, else the
+    recorded ones (which exist for the default seed range of each test)."""
+    if os.environ.get("ART_REFERENCE"):
+        return run_reference(os.environ["ART_REFERENCE"], script, stdin, lo, hi)
+    with gzip.open(RECORDED, "rt") as f:
+        rec = json.load(f)[key]
+    assert rec["script_sha256"] == script_key(script, stdin), \
+        "the reference-side script or generator changed: rerun tests/golden/generate_reference_differential.py"
+    if rec["range"] != [lo, hi]:
+        pytest.fail(f"seeds [{lo}, {hi}) of '{key}' are not recorded (recorded: {rec['range']}): set ART_REFERENCE to a "
+                    "reference tree to run them")
+    return rec["result"]
 
 GENERATOR = textwrap.dedent('''
     import numpy as np
@@ -108,11 +140,7 @@ def twin():
 
 def test_oeplacement_random_chains_match_reference(twin):
     lo, hi = 0, int(os.environ.get("ART_FUZZ_PLACEMENTS", "60"))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", REF_SCRIPT, ROOT, REF, str(lo), str(hi)], input=GENERATOR,
-                       capture_output=True, text=True, timeout=3000, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    ref = json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+    ref = reference_results("placements", REF_SCRIPT, GENERATOR, lo, hi)
     import ART.ModuleProcessing as mp
     import ART.ModuleMirror as mmirror
     import ART.ModuleMask as mmask
@@ -184,11 +212,7 @@ def test_autofocus_and_summary_random_chains_match_reference(twin):
     """FindOptimalDistance (both working OptFor values, weighted or not), GetResultSummary and getETransmission on the
     bundles of random chains: the product's device-side moment scan against the reference's per-position loops."""
     lo, hi = 0, int(os.environ.get("ART_FUZZ_FOCUS", "24"))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", FOCUS_SCRIPT, ROOT, REF, str(lo), str(hi)], input=GENERATOR,
-                       capture_output=True, text=True, timeout=3000, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    ref = json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+    ref = reference_results("focus", FOCUS_SCRIPT, GENERATOR, lo, hi)
     import ART.ModuleProcessing as mp
     import ART.ModuleMirror as mmirror
     import ART.ModuleMask as mmask
@@ -321,11 +345,7 @@ def test_chain_operations_random_sequences_match_reference(twin):
     219-615) applied in random sequences to random chains: same resulting sources, poses, loop-variable names, survivor
     counts, final rays and exception types as the reference."""
     lo, hi = 0, int(os.environ.get("ART_FUZZ_OPS", "30"))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", OPS_SCRIPT, ROOT, REF, str(lo), str(hi)], input=GENERATOR + OPS_GEN,
-                       capture_output=True, text=True, timeout=3000, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    ref = json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+    ref = reference_results("ops", OPS_SCRIPT, GENERATOR + OPS_GEN, lo, hi)
     import ART.ModuleProcessing as mp
     import ART.ModuleMirror as mmirror
     import ART.ModuleMask as mmask
@@ -446,11 +466,7 @@ def test_single_ray_methods_and_square_source_match_reference(twin):
     `TransmitMaskRayList` of every optic class on rays given in the optic's own frame, and `PlaneWaveSquare`
     (which the reference only runs for NbRays < 4)."""
     lo, hi = 0, int(os.environ.get("ART_FUZZ_METHODS", "48"))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", METHODS_SCRIPT, ROOT, REF, str(lo), str(hi)], input=METHODS_GEN,
-                       capture_output=True, text=True, timeout=3000, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    ref = json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+    ref = reference_results("methods", METHODS_SCRIPT, METHODS_GEN, lo, hi)
     import ART.ModuleMirror as mmirror
     import ART.ModuleMask as mmask
     import ART.ModuleSupport as msupp
@@ -581,11 +597,7 @@ def test_detector_sessions_match_reference(twin):
     """Detector construction errors, autoplace, shiftBy/shiftTo/copy, manual re-posing, and the four read-out
     methods in random sequences (ART/ModuleDetector.py:47-279)."""
     lo, hi = 0, int(os.environ.get("ART_FUZZ_DETECTOR", "40"))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", DET_SCRIPT, ROOT, REF, str(lo), str(hi)], input=GENERATOR + DET_GEN,
-                       capture_output=True, text=True, timeout=3000, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    ref = json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+    ref = reference_results("detector", DET_SCRIPT, GENERATOR + DET_GEN, lo, hi)
     import ART.ModuleProcessing as mp
     import ART.ModuleMirror as mmirror
     import ART.ModuleMask as mmask
@@ -786,11 +798,7 @@ def test_values_and_exception_types_of_the_host_api_match_reference(twin, capsys
     """A table of small API calls -- constructors with bad arguments, validating setters, helper functions, chain
     operations with wrong axis names or indices -- evaluated by the reference and by the product: same values, same
     exception TYPES ("same names, argument meaning and error behaviour")."""
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", ERR_SCRIPT, ROOT, REF], input=ERR_PRELUDE + "#CASES#" + json.dumps(ERR_CASES),
-                       capture_output=True, text=True, timeout=3000, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    ref = json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+    ref = reference_results("errors", ERR_SCRIPT, ERR_PRELUDE + "#CASES#" + json.dumps(ERR_CASES), None, None)
     ns = {}
     exec(ERR_PRELUDE, ns)
     mine = ns["run_cases"](ERR_CASES)
@@ -863,11 +871,7 @@ def test_geometry_helpers_match_reference(twin):
     """All 27 functions of ModuleGeometry on random inputs (rotations incl. the identity / point-inversion special
     cases, ray and ray-list transforms, solvers, point-list statistics)."""
     lo, hi = 0, int(os.environ.get("ART_FUZZ_GEOMETRY", "60"))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", GEO_SCRIPT, ROOT, REF, str(lo), str(hi)], input=GEO_GEN,
-                       capture_output=True, text=True, timeout=3000, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    ref = json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+    ref = reference_results("geometry", GEO_SCRIPT, GEO_GEN, lo, hi)
     import ART.ModuleGeometry as mgeo
     import ART.ModuleOpticalRay as mray
     ns = {"np": np}
@@ -941,11 +945,7 @@ def test_artmain_main_matches_reference(twin):
     """`ARTmain.main` end to end (trace, transmission, detector set-up -- automatic, manual or invalid --, autofocus or
     summary) on random chains with <= 1000 rays, where the reference's autofocus also uses every ray."""
     lo, hi = 0, int(os.environ.get("ART_FUZZ_MAIN", "24"))
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", MAIN_SCRIPT, ROOT, REF, str(lo), str(hi)], input=GENERATOR + MAIN_GEN,
-                       capture_output=True, text=True, timeout=3000, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    ref = json.loads(r.stdout[r.stdout.index("RESULT") + 6:])
+    ref = reference_results("main", MAIN_SCRIPT, GENERATOR + MAIN_GEN, lo, hi)
     import ART.ModuleProcessing as mp
     import ART.ModuleMirror as mmirror
     import ART.ModuleMask as mmask

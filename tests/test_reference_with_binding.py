@@ -1,63 +1,81 @@
-"""CPU: the REFERENCE ITSELF (read from /root/reference, its own OpticalChain / OEPlacement / Detector classes) with
-its `RayTracingCalculation` replaced by the INTEGRATION.md binding stub calling our C ABI (CPU twin of the kernels
-here).  Run in a subprocess because the reference's package is also called `ART`.  The patched reference must
-reproduce what the unpatched reference computes."""
+"""CPU: the INTEGRATION.md binding stub (a drop-in for the reference's `RayTracingCalculation` that calls our C ABI; CPU
+twin of the kernels here) fed exactly what the reference feeds its own `RayTracingCalculation`.  The reference's calls
+while it places and traces a mask + two toroids + off-axis parabola chain -- the 1-ray alignment traces of its
+OEPlacement, then the 400-ray trace -- are recorded with their results in tests/golden/reference_binding.json.gz
+(tests/golden/generate_binding_goldens.py).  Each call is replayed through the stub on objects that carry the same public
+attributes as the reference's rays, optics, supports and elements; the stub must reproduce what the reference computed.
+The reference's element poses and detector delays are recorded too: the package's own OEPlacement must put the elements
+there, and the package's Detector on the stub's last bundle must give the reference Detector's delays."""
+import gzip
+import json
 import os
-import subprocess
-import sys
-import textwrap
+import types
 
-import pytest
+import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
+from conftest import GOLDEN_DIR
 
-SCRIPT = textwrap.dedent('''
-    import sys, ctypes as C
-    sys.dont_write_bytecode = True
-    ROOT, REF = sys.argv[1], sys.argv[2]
-    sys.path[:0] = [REF, ROOT + "/tests/golden/_standin", ROOT + "/tests", ROOT]     # `ART` = the reference
-    import matplotlib; matplotlib.use("Agg")
-    import numpy as np, torch
-    import ART.ModuleProcessing as mp, ART.ModuleMirror as mmirror, ART.ModuleMask as mmask
-    import ART.ModuleSupport as msupp, ART.ModuleDetector as mdet, ART.ModuleOpticalRay as mray
-    assert mp.__file__.startswith(REF)
+
+def _support(d):
+    # the stub dispatches on the support's class name, as it does on the reference's own classes
+    return type(d["class"], (), dict(d["attrs"]))()
+
+
+def _element(d):
+    o = d["optic"]
+    optic = types.SimpleNamespace(type=o["type"], support=_support(o["support"]), **o["params"])
+    optic.get_centre = lambda c=np.array(o["centre"]): c
+    return types.SimpleNamespace(type=optic, position=np.array(d["position"]), normal=np.array(d["normal"]),
+                                 majoraxis=np.array(d["majoraxis"]))
+
+
+def _rays(d):
+    return [types.SimpleNamespace(point=np.array(p), vector=np.array(v), path=tuple(s), number=k, wavelength=w,
+                                  incidence=i, intensity=t)
+            for p, v, s, k, w, i, t in zip(d["point"], d["vector"], d["path"], d["number"], d["wavelength"],
+                                           d["incidence"], d["intensity"])]
+
+
+def test_reference_runs_on_our_abi_through_the_stub(monkeypatch):
+    import ctypes as C
+    import torch
+    from twin_backend import TwinBackend
+    from attosecondraytracing_amd import _lib
+    monkeypatch.setattr(_lib, "_BACKEND", TwinBackend())       # the package's Detector below runs on the CPU twin too
+    import ART.ModuleOpticalRay as mray
+    import ART.ModuleDetector as mdet
     from twin_backend import build_twin
     import binding_stub
+    with gzip.open(os.path.join(GOLDEN_DIR, "reference_binding.json.gz"), "rt") as f:
+        rec = json.load(f)
     lib = C.CDLL(build_twin())
+    trace = binding_stub.make_binding(lib, "art_cpu_", torch.device("cpu"), mray.Ray)
+    assert len(rec["calls"]) >= 2                   # the placement's alignment traces, then the chain's trace
+    for call in rec["calls"]:
+        out = trace(_rays(call["source"]), [_element(e) for e in call["elements"]], call["IgnoreDefects"])
+        ref = call["result"]
+        assert [len(o) for o in out] == [len(q["number"]) for q in ref]
+        for o, q in zip(out, ref):
+            assert [x.number for x in o] == q["number"]
+            if not o:
+                continue
+            assert np.abs(np.array([x.point for x in o]) - q["point"]).max() <= 1e-10 * 2000
+            assert np.abs(np.array([x.vector for x in o]) - q["vector"]).max() <= 1e-10
+            assert np.abs(np.array([sum(x.path) for x in o]) - np.array([sum(p) for p in q["path"]])).max() <= 1e-10 * 2000
+            assert np.abs(np.array([x.incidence for x in o]) - q["incidence"]).max() <= 1e-9
+    assert [len(o) for o in out] == rec["n_out"] and len(out[-1]) > 200
+    # the placement: the package's own OEPlacement of the same chain puts the elements where the reference put them
+    import ART.ModuleProcessing as mp, ART.ModuleMirror as mmirror, ART.ModuleMask as mmask, ART.ModuleSupport as msupp
     SP = {"Divergence": 50e-3 / 2, "SourceSize": 0, "Wavelength": 50e-6, "DeltaFT": 0.5, "NumberRays": 400}
-    Mask = mmask.Mask(msupp.SupportRoundHole(30, 41e-3 / 2 * 500, 0, 0))
     R, r = mmirror.ReturnOptimalToroidalRadii(600, 80)
     Tor = mmirror.MirrorToroidal(R, r, msupp.SupportRectangle(200, 30))
-    oap = mmirror.MirrorParabolic(150, 45, msupp.SupportRound(40))
-    original = mp.RayTracingCalculation
-    def build():
-        return mp.OEPlacement(SP, [Mask, Tor, Tor, oap], [500, 100, 600, 400], [0, 80, -80, 0], [0, 0, 30.0, 0], "stub")
-    ref_chain = build()
-    ref = ref_chain.get_output_rays()
-    mp.RayTracingCalculation = binding_stub.make_binding(lib, "art_cpu_", torch.device("cpu"), mray.Ray)
-    chain = build()                      # OEPlacement's alignment traces already go through the binding
-    out = chain.get_output_rays()
-    for a, b in zip(ref_chain.optical_elements, chain.optical_elements):
-        assert np.abs(a.position - b.position).max() <= 1e-9 and np.abs(a.normal - b.normal).max() <= 1e-12
-    assert [len(o) for o in out] == [len(o) for o in ref] and len(out[-1]) > 200
-    for o, q in zip(out, ref):
-        assert [x.number for x in o] == [x.number for x in q]
-        assert max(np.abs(x.point - y.point).max() for x, y in zip(o, q)) <= 1e-10 * 2000
-        assert max(np.abs(x.vector - y.vector).max() for x, y in zip(o, q)) <= 1e-10
-        assert max(abs(sum(x.path) - sum(y.path)) for x, y in zip(o, q)) <= 1e-10 * 2000
-        assert max(abs(x.incidence - y.incidence) for x, y in zip(o, q)) <= 1e-9
-    det = mdet.Detector(chain.optical_elements[-1].position); det.autoplace(out[-1], 150)
-    det0 = mdet.Detector(ref_chain.optical_elements[-1].position); det0.autoplace(ref[-1], 150)
-    d1, d0 = np.array(det.get_Delays(out[-1])), np.array(det0.get_Delays(ref[-1]))
+    chain = mp.OEPlacement(SP, [mmask.Mask(msupp.SupportRoundHole(30, 41e-3 / 2 * 500, 0, 0)), Tor, Tor,
+                                mmirror.MirrorParabolic(150, 45, msupp.SupportRound(40))],
+                           [500, 100, 600, 400], [0, 80, -80, 0], [0, 0, 30.0, 0], "stub")
+    for oe, pose in zip(chain.optical_elements, rec["poses"]):
+        assert np.abs(oe.position - pose["position"]).max() <= 1e-9 and np.abs(oe.normal - pose["normal"]).max() <= 1e-12
+    # the reference Detector's delays on the reference's last bundle, against ours on the stub's
+    det = mdet.Detector(np.array(rec["poses"][-1]["position"]))
+    det.autoplace(out[-1], 150)
+    d1, d0 = np.array(det.get_Delays(out[-1])), np.array(rec["delays"])
     assert np.abs(d1 - d0).max() <= 1e-10 * 1e15 * 2000 / 299792458000
-    print("BINDING_OK", [len(o) for o in out])
-''')
-
-
-def test_reference_runs_on_our_abi_through_the_stub():
-    env = dict(os.environ, PYTHONDONTWRITEBYTECODE="1")
-    r = subprocess.run([sys.executable, "-c", SCRIPT, ROOT, REF], capture_output=True, text=True, timeout=600, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "BINDING_OK" in r.stdout

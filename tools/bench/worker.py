@@ -295,6 +295,8 @@ def worker(args):
         for _ in range(int(cnt.item())):
             step(main_kind)
     dt, t_enq, o, r = timed(main_kind, args.steps, args.warmup)
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dump_outputs(args.dump_outputs, o, r, n)        # what the last timed step computed (after the clock stopped)
     dt_stats = gather_only = None
     if use_dist:
         b_last = (state["step"] - 1) % 2
@@ -645,3 +647,55 @@ def _roofline(args, cfg, be, program, mode, fuse, lite, src, element_lists, live
               "frac_algorithmic": ro_bytes / (readout_ms * 1e-3) / 1e9 / rl.HBM_PEAK_GBS,
               "algorithmic_bytes_per_ray": 89.0, "kernel_ms": readout_ms, "launches_per_step": n_chains}
     return roof, ro
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 20240601
+
+
+def dump_outputs(path, outs, readouts, n):
+    """--dump-outputs DIR: the last timed step's results, as a caller of the step receives them, written as float64 .npy
+    files under DIR -- per chain c and element e the bundle's ray state (`c{c}_e{e}_{point,vector,path,incidence,number,
+    alive}`), per chain the detector read-out (`c{c}_det_{X,Y,opl}`, `c{c}_det_stats`: the 24 statistics).  Per-ray
+    arrays hold a fixed, seeded sample of slots (the same for every array, `sample_slots.npy`), sized so that all files
+    stay under 64 MB; entries of rays that did not survive are NaN, so that two builds compare element for element.
+    N > 1: rank 0's shard."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n_bundles = sum(len(o) for o in outs)
+    per_ray = 8 * (10 * n_bundles + 3 * len(outs) + 1)       # 10 float64 values per ray and bundle, 3 per read-out, the slot
+    fixed = 8 * 24 * len(outs) + 128 * (1 + 6 * n_bundles + 4 * len(outs))    # statistics, one .npy header per file
+    k = max(1, min(n, (DUMP_BUDGET_BYTES - fixed) // per_ray))
+    slots = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+    files = {"sample_slots": slots.astype(np.float64)}
+
+    def host(t, idx, alive):
+        a = t.index_select(0, idx).to(torch.float64).cpu().numpy()
+        a[~alive] = np.nan
+        return a
+
+    for c, (chain, ro) in enumerate(zip(outs, readouts)):
+        idx, ro = None, ro or {}            # a tiled N > 1 step reports the read-out of the last chain only
+        for e, b in enumerate(chain):
+            idx = torch.from_numpy(slots).to(b.alive.device)
+            alive = b.alive.index_select(0, idx).cpu().numpy().astype(bool)
+            d = b.data.index_select(1, idx).cpu().numpy().T.copy()          # [k, 8]: point, vector, path, incidence
+            d[~alive] = np.nan
+            number = idx if b.number is None else b.number.index_select(0, idx)
+            files.update({f"c{c}_e{e}_point": d[:, 0:3], f"c{c}_e{e}_vector": d[:, 3:6], f"c{c}_e{e}_path": d[:, 6],
+                          f"c{c}_e{e}_incidence": d[:, 7], f"c{c}_e{e}_alive": alive.astype(np.float64),
+                          f"c{c}_e{e}_number": np.where(alive, number.cpu().numpy().astype(np.float64), np.nan)})
+        for key in ("X", "Y", "opl"):
+            if ro.get(key) is not None:
+                files[f"c{c}_det_{key}"] = host(ro[key], idx, alive)
+        stats = ro.get("stats_dev", ro.get("stats"))
+        if stats is not None:
+            files[f"c{c}_det_stats"] = (stats.cpu().numpy() if torch.is_tensor(stats) else np.asarray(stats)).astype(np.float64)
+    total = 0
+    for name, a in files.items():
+        f = os.path.join(path, name + ".npy")
+        np.save(f, np.ascontiguousarray(a, dtype=np.float64))
+        total += os.path.getsize(f)
+    assert total <= DUMP_BUDGET_BYTES, total
+    log(f"[bench] --dump-outputs: {len(files)} arrays ({total / 2**20:.1f} MB, {k} of {n} slots per bundle) -> {path}")
