@@ -250,6 +250,10 @@ constexpr int kRedUnroll = 4;
 // 4 waves, one partial per workgroup into `scratch`, then fold_slot(): one workgroup per statistic folds the
 // partials in a fixed order.
 constexpr int kRedBlocks = 1024;
+inline int red_blocks(int64_t n) {   // workgroups of a reduction over n slots: one per 256, between 1 and kRedBlocks
+  const int64_t b = (n + kBlock - 1) / kBlock;
+  return (int)(b < 1 ? 1 : (b > kRedBlocks ? kRedBlocks : b));
+}
 constexpr int kRedSlots = 16;
 constexpr int kReadoutSlots = 24;   // art_detector_readout / fused chain read-out statistics
 constexpr int kUsedSlots = 22;      // slots 22, 23 are reserved (always 0): the fused tail writes no partials for them
@@ -701,6 +705,36 @@ __device__ __forceinline__ void store_tile_lds4(const ArtBundleView& v, const in
 }
 #endif
 
+// End of the fused read-out tail of both bodies.  One partial per WORKGROUP (round 3; per wave before): the four wave totals
+// `tot` meet in LDS behind a bare s_barrier -- __syncthreads() would also wait for the acknowledgement of the stores in
+// flight -- and threads 0..21 fold them in wave order and store row `thread` (= pass * 8 + stat, row_of_slot) of the scratch
+// area.  A quarter of the partials: the fold that follows reads 7.5 MB instead of 30 MB per 1e7 rays and fits ONE launch
+// (launch_fold).  `a` is passed by reference and ro.scratch read here: as a pointer argument its scalar load was hoisted
+// and the scene kernel gained v_readlane moves.
+__device__ __forceinline__ void tail_partial(const ChainArgs& a, const double tot[3], double (*s_part)[kReadoutSlots],
+                                             const unsigned lane, const unsigned bx, const unsigned nbx) {
+  if ((lane & 7) == 0) {
+    const int stat = (lane & 63) >> 3, w = lane >> 6;
+    s_part[w][stat] = tot[0];
+    s_part[w][8 + stat] = tot[1];
+    if (stat < 6) s_part[w][16 + stat] = tot[2];
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#ifdef ART_DIAG_RO_NOSCRATCH  // timing-only build: the fused tail without the partial-statistics stores
+  if (tot[0] + tot[1] + tot[2] == -1.2345e300) {
+#else
+  if (lane < kUsedSlots) {
+#endif
+    double v = s_part[0][lane];
+#pragma unroll
+    for (int j = 1; j < kBlock / 64; ++j) {
+      const double q = s_part[j][lane];
+      v = (lane < 16) ? v + q : (lane < 19 ? fmin(v, q) : fmax(v, q));    // rows 16-18: minima, 19-21: maxima
+    }
+    a.ro.scratch[(int64_t)lane * nbx + bx] = v;
+  }
+}
+
 // Whole chain with the ray resident in registers; history written for every element whose view is non-null.
 // `a` lives in kernel arguments (k_trace_chain) or in the device-resident scene table (k_trace_scene): either way
 // its fields are wave-uniform and fetched by scalar loads where they are used.  Rays [first, first + n) of every view.
@@ -814,7 +848,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const int64_t fir
       } else {
       readout_single(acc, ok, x, y, o, s_w[lane ^ ((unsigned)a.flags >> 30)], a.ro.w != nullptr, a.ro.cx, a.ro.cy,
                      a.ro.co);
-#ifdef ART_DIAG_RO_NOREDUCE  // ... without the wave reduction, ...
+#ifdef ART_DIAG_RO_NOREDUCE  // ... without the wave reduction (ART_DIAG_RO_NOSCRATCH: see tail_partial)
       tot[0] = acc[0] + acc[1] + acc[6] + acc[7] + acc[8] + acc[9] + acc[10] + acc[11];
       tot[1] = acc[16] + acc[17] + acc[18] + acc[19] + acc[20] + acc[21];
       tot[2] = acc[2] + acc[3] + acc[4] + acc[5] + acc[12] + acc[13];
@@ -822,30 +856,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const int64_t fir
       wave_reduce24(acc, s_red + (lane >> 6) * (8 * kTileStride), lane & 63, tot);
 #endif
       }
-      // One partial per WORKGROUP (round 3; per wave before): the four wave totals meet in LDS behind a bare s_barrier --
-      // __syncthreads() would also wait for the acknowledgement of the stores in flight -- and threads 0..21 fold them in
-      // wave order and store row `thread` (= pass * 8 + stat, row_of_slot) of the scratch area.  A quarter of the partials:
-      // the fold that follows reads 7.5 MB instead of 30 MB per 1e7 rays and fits ONE launch (launch_fold_*).
-      if ((lane & 7) == 0) {
-        const int stat = (lane & 63) >> 3, w = lane >> 6;
-        s_part[w][stat] = tot[0];
-        s_part[w][8 + stat] = tot[1];
-        if (stat < 6) s_part[w][16 + stat] = tot[2];
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#ifdef ART_DIAG_RO_NOSCRATCH  // ... without the partial-statistics stores
-      if (tot[0] + tot[1] + tot[2] == -1.2345e300) {
-#else
-      if (lane < kUsedSlots) {
-#endif
-        double v = s_part[0][lane];
-#pragma unroll
-        for (int j = 1; j < kBlock / 64; ++j) {
-          const double q = s_part[j][lane];
-          v = (lane < 16) ? v + q : (lane < 19 ? fmin(v, q) : fmax(v, q));    // rows 16-18: minima, 19-21: maxima
-        }
-        a.ro.scratch[(int64_t)lane * nbx + bx] = v;
-      }
+      tail_partial(a, tot, s_part, lane, bx, nbx);
       }
     }
     i0 += stride;
@@ -948,22 +959,7 @@ __device__ __forceinline__ void chain_body2(const ChainArgs& a, const int64_t fi
       readout_accumulate(acc, ok[1], x[1], y[1], o[1], s_w[1][li], a.ro.w != nullptr, a.ro.cx, a.ro.cy, a.ro.co);
       wave_reduce24(acc, s_red + (lane >> 6) * (8 * kTileStride), lane & 63, tot);
     }
-    if ((lane & 7) == 0) {
-      const int stat = (lane & 63) >> 3, w = lane >> 6;
-      s_part[w][stat] = tot[0];
-      s_part[w][8 + stat] = tot[1];
-      if (stat < 6) s_part[w][16 + stat] = tot[2];
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    if (lane < kUsedSlots) {
-      double t = s_part[0][lane];
-#pragma unroll
-      for (int j = 1; j < kBlock / 64; ++j) {
-        const double q = s_part[j][lane];
-        t = (lane < 16) ? t + q : (lane < 19 ? fmin(t, q) : fmax(t, q));
-      }
-      a.ro.scratch[(int64_t)lane * nbx + bx] = t;
-    }
+    tail_partial(a, tot, s_part, lane, bx, nbx);
   }
 }
 
@@ -1052,22 +1048,8 @@ __global__ __launch_bounds__(kFoldBlock) void k_chain_readout_fold2_one(double* 
   fold_stage2(scratch, nparts, out24, direct);
 }
 
-// launch the fold (host side): ONE launch up to kFoldDirect partials; a short row does not need 1024 threads
+// threads per workgroup of a one-stage fold: a short row does not need 1024
 inline int fold_threads(int64_t nparts) { return nparts <= 4096 ? kBlock : kFoldBlock; }
-inline void launch_fold_one(double* scratch, double* out24, int64_t nparts, hipStream_t s) {
-  const int direct = nparts <= kFoldDirect;
-  if (!direct)
-    hipLaunchKernelGGL(k_chain_readout_fold1_one, dim3(kReadoutSlots, kFoldChunks), dim3(kFoldBlock), 0, s, scratch, nparts);
-  hipLaunchKernelGGL(k_chain_readout_fold2_one, dim3(kReadoutSlots), dim3(direct ? fold_threads(nparts) : kBlock), 0, s, scratch,
-                     out24, nparts, direct);
-}
-inline void launch_fold_scene(const ChainArgs* seg, int n_chains, int64_t nparts, hipStream_t s) {
-  const int direct = nparts <= kFoldDirect;
-  if (!direct)
-    hipLaunchKernelGGL(k_chain_readout_fold1, dim3(kReadoutSlots, kFoldChunks, n_chains), dim3(kFoldBlock), 0, s, seg, nparts);
-  hipLaunchKernelGGL(k_chain_readout_fold2, dim3(kReadoutSlots, 1, n_chains), dim3(direct ? fold_threads(nparts) : kBlock), 0, s,
-                     seg, nparts, direct);
-}
 
 // Fold of the per-tile partial SUMS (kSumRows rows of `ntiles`, see run_sums8) into out[0 .. 8]: the same launch shape and
 // fold_range for the tail of a tracing launch and for art_analyse_bundles' own pass (1) -- same bits either way.  Beyond
@@ -1098,19 +1080,22 @@ __global__ __launch_bounds__(kFoldBlock) void k_chain_sums_fold2_one(double* scr
   sums_fold2(scratch, ntiles, out24, direct);
   if (blockIdx.x == 0 && threadIdx.x < kReadoutSlots - kSumRows) out24[kSumRows + threadIdx.x] = 0.0;
 }
-inline void launch_sums_fold_one(double* scratch, double* out24, int64_t ntiles, hipStream_t s) {
-  const int direct = ntiles <= kFoldDirect;
-  if (!direct)
-    hipLaunchKernelGGL(k_chain_sums_fold1_one, dim3(kSumRows, kFoldChunks), dim3(kFoldBlock), 0, s, scratch, ntiles);
-  hipLaunchKernelGGL(k_chain_sums_fold2_one, dim3(kSumRows), dim3(direct ? fold_threads(ntiles) : kBlock), 0, s, scratch, out24,
-                     ntiles, direct);
-}
-inline void launch_sums_fold_scene(const ChainArgs* seg, int n_chains, int64_t ntiles, hipStream_t s) {
-  const int direct = ntiles <= kFoldDirect;
-  if (!direct)
-    hipLaunchKernelGGL(k_chain_sums_fold1, dim3(kSumRows, kFoldChunks, n_chains), dim3(kFoldBlock), 0, s, seg, ntiles);
-  hipLaunchKernelGGL(k_chain_sums_fold2, dim3(kSumRows, 1, n_chains), dim3(direct ? fold_threads(ntiles) : kBlock), 0, s, seg,
-                     ntiles, direct);
+// Launch the fold behind a tail (host side): `sums` selects the sums kernels (kSumRows rows of `nparts` tiles) over the
+// read-out ones (24 slots of `nparts` workgroups); `seg` != nullptr folds the tails of the n_chains chains of that table
+// segment, else the one pair `scratch` / `out24`.  ONE launch up to kFoldDirect partials.
+void launch_fold(const bool sums, const ChainArgs* seg, const int n_chains, double* scratch, double* out24,
+                 const int64_t nparts, hipStream_t s) {
+  const int direct = nparts <= kFoldDirect;
+  const unsigned rows = sums ? kSumRows : kReadoutSlots, z = seg ? n_chains : 1;
+  if (!direct) {
+    if (seg) hipLaunchKernelGGL(sums ? k_chain_sums_fold1 : k_chain_readout_fold1, dim3(rows, kFoldChunks, z), dim3(kFoldBlock),
+                                0, s, seg, nparts);
+    else hipLaunchKernelGGL(sums ? k_chain_sums_fold1_one : k_chain_readout_fold1_one, dim3(rows, kFoldChunks), dim3(kFoldBlock),
+                            0, s, scratch, nparts);
+  }
+  const dim3 g2(rows, 1, z), b2(direct ? fold_threads(nparts) : kBlock);
+  if (seg) hipLaunchKernelGGL(sums ? k_chain_sums_fold2 : k_chain_readout_fold2, g2, b2, 0, s, seg, nparts, direct);
+  else hipLaunchKernelGGL(sums ? k_chain_sums_fold2_one : k_chain_readout_fold2_one, g2, b2, 0, s, scratch, out24, nparts, direct);
 }
 
 template <bool DEFECT, int WAVES>
@@ -1193,32 +1178,6 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_trace_chain1(const ChainArgs,
   typedef const ChainArgs __attribute__((address_space(4)))* kernarg_t;
   chain_body<true, KIND1>(*(const ChainArgs*)(kernarg_t)__builtin_amdgcn_kernarg_segment_ptr(), 0, n, xmap, s_dyn, blockIdx.x,
                           gridDim.x);
-}
-
-// One-element chains with defects whose optic is a plane, a sphere or a parabola (what a deformed mirror usually is: C5)
-// run a body compiled for that kind (k_trace_*1): no run-time switch, no torus state -- 98 VGPRs instead of 118.
-// ART_CHAIN_SPECIAL=0 switches it off, ART_CHAIN_SPECIAL_WAVES=5 selects the 5-wave build (96 VGPRs, one 8-byte spill per
-// ray in front of the stores); read per launch: the A/B tool alternates them inside one process.
-inline int special_waves() {
-  const char* e = getenv("ART_CHAIN_SPECIAL");
-  if (e && e[0] == '0') return 0;
-  const char* w = getenv("ART_CHAIN_SPECIAL_WAVES");
-  return (w && atoi(w) == 5) ? 5 : 4;
-}
-inline bool special_kind(const int kind) { return kind == ART_PLANE || kind == ART_SPHERE || kind == ART_PARABOLA; }
-template <int WAVES>
-void launch_scene1(const int kind, const dim3 g, hipStream_t s, const ChainArgs* seg, int64_t off, int64_t cnt, int xm, int tr) {
-  const dim3 b(kBlock);
-  if (kind == ART_PLANE) hipLaunchKernelGGL((k_trace_scene1<ART_PLANE, WAVES>), g, b, 0, s, seg, off, cnt, xm, tr);
-  else if (kind == ART_SPHERE) hipLaunchKernelGGL((k_trace_scene1<ART_SPHERE, WAVES>), g, b, 0, s, seg, off, cnt, xm, tr);
-  else hipLaunchKernelGGL((k_trace_scene1<ART_PARABOLA, WAVES>), g, b, 0, s, seg, off, cnt, xm, tr);
-}
-template <int WAVES>
-void launch_chain1(const int kind, const dim3 g, hipStream_t s, const ChainArgs& a, int64_t cnt, int xm) {
-  const dim3 b(kBlock);
-  if (kind == ART_PLANE) hipLaunchKernelGGL((k_trace_chain1<ART_PLANE, WAVES>), g, b, 0, s, a, cnt, xm);
-  else if (kind == ART_SPHERE) hipLaunchKernelGGL((k_trace_chain1<ART_SPHERE, WAVES>), g, b, 0, s, a, cnt, xm);
-  else hipLaunchKernelGGL((k_trace_chain1<ART_PARABOLA, WAVES>), g, b, 0, s, a, cnt, xm);
 }
 
 // ------------------------------------------------------------------------------------------- AoS -> SoA
@@ -1716,7 +1675,7 @@ __global__ __launch_bounds__(kBlock) void k_analysis_sums(const ArtAnalysisJob* 
   const double tot = run_sums8(v, s_tile + (t >> 6) * (8 * kTileStride), t & 63);
   tile_sums_store(tot, __ballot(live), s_run, t, rows + (int64_t)job * job_stride, gridDim.x, blockIdx.x);
 }
-// grids (kSumRows, kFoldChunks, jobs) and (kSumRows, 1, jobs): the folds of launch_sums_fold_*, or a copy of the sums a job
+// grids (kSumRows, kFoldChunks, jobs) and (kSumRows, 1, jobs): the sums folds of launch_fold, or a copy of the sums a job
 // brought along
 __global__ __launch_bounds__(kFoldBlock) void k_analysis_sums_fold1(const ArtAnalysisJob* __restrict__ jobs, const int job0,
                                                                     double* rows, const int64_t job_stride,
@@ -2199,67 +2158,24 @@ void launch_element(const ArtElementDesc& e, const ArtBundleView& in, const ArtB
                        xm);
 }
 
-}  // namespace
-
-// =================================================================================================== C ABI
-extern "C" {
-
-int art_abi_version(void) { return ART_ABI_VERSION; }
-
-const char* art_last_error(void) { return g_err; }
-
-int art_device_count(void) {
-  int n = 0;
-  hipError_t e = hipGetDeviceCount(&n);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    return fail_hip(e, "hipGetDeviceCount");
-  }
-  int good = 0;
-  for (int i = 0; i < n; ++i) {
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, i) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0) ++good;
-  }
-  return good;
-}
-
-int art_trace_element(const ArtElementDesc* e, const ArtBundleView* in, const ArtBundleView* out, int64_t n,
-                      void* stream) {
-  int rc = check_elem(e);
-  if (rc) return rc;
-  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
-  if (n == 0) return ART_OK;  // an empty bundle has no arrays to point to
-  if (!view_ok(in) || !view_ok(out)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
-  hipStream_t s = (hipStream_t)stream;
-  ArtElementDesc ec = *e;
-  art::prepare_element(ec);
+// The launches of an n-ray call: f(off, m) for the slots [off, off + m), m <= max_rays_per_launch() (32-bit buffer
+// offsets); stops at the first error code f returns.
+template <typename F>
+int per_launch(const int64_t n, F&& f) {
   const int64_t chunk = max_rays_per_launch();
   for (int64_t off = 0; off < n; off += chunk) {
-    const int64_t m = (n - off < chunk) ? n - off : chunk;
-    const ArtBundleView vi = view_at(*in, off), vo = view_at(*out, off);
-    if (ec.flags & ART_FLAG_ZERN_RECURRENCE) {
-      ElemArg ea;
-      ea.e[0] = ec;
-      hipLaunchKernelGGL(k_trace_element_zrec, dim3(grid_stream(m)), dim3(kBlock), 0, s, ea, vi, vo, m);
-      continue;
-    }
-    switch (ec.kind) {
-      case ART_PLANE: launch_element<ART_PLANE>(ec, vi, vo, m, s); break;
-      case ART_SPHERE: launch_element<ART_SPHERE>(ec, vi, vo, m, s); break;
-      case ART_PARABOLA: launch_element<ART_PARABOLA>(ec, vi, vo, m, s); break;
-      case ART_TORUS: launch_element<ART_TORUS>(ec, vi, vo, m, s); break;
-      case ART_ELLIPSOID: launch_element<ART_ELLIPSOID>(ec, vi, vo, m, s); break;
-      case ART_CYLINDER: launch_element<ART_CYLINDER>(ec, vi, vo, m, s); break;
-      default: launch_element<ART_MASK>(ec, vi, vo, m, s); break;
-    }
+    const int rc = f(off, (n - off < chunk) ? n - off : chunk);
+    if (rc) return rc;
   }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_trace_element launch");
   return ART_OK;
 }
 
-// launch one segment (<= 8 elements) of one or many chains
-namespace {
+// the entry points' epilogue: a launch that failed in this call (hipGetLastError) -> ART_ERR_HIP
+int launched(const char* what) {
+  const hipError_t err = hipGetLastError();
+  return (err != hipSuccess) ? fail_hip(err, what) : ART_OK;
+}
+
 #ifdef ART_ZERN_LDS
 inline size_t zern_lds_bytes(const ChainArgs& a) {
   size_t d = 0;
@@ -2333,10 +2249,138 @@ inline size_t chain_dyn_lds() {
   }();
   return v;
 }
-// (the fused kernel WITH defects stays at 4 waves: 112 VGPRs without spills; at 5 waves it spills 15 dwords and
-// measured 0.335 instead of 0.31 ms per 1e7 rays on C5, tools/r02_exp17.sh)
+
+// One-element chains with defects whose optic is a plane, a sphere or a parabola (what a deformed mirror usually is: C5)
+// run a body compiled for that kind (k_trace_*1): no run-time switch, no torus state -- 98 VGPRs instead of 118.
+// ART_CHAIN_SPECIAL=0 switches it off, ART_CHAIN_SPECIAL_WAVES=5 selects the 5-wave build (96 VGPRs, one 8-byte spill per
+// ray in front of the stores); read per launch: the A/B tool alternates them inside one process.
+inline int special_waves() {
+  const char* e = getenv("ART_CHAIN_SPECIAL");
+  if (e && e[0] == '0') return 0;
+  const char* w = getenv("ART_CHAIN_SPECIAL_WAVES");
+  return (w && atoi(w) == 5) ? 5 : 4;
+}
+inline bool special_kind(const int kind) { return kind == ART_PLANE || kind == ART_SPHERE || kind == ART_PARABOLA; }
+static_assert(ART_PLANE == 0 && ART_SPHERE == 1 && ART_PARABOLA == 2, "special kinds index the dispatchers' tables");
+
+// The body of a fused launch: kSpecial k_trace_*1<kind, waves>, kDefect k_trace_*<true, 4>, kTwoRay k_trace_*2<false, 4>,
+// kOneRay k_trace_*<false, waves>.
+enum class Body { kSpecial, kDefect, kTwoRay, kOneRay };
+struct BodyChoice {
+  Body body;
+  int waves;   // waves per SIMD of the build (__launch_bounds__)
+  int kind;    // kSpecial: the optic kind the body is compiled for
+};
+// The one rule of both entry points: art_trace_chain* (descriptors in kernel arguments, launch_chain_body) and
+// art_trace_scene (table segments, launch_scene_body).  Where the two paths differ they do so on purpose, as measured:
+//   * has_mask -- chain path: a MASK element in this segment; scene path: kFlagMask, or kFlagSharedIn && n_chains > 1 &&
+//     S == 1 (one segment of chains that share their input: the XCD-grouped grid, where the two-ray body gains too);
+//   * kind1, the kind a special body would be compiled for (ART_KIND_DYN: none) -- chain path: m == 1, !kDefectLoop and special_kind;
+//     scene path: n_elems == 1 and the same kind in every chain;
+//   * dynamic LDS -- chain path: chain_dyn_lds() for the bodies without defects, zern_lds_bytes() (ART_ZERN_LDS) for the
+//     defect body, 0 for the special one; scene path: 0;
+//   * kDefectLoop builds (ART_ZERN_LDS) -- chain path: the defect body runs the persistent grid_for(n) with xmap 0; scene
+//     path: scenes with defects are refused;
+//   * a chain of ONE element without a read-out never gets here: trace_chain_impl hands it to art_trace_element.
+// The knobs are read at every call (chain_rpl, chain_waves, special_waves): the A/B tools and the GPU tests switch them
+// inside one process.
+BodyChoice choose_body(const bool defects, const bool has_mask, const int kind1) {
+  if (defects) {
+    const int sw = special_kind(kind1) ? special_waves() : 0;
+    if (sw) return {Body::kSpecial, sw, kind1};
+    // (the fused kernel WITH defects stays at 4 waves: 112 VGPRs without spills; at 5 waves it spills 15 dwords and
+    // measured 0.335 instead of 0.31 ms per 1e7 rays on C5, tools/r02_exp17.sh.  It keeps the one-ray body: the two-ray
+    // one needs 133 VGPRs = 3 waves per SIMD there and measured +1.6 % on C5 with the read-out, the same without;
+    // profiles/r03_experiments.md)
+    return {Body::kDefect, 4, ART_KIND_DYN};
+  }
+  // two rays per lane: 107 VGPRs, 4 waves per SIMD (3 and 5 measured the same or worse, tools/ab_kernel.py)
+  if (chain_rpl(has_mask) == 2) return {Body::kTwoRay, 4, ART_KIND_DYN};
+  return {Body::kOneRay, chain_waves() == 6 ? 6 : 5, ART_KIND_DYN};
+}
+
+// The choice -> its kernel, and the launch.  Descriptors in kernel arguments (one chain, `n` rays of one launch):
+void launch_chain_body(const BodyChoice& c, const ChainArgs& a, const int64_t n, const int tiles, const int xm,
+                       const size_t zern_lds, hipStream_t s) {
+  typedef void (*K)(const ChainArgs, const int64_t, const int);
+  const K special[2][3] = {{k_trace_chain1<ART_PLANE, 4>, k_trace_chain1<ART_SPHERE, 4>, k_trace_chain1<ART_PARABOLA, 4>},
+                           {k_trace_chain1<ART_PLANE, 5>, k_trace_chain1<ART_SPHERE, 5>, k_trace_chain1<ART_PARABOLA, 5>}};
+  const K k = (c.body == Body::kSpecial) ? special[c.waves - 4][c.kind]
+              : (c.body == Body::kDefect) ? k_trace_chain<true, 4>
+              : (c.body == Body::kTwoRay) ? k_trace_chain2<false, 4>
+              : (c.waves == 6) ? k_trace_chain<false, 6> : k_trace_chain<false, 5>;
+  const bool loop = kDefectLoop && c.body == Body::kDefect;
+  const size_t lds = (c.body == Body::kSpecial) ? 0 : (c.body == Body::kDefect ? zern_lds : chain_dyn_lds());
+  hipLaunchKernelGGL(k, dim3(loop ? grid_for(n) : tiles), dim3(kBlock), lds, s, a, n, loop ? 0 : xm);
+}
+// ... in a segment of the scene table (rays [first, first + n) of every chain, grid and shape from art_trace_scene):
+void launch_scene_body(const BodyChoice& c, const dim3 g, const ChainArgs* seg, const int64_t first, const int64_t n,
+                       const int xarg, const int shape, hipStream_t s) {
+  typedef void (*K)(const ChainArgs*, const int64_t, const int64_t, const int, const int);
+  const K special[2][3] = {{k_trace_scene1<ART_PLANE, 4>, k_trace_scene1<ART_SPHERE, 4>, k_trace_scene1<ART_PARABOLA, 4>},
+                           {k_trace_scene1<ART_PLANE, 5>, k_trace_scene1<ART_SPHERE, 5>, k_trace_scene1<ART_PARABOLA, 5>}};
+  const K k = (c.body == Body::kSpecial) ? special[c.waves - 4][c.kind]
+              : (c.body == Body::kDefect) ? k_trace_scene<true, 4>
+              : (c.body == Body::kTwoRay) ? k_trace_scene2<false, 4>
+              : (c.waves == 6) ? k_trace_scene<false, 6> : k_trace_scene<false, 5>;
+  hipLaunchKernelGGL(k, g, dim3(kBlock), 0, s, seg, first, n, xarg, shape);
+}
 
 }  // namespace
+
+// =================================================================================================== C ABI
+extern "C" {
+
+int art_abi_version(void) { return ART_ABI_VERSION; }
+
+const char* art_last_error(void) { return g_err; }
+
+int art_device_count(void) {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail_hip(e, "hipGetDeviceCount");
+  }
+  int good = 0;
+  for (int i = 0; i < n; ++i) {
+    hipDeviceProp_t p;
+    if (hipGetDeviceProperties(&p, i) == hipSuccess && strncmp(p.gcnArchName, "gfx950", 6) == 0) ++good;
+  }
+  return good;
+}
+
+int art_trace_element(const ArtElementDesc* e, const ArtBundleView* in, const ArtBundleView* out, int64_t n,
+                      void* stream) {
+  int rc = check_elem(e);
+  if (rc) return rc;
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (n == 0) return ART_OK;  // an empty bundle has no arrays to point to
+  if (!view_ok(in) || !view_ok(out)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
+  hipStream_t s = (hipStream_t)stream;
+  ArtElementDesc ec = *e;
+  art::prepare_element(ec);
+  per_launch(n, [&](const int64_t off, const int64_t m) {
+    const ArtBundleView vi = view_at(*in, off), vo = view_at(*out, off);
+    if (ec.flags & ART_FLAG_ZERN_RECURRENCE) {
+      ElemArg ea;
+      ea.e[0] = ec;
+      hipLaunchKernelGGL(k_trace_element_zrec, dim3(grid_stream(m)), dim3(kBlock), 0, s, ea, vi, vo, m);
+      return ART_OK;
+    }
+    switch (ec.kind) {
+      case ART_PLANE: launch_element<ART_PLANE>(ec, vi, vo, m, s); break;
+      case ART_SPHERE: launch_element<ART_SPHERE>(ec, vi, vo, m, s); break;
+      case ART_PARABOLA: launch_element<ART_PARABOLA>(ec, vi, vo, m, s); break;
+      case ART_TORUS: launch_element<ART_TORUS>(ec, vi, vo, m, s); break;
+      case ART_ELLIPSOID: launch_element<ART_ELLIPSOID>(ec, vi, vo, m, s); break;
+      case ART_CYLINDER: launch_element<ART_CYLINDER>(ec, vi, vo, m, s); break;
+      default: launch_element<ART_MASK>(ec, vi, vo, m, s); break;
+    }
+    return ART_OK;
+  });
+  return launched("art_trace_element launch");
+}
 
 static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const ArtBundleView* in,
                             const ArtBundleView* outs, const ArtChainReadout* ro, int64_t n, void* stream) {
@@ -2358,10 +2402,8 @@ static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const 
   }
   if (n == 0) {
     if (ro) {   // nothing to trace: the statistics are the reduction identities
-      if (ro->sums) launch_sums_fold_one(ro->scratch, ro->out24, 0, s);
-      else launch_fold_one(ro->scratch, ro->out24, 0, s);
-      hipError_t e0 = hipGetLastError();
-      if (e0 != hipSuccess) return fail_hip(e0, "art_trace_chain_readout launch");
+      launch_fold(ro->sums, nullptr, 1, ro->scratch, ro->out24, 0, s);
+      return launched("art_trace_chain_readout launch");
     }
     return ART_OK;  // an empty bundle has no arrays to point to
   }
@@ -2377,10 +2419,7 @@ static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const 
     // the chunk's last bundle is the next chunk's input: it must exist
     if (!view_ok(&outs[k0 + m - 1])) return fail(ART_ERR_BAD_ARG, "chains longer than 8 need a view every 8th element");
   }
-  const int waves = chain_waves();
-  const int64_t chunk = max_rays_per_launch();
-  for (int64_t off = 0; off < n; off += chunk) {
-    const int64_t cnt = (n - off < chunk) ? n - off : chunk;
+  const int rc = per_launch(n, [&](const int64_t off, const int64_t cnt) {
     ArtBundleView cur = view_at(*in, off);
     for (int k0 = 0; k0 < n_elems; k0 += kChainMax) {
       ChainArgs a;
@@ -2388,11 +2427,13 @@ static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const 
       const int m = (n_elems - k0 < kChainMax) ? n_elems - k0 : kChainMax;
       a.n_elems = m;
       a.in = cur;
+      bool has_mask = false;
       for (int k = 0; k < m; ++k) {
         a.e[k] = elems[k0 + k];
         art::prepare_element(a.e[k]);
         a.out[k] = view_at(outs[k0 + k], off);
         if (a.e[k].n_defects > 0 || a.e[k].n_grid > 0) a.flags |= art::kFlagDefects;
+        has_mask = has_mask || a.e[k].kind == ART_MASK;
       }
       const bool tail = ro && k0 + m == n_elems;       // the read-out rides on the chain's last fused launch
       if (tail) {
@@ -2404,37 +2445,17 @@ static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const 
       lds = zern_lds_bytes(a);
       if (lds > 64 * 1024) return fail(ART_ERR_UNSUPPORTED, "ART_ZERN_LDS build: Zernike tables of one fused launch exceed 64 KiB");
 #endif
+      const BodyChoice c = choose_body((a.flags & art::kFlagDefects) != 0, has_mask,
+                                       (!kDefectLoop && m == 1) ? a.e[0].kind : ART_KIND_DYN);
       const int xm = xcd_map();
-      bool has_mask = false;
-      for (int k = 0; k < m; ++k) has_mask = has_mask || a.e[k].kind == ART_MASK;
-      // (chains WITH defects keep the one-ray body: the two-ray one needs 133 VGPRs = 3 waves per SIMD there and measured
-      // +1.6 % on C5 with the read-out, the same without; profiles/r03_experiments.md)
-      const bool two = !(a.flags & art::kFlagDefects) && chain_rpl(has_mask) == 2;
-      const dim3 g(grid_stream_mapped(two ? (cnt + 1) / 2 : cnt, xm)), b(kBlock);
-      const int sw = (!kDefectLoop && m == 1 && special_kind(a.e[0].kind)) ? special_waves() : 0;
-      if ((a.flags & art::kFlagDefects) && sw == 5)
-        launch_chain1<5>(a.e[0].kind, dim3(grid_stream_mapped(cnt, xm)), s, a, cnt, xm);
-      else if ((a.flags & art::kFlagDefects) && sw == 4)
-        launch_chain1<4>(a.e[0].kind, dim3(grid_stream_mapped(cnt, xm)), s, a, cnt, xm);
-      else if (a.flags & art::kFlagDefects)
-        hipLaunchKernelGGL((k_trace_chain<true, 4>), dim3(kDefectLoop ? grid_for(cnt) : grid_stream_mapped(cnt, xm)), b, lds,
-                           s, a, cnt, kDefectLoop ? 0 : xm);
-      else if (two)       // 107 VGPRs: 4 waves per SIMD (3 and 5 measured the same or worse, tools/ab_kernel.py)
-        hipLaunchKernelGGL((k_trace_chain2<false, 4>), g, b, chain_dyn_lds(), s, a, cnt, xm);
-      else if (waves == 6)
-        hipLaunchKernelGGL((k_trace_chain<false, 6>), g, b, chain_dyn_lds(), s, a, cnt, xm);
-      else
-        hipLaunchKernelGGL((k_trace_chain<false, 5>), g, b, chain_dyn_lds(), s, a, cnt, xm);
-      if (tail && ro->sums)
-        launch_sums_fold_one(ro->scratch, ro->out24, analysis_tiles(cnt), s);
-      else if (tail)
-        launch_fold_one(ro->scratch, ro->out24, (int64_t)g.x, s);
+      const int tiles = grid_stream_mapped(c.body == Body::kTwoRay ? (cnt + 1) / 2 : cnt, xm);
+      launch_chain_body(c, a, cnt, tiles, xm, lds, s);
+      if (tail) launch_fold(ro->sums, nullptr, 1, ro->scratch, ro->out24, ro->sums ? analysis_tiles(cnt) : tiles, s);
       cur = a.out[m - 1];
     }
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_trace_chain launch");
-  return ART_OK;
+    return ART_OK;
+  });
+  return rc ? rc : launched("art_trace_chain launch");
 }
 
 int art_trace_chain(const ArtElementDesc* elems, int32_t n_elems, const ArtBundleView* in, const ArtBundleView* outs,
@@ -2490,29 +2511,23 @@ int art_trace_scene(const void* image_dev, const void* image_host, int64_t n, vo
   hipStream_t s = (hipStream_t)stream;
   const ChainArgs* tab = art::scene_table(image_dev);
   const int S = art::scene_segments(n_elems);
+  const bool sums = (flags & art::kFlagSums) != 0, tails = sums || (flags & art::kFlagReadout);
   if (n == 0) {
-    if (flags & art::kFlagSums)
-      launch_sums_fold_scene(tab + (int64_t)(S - 1) * n_chains, n_chains, 0, s);
-    else if (flags & art::kFlagReadout)
-      launch_fold_scene(tab + (int64_t)(S - 1) * n_chains, n_chains, 0, s);
+    if (tails) launch_fold(sums, tab + (int64_t)(S - 1) * n_chains, n_chains, nullptr, nullptr, 0, s);
     return ART_OK;
   }
-  const int waves = chain_waves();
   // one-element scenes with defects whose chains all carry the same simple optic: the body compiled for that kind
-  int kind1 = -1, special1 = 0;
+  int kind1 = ART_KIND_DYN;
   if ((flags & 1) && n_elems == 1) {
     const ChainArgs* ht = art::scene_table(image_host);
     kind1 = ht[0].e[0].kind;
-    for (int c = 1; c < n_chains; ++c) kind1 = (ht[c].e[0].kind == kind1) ? kind1 : -1;
-    special1 = special_kind(kind1) ? special_waves() : 0;
+    for (int c = 1; c < n_chains; ++c) kind1 = (ht[c].e[0].kind == kind1) ? kind1 : ART_KIND_DYN;
   }
-  const int64_t chunk = max_rays_per_launch();
-  for (int64_t off = 0; off < n; off += chunk) {
-    const int64_t cnt = (n - off < chunk) ? n - off : chunk;
+  const BodyChoice c = choose_body((flags & 1) != 0, (flags & art::kFlagMask) != 0 ||
+                                   ((flags & art::kFlagSharedIn) != 0 && n_chains > 1 && S == 1), kind1);
+  per_launch(n, [&](const int64_t off, const int64_t cnt) {
     const int xm = xcd_map();
-    const bool two = !(flags & 1) && chain_rpl((flags & art::kFlagMask) != 0 ||
-                                               ((flags & art::kFlagSharedIn) != 0 && n_chains > 1 && S == 1)) == 2;
-    const int tiles = grid_stream_mapped(two ? (cnt + 1) / 2 : cnt, xm);
+    const int tiles = grid_stream_mapped(c.body == Body::kTwoRay ? (cnt + 1) / 2 : cnt, xm);
     for (int sg = 0; sg < S; ++sg) {
       const ChainArgs* seg = tab + (int64_t)sg * n_chains;
       // chains that share their input (first segment only: later segments read their own hand-over bundles) are
@@ -2525,30 +2540,14 @@ int art_trace_scene(const void* image_dev, const void* image_host, int64_t n, vo
       if (tr == 1 && tiles > 65535) tr = 0;
       if (tr && scene_keep(cnt, (tr & 4) != 0)) tr |= 2;
       if (tr & 4) tr |= n_chains << 8;
-      const dim3 g = (tr & 4) ? dim3((unsigned)(tiles8 * n_chains)) : ((tr & 1) ? dim3(n_chains, tiles) : dim3(tiles, n_chains)),
-                 b(kBlock);
+      const dim3 g = (tr & 4) ? dim3((unsigned)(tiles8 * n_chains)) : ((tr & 1) ? dim3(n_chains, tiles) : dim3(tiles, n_chains));
       const int xarg = (tr & 4) ? tiles : xm;      // (XCD-grouped: the true tile count travels in the mapping's parameter)
-      if ((flags & 1) && special1 == 5)
-        launch_scene1<5>(kind1, g, s, seg, off, cnt, xarg, tr);
-      else if ((flags & 1) && special1 == 4)
-        launch_scene1<4>(kind1, g, s, seg, off, cnt, xarg, tr);
-      else if (flags & 1)
-        hipLaunchKernelGGL((k_trace_scene<true, 4>), g, b, 0, s, seg, off, cnt, xarg, tr);
-      else if (two)
-        hipLaunchKernelGGL((k_trace_scene2<false, 4>), g, b, 0, s, seg, off, cnt, xarg, tr);
-      else if (waves == 6)
-        hipLaunchKernelGGL((k_trace_scene<false, 6>), g, b, 0, s, seg, off, cnt, xarg, tr);
-      else
-        hipLaunchKernelGGL((k_trace_scene<false, 5>), g, b, 0, s, seg, off, cnt, xarg, tr);
-      if ((flags & art::kFlagSums) && sg == S - 1)
-        launch_sums_fold_scene(seg, n_chains, analysis_tiles(cnt), s);
-      else if ((flags & art::kFlagReadout) && sg == S - 1)
-        launch_fold_scene(seg, n_chains, (int64_t)tiles, s);
+      launch_scene_body(c, g, seg, off, cnt, xarg, tr, s);
+      if (tails && sg == S - 1) launch_fold(sums, seg, n_chains, nullptr, nullptr, sums ? analysis_tiles(cnt) : tiles, s);
     }
-  }
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_trace_scene launch");
-  return ART_OK;
+    return ART_OK;
+  });
+  return launched("art_trace_scene launch");
 }
 
 int art_pack_rays(const double* points, const double* vectors, const double* path0, int64_t n, const ArtBundleView* out,
@@ -2558,9 +2557,7 @@ int art_pack_rays(const double* points, const double* vectors, const double* pat
   if (!points || !vectors || !view_ok(out)) return fail(ART_ERR_BAD_ARG, "NULL argument");
   hipLaunchKernelGGL(k_pack_rays, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, points, vectors, path0, n,
                      *out);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_pack_rays launch");
-  return ART_OK;
+  return launched("art_pack_rays launch");
 }
 
 int art_transform_bundle(const double M[9], const double T[3], int32_t rotate_points, const ArtBundleView* in,
@@ -2575,9 +2572,7 @@ int art_transform_bundle(const double M[9], const double T[3], int32_t rotate_po
   memcpy(mt.centre, T, 3 * sizeof(double));
   hipLaunchKernelGGL(k_transform, dim3(grid_stream(n)), dim3(kBlock), 0, (hipStream_t)stream, mt, (int)rotate_points, *in,
                      *out, n);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_transform_bundle launch");
-  return ART_OK;
+  return launched("art_transform_bundle launch");
 }
 
 int art_detector(const ArtDetectorDesc* d, const ArtBundleView* b, int64_t n, double* p3x, double* p3y, double* p3z,
@@ -2591,9 +2586,7 @@ int art_detector(const ArtDetectorDesc* d, const ArtBundleView* b, int64_t n, do
   if (n == 0) return ART_OK;
   hipLaunchKernelGGL(k_detector, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, *d, *b, n, p3x, p3y, p3z, X,
                      Y, opl);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_detector launch");
-  return ART_OK;
+  return launched("art_detector launch");
 }
 
 int art_detector_readout(const ArtDetectorDesc* d, const ArtBundleView* b, const double* w, int64_t n, double cx,
@@ -2608,9 +2601,7 @@ int art_detector_readout(const ArtDetectorDesc* d, const ArtBundleView* b, const
     // an empty shard must not pollute a cross-rank fold: the final kernel over zero partials writes the reduction
     // identities (0 for sums, +inf / -inf for the min / max slots 2-5 and 12-13)
     hipLaunchKernelGGL(k_readout_final, dim3(kReadoutSlots), dim3(kBlock), 0, s, scratch, 0, out24);
-    hipError_t e0 = hipGetLastError();
-    if (e0 != hipSuccess) return fail_hip(e0, "art_detector_readout launch");
-    return ART_OK;
+    return launched("art_detector_readout launch");
   }
   if (!view_ok(b)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
   // one launch per <= 2^28 rays (32-bit buffer offsets); every launch leaves one partial per workgroup, all of
@@ -2619,8 +2610,7 @@ int art_detector_readout(const ArtDetectorDesc* d, const ArtBundleView* b, const
   const int64_t launches = (n + chunk - 1) / chunk;
   if (launches > 8) return fail(ART_ERR_UNSUPPORTED, "more than 2^31 rays in one read-out");
   int nb_total = 0;
-  for (int64_t off = 0; off < n; off += chunk) {
-    const int64_t m = (n - off < chunk) ? n - off : chunk;
+  per_launch(n, [&](const int64_t off, const int64_t m) {
     const int64_t want = ((m + 1) / 2 + kBlock - 1) / kBlock;      // two slots per thread
     const int64_t cap = readout_block_cap(launches);
     const int nb = (int)(want < 1 ? 1 : (want > cap ? cap : want));
@@ -2630,11 +2620,10 @@ int art_detector_readout(const ArtDetectorDesc* d, const ArtBundleView* b, const
                        X ? X + off : nullptr, Y ? Y + off : nullptr, opl ? opl + off : nullptr,
                        scratch + (int64_t)nb_total * kReadoutSlots);
     nb_total += nb;
-  }
+    return ART_OK;
+  });
   hipLaunchKernelGGL(k_readout_final, dim3(kReadoutSlots), dim3(kBlock), 0, s, scratch, nb_total, out24);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_detector_readout launch");
-  return ART_OK;
+  return launched("art_detector_readout launch");
 }
 
 int art_detector_scan_moments(const ArtDetectorDesc* d, const ArtBundleView* b, const double* w, int64_t n, double co,
@@ -2648,14 +2637,11 @@ int art_detector_scan_moments(const ArtDetectorDesc* d, const ArtBundleView* b, 
     return ART_OK;
   }
   if (!view_ok(b)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
-  int64_t nbk = (n + kBlock - 1) / kBlock;
-  const int nb = (int)(nbk > kRedBlocks ? kRedBlocks : nbk);
+  const int nb = red_blocks(n);
   if (w) hipLaunchKernelGGL(k_scan_moments_partial<true>, dim3(nb), dim3(kBlock), 0, s, *d, *b, w, n, co, span, scratch);
   else hipLaunchKernelGGL(k_scan_moments_partial<false>, dim3(nb), dim3(kBlock), 0, s, *d, *b, w, n, co, span, scratch);
   hipLaunchKernelGGL(k_scan_moments_final, dim3(kScanSlots), dim3(kBlock), 0, s, scratch, nb, out32);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_detector_scan_moments launch");
-  return ART_OK;
+  return launched("art_detector_scan_moments launch");
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }
@@ -2665,14 +2651,11 @@ int art_detector_stats(const uint8_t* alive, const double* X, const double* Y, c
   if (!alive || !scratch || !out16) return fail(ART_ERR_BAD_ARG, "alive/scratch/out16 must not be NULL");
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   hipStream_t s = (hipStream_t)stream;
-  int64_t b = (n + kBlock - 1) / kBlock;
-  const int nb = (int)(b < 1 ? 1 : (b > kRedBlocks ? kRedBlocks : b));
+  const int nb = red_blocks(n);
   if (w) hipLaunchKernelGGL(k_stats_partial<true>, dim3(nb), dim3(kBlock), 0, s, alive, X, Y, opl, w, n, scratch);
   else hipLaunchKernelGGL(k_stats_partial<false>, dim3(nb), dim3(kBlock), 0, s, alive, X, Y, opl, w, n, scratch);
   hipLaunchKernelGGL(k_stats_final, dim3(kRedSlots), dim3(kBlock), 0, s, scratch, nb, out16);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_detector_stats launch");
-  return ART_OK;
+  return launched("art_detector_stats launch");
 }
 
 int art_detector_moments(const uint8_t* alive, const double* X, const double* Y, const double* opl, const double* w,
@@ -2680,28 +2663,22 @@ int art_detector_moments(const uint8_t* alive, const double* X, const double* Y,
   if (!alive || !scratch || !out8) return fail(ART_ERR_BAD_ARG, "alive/scratch/out8 must not be NULL");
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   hipStream_t s = (hipStream_t)stream;
-  int64_t b = (n + kBlock - 1) / kBlock;
-  const int nb = (int)(b < 1 ? 1 : (b > kRedBlocks ? kRedBlocks : b));
+  const int nb = red_blocks(n);
   if (w) hipLaunchKernelGGL(k_moments_partial<true>, dim3(nb), dim3(kBlock), 0, s, alive, X, Y, opl, w, n, cx, cy, co, scratch);
   else hipLaunchKernelGGL(k_moments_partial<false>, dim3(nb), dim3(kBlock), 0, s, alive, X, Y, opl, w, n, cx, cy, co, scratch);
   hipLaunchKernelGGL(k_sums_final, dim3(kSumSlots), dim3(kBlock), 0, s, scratch, nb, out8);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_detector_moments launch");
-  return ART_OK;
+  return launched("art_detector_moments launch");
 }
 
 int art_bundle_sums(const ArtBundleView* bv, const double* w, int64_t n, double* scratch, double* out8, void* stream) {
   if (!view_ok(bv) || !scratch || !out8) return fail(ART_ERR_BAD_ARG, "bundle/scratch/out8 must not be NULL");
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   hipStream_t s = (hipStream_t)stream;
-  int64_t b = (n + kBlock - 1) / kBlock;
-  const int nb = (int)(b < 1 ? 1 : (b > kRedBlocks ? kRedBlocks : b));
+  const int nb = red_blocks(n);
   if (w) hipLaunchKernelGGL(k_bundle_sums_partial<true>, dim3(nb), dim3(kBlock), 0, s, *bv, w, n, scratch);
   else hipLaunchKernelGGL(k_bundle_sums_partial<false>, dim3(nb), dim3(kBlock), 0, s, *bv, w, n, scratch);
   hipLaunchKernelGGL(k_sums_final, dim3(kSumSlots), dim3(kBlock), 0, s, scratch, nb, out8);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_bundle_sums launch");
-  return ART_OK;
+  return launched("art_bundle_sums launch");
 }
 
 static int gaussian_impl(const ArtBundleView* bv, const double axis[3], const double* axis_sums, double fraction, int64_t n,
@@ -2730,8 +2707,7 @@ static int gaussian_impl(const ArtBundleView* bv, const double axis[3], const do
   if (!(fraction > 0.0 && fraction < 1.0)) return fail(ART_ERR_BAD_ARG, "fraction must be in (0, 1)");
   if (n == 0) return ART_OK;
   hipStream_t s = (hipStream_t)stream;
-  int64_t b = (n + kBlock - 1) / kBlock;
-  const int nb = (int)(b < 1 ? 1 : (b > kRedBlocks ? kRedBlocks : b));
+  const int nb = red_blocks(n);
   const Axis3 ax = {axis[0], axis[1], axis[2]};
   // partials in scratch[0 .. nb*8), the two maxima right behind them
   double* maxima = scratch + (int64_t)kRedBlocks * kSumSlots;
@@ -2739,9 +2715,7 @@ static int gaussian_impl(const ArtBundleView* bv, const double axis[3], const do
   hipLaunchKernelGGL(k_gauss_max_final, dim3(1), dim3(kBlock), 0, s, scratch, nb, maxima);
   hipLaunchKernelGGL(k_gauss_weights, dim3(grid_for(n)), dim3(kBlock), 0, s, *bv, ax, axis_sums, -0.5 * log(fraction), maxima, n,
                      w_out);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_gaussian_intensity launch");
-  return ART_OK;
+  return launched("art_gaussian_intensity launch");
 }
 
 int art_bundle_max_angle(const ArtBundleView* bv, const double axis[3], int64_t n, double* scratch, double* out2,
@@ -2755,17 +2729,14 @@ int art_bundle_max_angle(const ArtBundleView* bv, const double axis[3], int64_t 
     return ART_OK;
   }
   if (!view_ok(bv)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
-  int64_t b = (n + kBlock - 1) / kBlock;
-  const int nb = (int)(b > kRedBlocks ? kRedBlocks : b);
+  const int nb = red_blocks(n);
   const Axis3 ax = {axis[0], axis[1], axis[2]};
   double* tmp = scratch + (int64_t)kRedBlocks * kSumSlots;   // 8 doubles: the folded partials
   hipLaunchKernelGGL(k_gauss_max_partial, dim3(nb), dim3(kBlock), 0, s, *bv, ax, (const double*)nullptr, n, scratch);
   hipLaunchKernelGGL(k_gauss_max_final, dim3(1), dim3(kBlock), 0, s, scratch, nb, tmp);
   hipError_t e1 = hipMemcpyAsync(out2, tmp, 2 * sizeof(double), hipMemcpyDeviceToDevice, s);
   if (e1 != hipSuccess) return fail_hip(e1, "hipMemcpyAsync");
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_bundle_max_angle launch");
-  return ART_OK;
+  return launched("art_bundle_max_angle launch");
 }
 
 int64_t art_compact_scratch_ints(int64_t n) {
@@ -2791,9 +2762,7 @@ int art_compact(const uint8_t* alive, int64_t n, int32_t* block_counts, int64_t*
   hipLaunchKernelGGL(k_compact_count, dim3((unsigned)tiles), dim3(kBlock), 0, s, alive, n, block_counts);
   hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, s, block_counts, tiles, count_out, offsets);
   hipLaunchKernelGGL(k_compact_scatter, dim3((unsigned)tiles), dim3(kBlock), 0, s, alive, n, offsets, idx_out);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_compact launch");
-  return ART_OK;
+  return launched("art_compact launch");
 }
 
 int64_t art_survivor_bytes(int64_t count, int32_t dense) {
@@ -2827,9 +2796,7 @@ int art_pack_survivors(const uint8_t* alive, int64_t n, const double* X, const d
   hipLaunchKernelGGL(k_survivor_header, dim3(1), dim3(64), 0, s, total, n, number ? 0 : 1, reinterpret_cast<int64_t*>(send));
   hipLaunchKernelGGL(k_survivor_scatter, dim3((unsigned)tiles), dim3(kBlock), 0, s, alive, n, offsets, X, Y, opl, number,
                      first, step, reinterpret_cast<unsigned char*>(send));
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_pack_survivors launch");
-  return ART_OK;
+  return launched("art_pack_survivors launch");
 }
 
 int art_make_source(int32_t kind, double size, const double rot[9], const double S[3], int64_t first, int64_t n,
@@ -2850,9 +2817,7 @@ int art_make_source_strided(int32_t kind, double size, const double rot[9], cons
   memcpy(rs.centre, S, 3 * sizeof(double));
   hipLaunchKernelGGL(k_make_source, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, kind, size, rs, first, step,
                      n, n_total, *out);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_make_source launch");
-  return ART_OK;
+  return launched("art_make_source launch");
 }
 
 int art_exchange_pack(const double* stats24, const double* X, const double* Y, const double* opl, const uint8_t* alive,
@@ -2862,18 +2827,14 @@ int art_exchange_pack(const double* stats24, const double* X, const double* Y, c
   const int64_t work = k > kReadoutSlots ? k : kReadoutSlots;
   hipLaunchKernelGGL(k_exchange_pack, dim3((unsigned)((work + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
                      stats24, X, Y, opl, alive, slots, k, send);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_exchange_pack launch");
-  return ART_OK;
+  return launched("art_exchange_pack launch");
 }
 
 int art_exchange_fold(const double* recv, int32_t world, int64_t stride_doubles, double* stats_out24, void* stream) {
   if (!recv || !stats_out24) return fail(ART_ERR_BAD_ARG, "recv/stats_out24 must not be NULL");
   if (world < 1 || stride_doubles < kReadoutSlots) return fail(ART_ERR_BAD_ARG, "bad world size or stride");
   hipLaunchKernelGGL(k_exchange_fold, dim3(1), dim3(64), 0, (hipStream_t)stream, recv, world, stride_doubles, stats_out24);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_exchange_fold launch");
-  return ART_OK;
+  return launched("art_exchange_fold launch");
 }
 
 int art_make_extended_source(double radius, double divergence, int64_t n_points, int64_t rays_per_point,
@@ -2889,9 +2850,7 @@ int art_make_extended_source(double radius, double divergence, int64_t n_points,
   memcpy(rs.centre, S, 3 * sizeof(double));
   hipLaunchKernelGGL(k_make_extended_source, dim3(grid_for(n)), dim3(kBlock), 0, (hipStream_t)stream, radius,
                      divergence, n_points, rays_per_point, rs, first, n, *out);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_make_extended_source launch");
-  return ART_OK;
+  return launched("art_make_extended_source launch");
 }
 
 int art_trace_guides(const ArtElementDesc* elems, int32_t count, double* rays, uint8_t* alive, void* stream) {
@@ -2913,9 +2872,7 @@ int art_trace_guides(const ArtElementDesc* elems, int32_t count, double* rays, u
   hipStream_t s = (hipStream_t)stream;
   if (defects) hipLaunchKernelGGL(k_trace_guides<true>, dim3(1), dim3(64), 0, s, ga, rays, alive, (int)count);
   else hipLaunchKernelGGL(k_trace_guides<false>, dim3(1), dim3(64), 0, s, ga, rays, alive, (int)count);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_trace_guides launch");
-  return ART_OK;
+  return launched("art_trace_guides launch");
 }
 
 // scratch layout of art_analyse_bundles: [job][kSumRows rows x ntiles + chunk totals] | [job][kAnaSumsPad] | [job][P][kAnaMom] | [job][kAnaPlace]
@@ -2978,9 +2935,7 @@ int art_analyse_bundles(const ArtAnalysisJob* jobs_dev, const ArtAnalysisJob* jo
     }
   }
   hipLaunchKernelGGL(k_analysis_fold, dim3(kAnaMom - 1, n_jobs), dim3(kBlock), 0, s, jobs_dev, P, mom, out);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_analyse_bundles launch");
-  return ART_OK;
+  return launched("art_analyse_bundles launch");
 }
 
 int art_survivor_finish(const double* stats24, int64_t n, void* send, double* xhdr, void* stream) {
@@ -2988,18 +2943,14 @@ int art_survivor_finish(const double* stats24, int64_t n, void* send, double* xh
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   if (((uintptr_t)send & 15u) != 0) return fail(ART_ERR_BAD_ARG, "send buffer must be 16-byte aligned");
   hipLaunchKernelGGL(k_survivor_finish, dim3(1), dim3(64), 0, (hipStream_t)stream, stats24, n, reinterpret_cast<int64_t*>(send), xhdr);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_survivor_finish launch");
-  return ART_OK;
+  return launched("art_survivor_finish launch");
 }
 
 int art_survivor_xheader(const void* send, const double* stats24, double* xhdr, void* stream) {
   if (!send || !xhdr) return fail(ART_ERR_BAD_ARG, "NULL argument");
   if (((uintptr_t)send & 7u) != 0) return fail(ART_ERR_BAD_ARG, "send buffer must be 8-byte aligned");
   hipLaunchKernelGGL(k_survivor_xheader, dim3(1), dim3(64), 0, (hipStream_t)stream, reinterpret_cast<const int64_t*>(send), stats24, xhdr);
-  hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return fail_hip(err, "art_survivor_xheader launch");
-  return ART_OK;
+  return launched("art_survivor_xheader launch");
 }
 
 }  // extern "C"
