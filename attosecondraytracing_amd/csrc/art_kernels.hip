@@ -11,6 +11,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "art_device.h"
 #include "art_scene.h"
@@ -247,25 +248,38 @@ __device__ __forceinline__ void st_nt(T* p, const T v) {
 constexpr int kRedUnroll = 4;
 // ------------------------------------------------------------------------------------------- reductions
 // Deterministic: fixed grid, each lane accumulates its grid-stride slice, wave shuffle tree, LDS across the
-// 4 waves, one partial per workgroup into `scratch`, then fold_slot(): one workgroup per statistic folds the
-// partials in a fixed order.
+// 4 waves, one partial per workgroup into `scratch`, then k_fold_partials: one workgroup per statistic folds the
+// partials in a fixed order (fold_range).
 constexpr int kRedBlocks = 1024;
 inline int red_blocks(int64_t n) {   // workgroups of a reduction over n slots: one per 256, between 1 and kRedBlocks
   const int64_t b = (n + kBlock - 1) / kBlock;
   return (int)(b < 1 ? 1 : (b > kRedBlocks ? kRedBlocks : b));
 }
-constexpr int kRedSlots = 16;
+constexpr int kRedSlots = 16;       // art_detector_stats
 constexpr int kReadoutSlots = 24;   // art_detector_readout / fused chain read-out statistics
 constexpr int kUsedSlots = 22;      // slots 22, 23 are reserved (always 0): the fused tail writes no partials for them
+constexpr int kSumSlots = 8;        // art_bundle_sums, art_detector_moments
+constexpr int kScanSlots = 33;      // art_detector_scan_moments
+constexpr int kMaxSlots = 2;        // the max pair: largest angle to the axis, largest distance from the origin
 
 enum RedOp { RSUM = 0, RMIN = 1, RMAX = 2 };
 
+__device__ __forceinline__ double fold_op(const double a, const double b, const int op_k) {
+  return (op_k == RSUM) ? a + b : (op_k == RMIN ? fmin(a, b) : fmax(a, b));
+}
+constexpr double red_ident(const int op_k) { return (op_k == RSUM) ? 0.0 : (op_k == RMIN ? INFINITY : -INFINITY); }
+// The operator of each slot of a layout: a function of the slot, computed where it is used (a run-time indexed local
+// array of operators lives in scratch memory).  stat_op: the 24 read-out statistics (art_hip.h, art_detector_readout);
+// the 16 of art_detector_stats are its first 16.  The analysis moments have ana_mom_op.
+constexpr int stat_op(const int k) {   // minima in slots 2, 4, 12, maxima in 3, 5, 13 (a bit mask each: no branches)
+  return ((0x1014 >> k) & 1) ? RMIN : (((0x2028 >> k) & 1) ? RMAX : RSUM);
+}
+constexpr int sum_op(int) { return RSUM; }   // kSumSlots, kScanSlots
+constexpr int max_op(int) { return RMAX; }   // kMaxSlots
+
 __device__ __forceinline__ double wave_reduce(double v, int op) {
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_down(v, off, 64);
-    v = (op == RSUM) ? v + o : (op == RMIN ? fmin(v, o) : fmax(v, o));
-  }
+  for (int off = 32; off > 0; off >>= 1) v = fold_op(v, __shfl_down(v, off, 64), op);
   return v;
 }
 
@@ -474,29 +488,9 @@ __device__ __forceinline__ void tile_sums_store_pairs(const double totA, const d
   }
 }
 
-template <int NS>
-__device__ __forceinline__ void block_reduce_store(double (&acc)[NS], const int (&ops)[NS], double* dst) {
-  __shared__ double s[kBlock / 64][NS];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < NS; ++k) {
-    const double v = wave_reduce(acc[k], ops[k]);
-    if (lane == 0) s[w][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NS) {
-    const int k = threadIdx.x;
-    double v = s[0][k];
-    for (int j = 1; j < kBlock / 64; ++j)
-      v = (ops[k] == RSUM) ? v + s[j][k] : (ops[k] == RMIN ? fmin(v, s[j][k]) : fmax(v, s[j][k]));
-    dst[k] = v;
-  }
-}
-
-// The same with the operator of slot k given by a function (computed, not looked up: a run-time indexed local array of
-// operators lives in scratch memory).
+// A workgroup's partial of each slot (operator op_of(k)) into dst[0 .. NS): wave shuffle trees, then the 4 waves in order
 template <int NS, typename F>
-__device__ __forceinline__ void block_reduce_store_f(double (&acc)[NS], F op_of, double* dst) {
+__device__ __forceinline__ void block_reduce_store(double (&acc)[NS], F op_of, double* dst) {
   __shared__ double s[kBlock / 64][NS];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
@@ -509,31 +503,51 @@ __device__ __forceinline__ void block_reduce_store_f(double (&acc)[NS], F op_of,
     const int k = threadIdx.x;
     const int op = op_of(k);
     double v = s[0][k];
-    for (int j = 1; j < kBlock / 64; ++j)
-      v = (op == RSUM) ? v + s[j][k] : (op == RMIN ? fmin(v, s[j][k]) : fmax(v, s[j][k]));
+    for (int j = 1; j < kBlock / 64; ++j) v = fold_op(v, s[j][k], op);
     dst[k] = v;
   }
 }
 
-// Final fold of per-block partials laid out [block][ns]: launched with ns blocks, block k folds slot k in a fixed
-// order (thread t takes partials t, t+256, ...; then the shuffle tree) — deterministic, and ns blocks work in
-// parallel instead of one block walking the whole table.
-__device__ __forceinline__ void fold_slot(const double* scratch, const int nblocks, const int ns, const int op_k,
-                                          double* out) {
-  const int k = blockIdx.x;
-  const int op[1] = {op_k};
-  const double ident = (op_k == RSUM) ? 0.0 : (op_k == RMIN ? INFINITY : -INFINITY);
-  double acc[1] = {ident};
-  constexpr int kU = 8;     // loads in flight per thread (one at a time they are that many memory latencies in a row)
-  for (int blk = threadIdx.x; blk < nblocks; blk += kBlock * kU) {
+// THE fold of a sequence of partials, row[p * stride] for p in [lo, hi), in one fixed order: thread t takes p = lo + t,
+// lo + t + B, lo + t + 2B, ... (B threads), then the wave shuffle tree, then the waves in order.  Every thread of the
+// workgroup (a multiple of 64) calls this; thread 0 stores the result.  An empty range leaves the identity of op_k.
+// kU: loads in flight per thread before the first is folded (a thread's ~40 values one load at a time are 40 memory
+// latencies in a row: 17 us per 1e7 rays, measured); it does not change the order.  B: the workgroup size when the
+// caller knows it (a table of per-workgroup partials: fewer than 2^31 of them, so 32-bit indices), 0 = blockDim.x.
+// Constant B and stride leave one pointer with immediate offsets per thread instead of a 64-bit address per load.
+constexpr int kFoldBlock = 1024;
+template <int kU = 8, int B = 0>
+__device__ __forceinline__ void fold_range(const double* row, const int64_t lo, const int64_t hi, const int op_k,
+                                           double* out, const int64_t stride = 1) {
+  using I = typename std::conditional<B == 0, int64_t, int>::type;
+  __shared__ double s[(B ? B : kFoldBlock) / 64];
+  const double ident = red_ident(op_k);
+  double acc = ident;
+  for (I p = (I)lo + threadIdx.x; p < (I)hi; p += (I)(B ? B : blockDim.x) * kU) {
     double v[kU];
 #pragma unroll
-    for (int u = 0; u < kU; ++u) v[u] = (blk + u * kBlock < nblocks) ? scratch[(int64_t)(blk + u * kBlock) * ns + k] : ident;
+    for (int u = 0; u < kU; ++u) {
+      const I q = p + (I)u * (B ? B : blockDim.x);
+      v[u] = (q < (I)hi) ? row[(int64_t)q * stride] : ident;
+    }
 #pragma unroll
-    for (int u = 0; u < kU; ++u)
-      acc[0] = (op_k == RSUM) ? acc[0] + v[u] : (op_k == RMIN ? fmin(acc[0], v[u]) : fmax(acc[0], v[u]));
+    for (int u = 0; u < kU; ++u) acc = fold_op(acc, v[u], op_k);
   }
-  block_reduce_store<1>(acc, op, out + k);
+  acc = wave_reduce(acc, op_k);
+  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double v = s[0];
+    for (int j = 1; j < (int)((B ? B : blockDim.x) >> 6); ++j) v = fold_op(v, s[j], op_k);
+    *out = v;
+  }
+}
+
+// Second pass of a standalone reduction: grid (NS), workgroup k folds slot k (operator OP(k)) of the nblocks partials
+// [block][NS] in `scratch` into out[k], kU loads in flight per thread.  Zero partials leave the identities.
+template <int NS, int kU, int (*OP)(int)>
+__global__ __launch_bounds__(kBlock) void k_fold_partials(const double* scratch, const int nblocks, double* out) {
+  fold_range<kU, kBlock>(scratch + blockIdx.x, 0, nblocks, OP(blockIdx.x), out + blockIdx.x, NS);
 }
 
 // The 24 read-out statistics (layout: art_hip.h, art_detector_readout) of one ray folded into `acc`; dead rays add the
@@ -588,8 +602,6 @@ __device__ __forceinline__ void readout_accumulate_lite(double (&acc)[kReadoutSl
   acc[4] = fmin(acc[4], live ? y : INFINITY); acc[5] = fmax(acc[5], live ? y : -INFINITY);
   acc[12] = fmin(acc[12], live ? o : INFINITY); acc[13] = fmax(acc[13], live ? o : -INFINITY);
 }
-#define ART_READOUT_OPS {RSUM, RSUM, RMIN, RMAX, RMIN, RMAX, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, \
-                         RMIN, RMAX, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM}
 
 // ------------------------------------------------------------------------------------------- trace kernels
 // The descriptor travels in a one-element array and is indexed with blockIdx.y (always 0): a dynamic index makes the
@@ -971,39 +983,7 @@ __device__ __forceinline__ void chain_body2(const ChainArgs& a, const int64_t fi
 // behind every relay4 trace, 18 us behind C2's 11 chains; that two-stage form remains for longer rows.
 // Grids: (24, 1, chains) direct; (24, chunks, chains) + (24, 1, chains) beyond.
 constexpr int kFoldChunks = 64;
-constexpr int kFoldBlock = 1024;
 constexpr int64_t kFoldDirect = 65536;
-__device__ __forceinline__ double fold_op(const double a, const double b, const int op_k) {
-  return (op_k == RSUM) ? a + b : (op_k == RMIN ? fmin(a, b) : fmax(a, b));
-}
-// every thread of the workgroup (blockDim.x threads, a multiple of 64) calls this; thread 0 stores the result
-__device__ __forceinline__ void fold_range(const double* row, const int64_t lo, const int64_t hi, const int op_k,
-                                           double* out) {
-  __shared__ double s[kFoldBlock / 64];
-  const double ident = (op_k == RSUM) ? 0.0 : (op_k == RMIN ? INFINITY : -INFINITY);
-  double acc = ident;
-  // eight loads in flight per thread before the first is folded (a thread's ~40 values one load at a time are 40 memory
-  // latencies in a row: 17 us per 1e7 rays, measured); the fold order stays fixed: p, p + B, p + 2B, ...
-  constexpr int kU = 8;
-  for (int64_t p = lo + threadIdx.x; p < hi; p += (int64_t)blockDim.x * kU) {
-    double v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) {
-      const int64_t q = p + (int64_t)u * blockDim.x;
-      v[u] = (q < hi) ? row[q] : ident;
-    }
-#pragma unroll
-    for (int u = 0; u < kU; ++u) acc = fold_op(acc, v[u], op_k);
-  }
-  acc = wave_reduce(acc, op_k);
-  if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double v = s[0];
-    for (int j = 1; j < (int)(blockDim.x >> 6); ++j) v = fold_op(v, s[j], op_k);
-    *out = v;
-  }
-}
 __device__ __forceinline__ double* fold_mid(double* scratch, const int64_t nparts) {
   return scratch + (int64_t)kReadoutSlots * nparts;
 }
@@ -1015,10 +995,9 @@ __device__ __forceinline__ int fold_row_of(const int slot) {
 }
 __device__ __forceinline__ void fold_stage1(double* scratch, const int64_t nparts) {
   if (blockIdx.x >= kUsedSlots) return;
-  const int ops[kReadoutSlots] = ART_READOUT_OPS;
   const int64_t per = (nparts + kFoldChunks - 1) / kFoldChunks;
   const int64_t lo = (int64_t)blockIdx.y * per, hi = (lo + per < nparts) ? lo + per : nparts;
-  fold_range(scratch + (int64_t)fold_row_of(blockIdx.x) * nparts, lo, hi, ops[blockIdx.x],
+  fold_range(scratch + (int64_t)fold_row_of(blockIdx.x) * nparts, lo, hi, stat_op(blockIdx.x),
              fold_mid(scratch, nparts) + blockIdx.x * kFoldChunks + blockIdx.y);
 }
 __device__ __forceinline__ void fold_stage2(double* scratch, const int64_t nparts, double* out24, const int direct) {
@@ -1026,12 +1005,11 @@ __device__ __forceinline__ void fold_stage2(double* scratch, const int64_t npart
     if (threadIdx.x == 0) out24[blockIdx.x] = 0.0;
     return;
   }
-  const int ops[kReadoutSlots] = ART_READOUT_OPS;
   if (direct) {   // nparts == 0 (an empty bundle): the fold of nothing leaves the identities
-    fold_range(scratch + (int64_t)fold_row_of(blockIdx.x) * nparts, 0, nparts, ops[blockIdx.x], out24 + blockIdx.x);
+    fold_range(scratch + (int64_t)fold_row_of(blockIdx.x) * nparts, 0, nparts, stat_op(blockIdx.x), out24 + blockIdx.x);
     return;
   }
-  fold_range(fold_mid(scratch, nparts) + blockIdx.x * kFoldChunks, 0, kFoldChunks, ops[blockIdx.x], out24 + blockIdx.x);
+  fold_range(fold_mid(scratch, nparts) + blockIdx.x * kFoldChunks, 0, kFoldChunks, stat_op(blockIdx.x), out24 + blockIdx.x);
 }
 __global__ __launch_bounds__(kFoldBlock) void k_chain_readout_fold1(const ChainArgs* __restrict__ tab, const int64_t nparts) {
   fold_stage1(tab[blockIdx.z].ro.scratch, nparts);
@@ -1240,11 +1218,9 @@ template <bool HAS_W>
 __global__ __launch_bounds__(kBlock) void k_stats_partial(const uint8_t* alive, const double* X, const double* Y,
                                                           const double* opl, const double* w, const int64_t n,
                                                           double* scratch) {
-  const int ops[kRedSlots] = {RSUM, RSUM, RMIN, RMAX, RMIN, RMAX, RSUM, RSUM,
-                              RSUM, RSUM, RSUM, RSUM, RMIN, RMAX, RSUM, RSUM};
   double acc[kRedSlots];
 #pragma unroll
-  for (int k = 0; k < kRedSlots; ++k) acc[k] = (ops[k] == RSUM) ? 0.0 : (ops[k] == RMIN ? INFINITY : -INFINITY);
+  for (int k = 0; k < kRedSlots; ++k) acc[k] = red_ident(stat_op(k));
   const int64_t stride = (int64_t)gridDim.x * kBlock, last = n - 1;
   for (int64_t i0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; i0 < n; i0 += kRedUnroll * stride) {
     double xv[kRedUnroll], yv[kRedUnroll], ov[kRedUnroll], wv[kRedUnroll];
@@ -1270,16 +1246,8 @@ __global__ __launch_bounds__(kBlock) void k_stats_partial(const uint8_t* alive, 
       acc[12] = fmin(acc[12], l ? ov[u] : INFINITY); acc[13] = fmax(acc[13], l ? ov[u] : -INFINITY);
     }
   }
-  block_reduce_store<kRedSlots>(acc, ops, scratch + (int64_t)blockIdx.x * kRedSlots);
+  block_reduce_store<kRedSlots>(acc, stat_op, scratch + (int64_t)blockIdx.x * kRedSlots);
 }
-
-__global__ __launch_bounds__(kBlock) void k_stats_final(const double* scratch, const int nblocks, double* out) {
-  const int ops[kRedSlots] = {RSUM, RSUM, RMIN, RMAX, RMIN, RMAX, RSUM, RSUM,
-                              RSUM, RSUM, RSUM, RSUM, RMIN, RMAX, RSUM, RSUM};
-  fold_slot(scratch, nblocks, kRedSlots, ops[blockIdx.x], out);
-}
-
-constexpr int kSumSlots = 8;
 
 // detector read-out fused with its reductions: one pass over the bundle, statistics accumulated in registers
 __global__ __launch_bounds__(kBlock) void k_detector_readout(const ArtDetectorDesc d, const ArtBundleView b,
@@ -1287,11 +1255,9 @@ __global__ __launch_bounds__(kBlock) void k_detector_readout(const ArtDetectorDe
                                                              const double cy, const double co, double* p3x, double* p3y,
                                                              double* p3z, double* X, double* Y, double* opl,
                                                              double* scratch) {
-  const int ops[kReadoutSlots] = {RSUM, RSUM, RMIN, RMAX, RMIN, RMAX, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM,
-                                  RMIN, RMAX, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM};
   double acc[kReadoutSlots];
 #pragma unroll
-  for (int k = 0; k < kReadoutSlots; ++k) acc[k] = (ops[k] == RSUM) ? 0.0 : (ops[k] == RMIN ? INFINITY : -INFINITY);
+  for (int k = 0; k < kReadoutSlots; ++k) acc[k] = red_ident(stat_op(k));
   // Two consecutive slots per lane and iteration: every stream is read with one 16-byte access per lane (1 KiB per
   // wave instruction) and the three outputs are written the same way; per-dword range checking of the raw buffer
   // descriptors takes care of an odd tail.  Dead rays contribute nothing through selects (no divergent skip); their
@@ -1329,9 +1295,9 @@ __global__ __launch_bounds__(kBlock) void k_detector_readout(const ArtDetectorDe
     st_2f64(rX, o16, xo[0], xo[1]); st_2f64(rY, o16, yo[0], yo[1]); st_2f64(rO, o16, oo[0], oo[1]);
   }
 #ifdef ART_READOUT_SHUFFLE_REDUCE      // round-1 form: 24 shuffle trees per wave + __syncthreads()
-  block_reduce_store<kReadoutSlots>(acc, ops, scratch + (int64_t)blockIdx.x * kReadoutSlots);
+  block_reduce_store<kReadoutSlots>(acc, stat_op, scratch + (int64_t)blockIdx.x * kReadoutSlots);
 #else
-  // One partial per WORKGROUP, [block][24] as k_readout_final expects it.  Per wave the LDS transpose of the fused tail
+  // One partial per WORKGROUP, [block][24] as k_fold_partials expects it.  Per wave the LDS transpose of the fused tail
   // (wave_reduce24, ~100 instructions instead of 24 shuffle trees), then the four waves meet in LDS behind a bare
   // s_barrier: __syncthreads() would also wait for the acknowledgement of every store this workgroup has in flight
   // (vmcnt).  174 -> 158 us per 1e7 rays (tools/r02_exp21.sh).
@@ -1358,16 +1324,13 @@ __global__ __launch_bounds__(kBlock) void k_detector_readout(const ArtDetectorDe
     const int k = threadIdx.x;
     double v = s_part[0][k];
 #pragma unroll
-    for (int j = 1; j < kBlock / 64; ++j)
-      v = (ops[k] == RSUM) ? v + s_part[j][k] : (ops[k] == RMIN ? fmin(v, s_part[j][k]) : fmax(v, s_part[j][k]));
+    for (int j = 1; j < kBlock / 64; ++j) v = fold_op(v, s_part[j][k], stat_op(k));
     scratch[(int64_t)blockIdx.x * kReadoutSlots + k] = v;
   } else if (threadIdx.x < kReadoutSlots) {
     scratch[(int64_t)blockIdx.x * kReadoutSlots + threadIdx.x] = 0.0;    // reserved slots 22, 23
   }
 #endif
 }
-
-constexpr int kScanSlots = 33;
 
 // the slot's seven streams + weight of kU grid-stride iterations, requested up front (see ld_nt)
 template <int kU>
@@ -1429,17 +1392,7 @@ __global__ __launch_bounds__(kBlock) void k_scan_moments_partial(const ArtDetect
       }
     }
   }
-  block_reduce_store_f<kScanSlots>(acc, [](int) { return (int)RSUM; }, scratch + (int64_t)blockIdx.x * kScanSlots);
-}
-
-__global__ __launch_bounds__(kBlock) void k_scan_moments_final(const double* scratch, const int nblocks, double* out) {
-  fold_slot(scratch, nblocks, kScanSlots, RSUM, out);
-}
-
-__global__ __launch_bounds__(kBlock) void k_readout_final(const double* scratch, const int nblocks, double* out) {
-  const int ops[kReadoutSlots] = {RSUM, RSUM, RMIN, RMAX, RMIN, RMAX, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM,
-                                  RMIN, RMAX, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM};
-  fold_slot(scratch, nblocks, kReadoutSlots, ops[blockIdx.x], out);
+  block_reduce_store<kScanSlots>(acc, sum_op, scratch + (int64_t)blockIdx.x * kScanSlots);
 }
 
 template <bool HAS_W>
@@ -1447,7 +1400,6 @@ __global__ __launch_bounds__(kBlock) void k_moments_partial(const uint8_t* alive
                                                             const double* opl, const double* w, const int64_t n,
                                                             const double cx, const double cy, const double co,
                                                             double* scratch) {
-  const int ops[kSumSlots] = {RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM};
   double acc[kSumSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int64_t stride = (int64_t)gridDim.x * kBlock, last = n - 1;
   for (int64_t i0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; i0 < n; i0 += kRedUnroll * stride) {
@@ -1474,13 +1426,12 @@ __global__ __launch_bounds__(kBlock) void k_moments_partial(const uint8_t* alive
       acc[4] += l ? 1.0 : 0.0;
     }
   }
-  block_reduce_store<kSumSlots>(acc, ops, scratch + (int64_t)blockIdx.x * kSumSlots);
+  block_reduce_store<kSumSlots>(acc, sum_op, scratch + (int64_t)blockIdx.x * kSumSlots);
 }
 
 template <bool HAS_W>
 __global__ __launch_bounds__(kBlock) void k_bundle_sums_partial(const ArtBundleView b, const double* w,
                                                                 const int64_t n, double* scratch) {
-  const int ops[kSumSlots] = {RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM};
   double acc[kSumSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
   const int64_t stride = (int64_t)gridDim.x * kBlock, last = n - 1;
   for (int64_t i0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; i0 < n; i0 += kRedUnroll * stride) {
@@ -1501,11 +1452,7 @@ __global__ __launch_bounds__(kBlock) void k_bundle_sums_partial(const ArtBundleV
       for (int k = 0; k < 7; ++k) acc[1 + k] += live[u] ? v[u][k] : 0.0;
     }
   }
-  block_reduce_store<kSumSlots>(acc, ops, scratch + (int64_t)blockIdx.x * kSumSlots);
-}
-
-__global__ __launch_bounds__(kBlock) void k_sums_final(const double* scratch, const int nblocks, double* out) {
-  fold_slot(scratch, nblocks, kSumSlots, RSUM, out);
+  block_reduce_store<kSumSlots>(acc, sum_op, scratch + (int64_t)blockIdx.x * kSumSlots);
 }
 
 // ------------------------------------------------------------------------------------------- source weights
@@ -1544,8 +1491,7 @@ __device__ __forceinline__ Axis3 axis_of(const Axis3 given, const double* axis_s
 __global__ __launch_bounds__(kBlock) void k_gauss_max_partial(const ArtBundleView b, const Axis3 ax_in, const double* axis_sums,
                                                               const int64_t n, double* scratch) {
   const Axis3 ax = axis_of(ax_in, axis_sums);
-  const int ops[kSumSlots] = {RMAX, RMAX, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM};
-  double acc[kSumSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double acc[kMaxSlots] = {0, 0};    // (the largest of nothing is 0)
   const int64_t stride = (int64_t)gridDim.x * kBlock, last = n - 1;
   constexpr int kU = 2;     // (an atan2 and three square roots per ray: the arithmetic hides the rest of the latency)
   for (int64_t i0 = (int64_t)blockIdx.x * kBlock + threadIdx.x; i0 < n; i0 += kU * stride) {
@@ -1568,17 +1514,7 @@ __global__ __launch_bounds__(kBlock) void k_gauss_max_partial(const ArtBundleVie
       acc[1] = fmax(acc[1], sqrt(art::dot3(px, py, pz, px, py, pz)));
     }
   }
-  block_reduce_store<kSumSlots>(acc, ops, scratch + (int64_t)blockIdx.x * kSumSlots);
-}
-
-__global__ __launch_bounds__(kBlock) void k_gauss_max_final(const double* scratch, const int nblocks, double* out) {
-  const int ops[kSumSlots] = {RMAX, RMAX, RSUM, RSUM, RSUM, RSUM, RSUM, RSUM};
-  double acc[kSumSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int blk = threadIdx.x; blk < nblocks; blk += kBlock) {
-    acc[0] = fmax(acc[0], scratch[(int64_t)blk * kSumSlots + 0]);
-    acc[1] = fmax(acc[1], scratch[(int64_t)blk * kSumSlots + 1]);
-  }
-  block_reduce_store<kSumSlots>(acc, ops, out);
+  block_reduce_store<kMaxSlots>(acc, max_op, scratch + (int64_t)blockIdx.x * kMaxSlots);
 }
 
 __global__ __launch_bounds__(kBlock) void k_gauss_weights(const ArtBundleView b, const Axis3 ax_in, const double* axis_sums,
@@ -1821,14 +1757,14 @@ __global__ __launch_bounds__(kBlock, 4) void k_analysis_moments(const ArtAnalysi
   const ArtAnalysisJob& jb = jobs[j];
   double acc[kAnaMom];
 #pragma unroll
-  for (int k = 0; k < kAnaMom; ++k) acc[k] = (ana_mom_op(k) == RSUM) ? 0.0 : (ana_mom_op(k) == RMIN ? INFINITY : -INFINITY);
+  for (int k = 0; k < kAnaMom; ++k) acc[k] = red_ident(ana_mom_op(k));
   acc[34] = 0.0;    // the largest angle of an empty set is 0 (ReturnNumericalAperture's max over nothing never happens)
   const bool active = jb.mode != ART_JOB_SUMS && out[(int64_t)j * ART_ANALYSIS_DOUBLES] > 0.0;
   if (active) {
     if (jb.w) moments_body<true>(jb, n, place + (int64_t)j * kAnaPlace, acc, blk, (unsigned)P);
     else moments_body<false>(jb, n, place + (int64_t)j * kAnaPlace, acc, blk, (unsigned)P);
   }
-  block_reduce_store_f<kAnaMom>(acc, [](int q) { return ana_mom_op(q); }, scratch + ((int64_t)j * P + blk) * kAnaMom);
+  block_reduce_store<kAnaMom>(acc, ana_mom_op, scratch + ((int64_t)j * P + blk) * kAnaMom);
 }
 
 // grid (kAnaMom - 1, n_jobs): workgroup (q, j) folds partial q of job j into its output slot
@@ -1836,24 +1772,10 @@ __global__ __launch_bounds__(kBlock) void k_analysis_fold(const ArtAnalysisJob* 
                                                           const double* scratch, double* out) {
   const int q = blockIdx.x, j = blockIdx.y;
   if (jobs[j].mode == ART_JOB_SUMS) return;
-  const int op = ana_mom_op(q);
-  const int op1[1] = {op};
-  const double ident = (op == RSUM) ? 0.0 : (op == RMIN ? INFINITY : -INFINITY);
-  double acc[1] = {ident};
-  const double* mine = scratch + (int64_t)j * nblocks * kAnaMom;
-  constexpr int kU = 4;    // partials in flight per thread (the fold order stays blk, blk + 256, ...)
-  for (int blk = threadIdx.x; blk < nblocks; blk += kBlock * kU) {
-    double v[kU];
-#pragma unroll
-    for (int u = 0; u < kU; ++u) v[u] = (blk + u * kBlock < nblocks) ? mine[(int64_t)(blk + u * kBlock) * kAnaMom + q] : ident;
-#pragma unroll
-    for (int u = 0; u < kU; ++u) acc[0] = (op == RSUM) ? acc[0] + v[u] : (op == RMIN ? fmin(acc[0], v[u]) : fmax(acc[0], v[u]));
-  }
-  __shared__ double s_res[1];
-  block_reduce_store<1>(acc, op1, s_res);
-  __syncthreads();
+  double v;
+  fold_range<4, kBlock>(scratch + (int64_t)j * nblocks * kAnaMom + q, 0, nblocks, ana_mom_op(q), &v, kAnaMom);
   // partial 34 carries tan^2(angle / 2) of the ray farthest from the mean direction: the angle is formed here, once
-  if (threadIdx.x == 0) out[(int64_t)j * ART_ANALYSIS_DOUBLES + ana_mom_slot(q)] = (q == 34) ? 2.0 * atan(sqrt(s_res[0])) : s_res[0];
+  if (threadIdx.x == 0) out[(int64_t)j * ART_ANALYSIS_DOUBLES + ana_mom_slot(q)] = (q == 34) ? 2.0 * atan(sqrt(v)) : v;
 }
 
 // ------------------------------------------------------------------------------------------- compaction
@@ -2095,12 +2017,9 @@ __global__ __launch_bounds__(kBlock) void k_exchange_pack(const double* stats, c
 __global__ void k_exchange_fold(const double* recv, const int world, const int64_t stride, double* out) {
   const int s = threadIdx.x;
   if (s >= kReadoutSlots) return;
-  const bool is_min = (s == 2 || s == 4 || s == 12), is_max = (s == 3 || s == 5 || s == 13);
+  const int op = stat_op(s);
   double v = recv[s];
-  for (int r = 1; r < world; ++r) {       // rank order: deterministic
-    const double w = recv[(int64_t)r * stride + s];
-    v = is_min ? fmin(v, w) : (is_max ? fmax(v, w) : v + w);
-  }
+  for (int r = 1; r < world; ++r) v = fold_op(v, recv[(int64_t)r * stride + s], op);   // rank order: deterministic
   out[s] = v;
 }
 
@@ -2174,6 +2093,13 @@ int per_launch(const int64_t n, F&& f) {
 int launched(const char* what) {
   const hipError_t err = hipGetLastError();
   return (err != hipSuccess) ? fail_hip(err, what) : ART_OK;
+}
+
+// the epilogue of a standalone reduction: fold the nb partials [block][NS] in `scratch` into out[0 .. NS)
+template <int NS, int (*OP)(int)>
+int fold_partials(const double* scratch, const int nb, double* out, hipStream_t s, const char* what) {
+  hipLaunchKernelGGL((k_fold_partials<NS, 8, OP>), dim3(NS), dim3(kBlock), 0, s, scratch, nb, out);
+  return launched(what);
 }
 
 #ifdef ART_ZERN_LDS
@@ -2598,14 +2524,13 @@ int art_detector_readout(const ArtDetectorDesc* d, const ArtBundleView* b, const
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) {
-    // an empty shard must not pollute a cross-rank fold: the final kernel over zero partials writes the reduction
-    // identities (0 for sums, +inf / -inf for the min / max slots 2-5 and 12-13)
-    hipLaunchKernelGGL(k_readout_final, dim3(kReadoutSlots), dim3(kBlock), 0, s, scratch, 0, out24);
-    return launched("art_detector_readout launch");
+    // an empty shard must not pollute a cross-rank fold: the fold of zero partials writes the reduction identities
+    // (0 for sums, +inf / -inf for the min / max slots 2-5 and 12-13)
+    return fold_partials<kReadoutSlots, stat_op>(scratch, 0, out24, s, "art_detector_readout launch");
   }
   if (!view_ok(b)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
   // one launch per <= 2^28 rays (32-bit buffer offsets); every launch leaves one partial per workgroup, all of
-  // them folded by the final kernel: scratch holds up to 8 launches x kReadoutBlocks workgroups x 24 doubles
+  // them folded by k_fold_partials: scratch holds up to 8 launches x kReadoutBlocks workgroups x 24 doubles
   const int64_t chunk = max_rays_per_launch();
   const int64_t launches = (n + chunk - 1) / chunk;
   if (launches > 8) return fail(ART_ERR_UNSUPPORTED, "more than 2^31 rays in one read-out");
@@ -2622,8 +2547,7 @@ int art_detector_readout(const ArtDetectorDesc* d, const ArtBundleView* b, const
     nb_total += nb;
     return ART_OK;
   });
-  hipLaunchKernelGGL(k_readout_final, dim3(kReadoutSlots), dim3(kBlock), 0, s, scratch, nb_total, out24);
-  return launched("art_detector_readout launch");
+  return fold_partials<kReadoutSlots, stat_op>(scratch, nb_total, out24, s, "art_detector_readout launch");
 }
 
 int art_detector_scan_moments(const ArtDetectorDesc* d, const ArtBundleView* b, const double* w, int64_t n, double co,
@@ -2640,8 +2564,7 @@ int art_detector_scan_moments(const ArtDetectorDesc* d, const ArtBundleView* b, 
   const int nb = red_blocks(n);
   if (w) hipLaunchKernelGGL(k_scan_moments_partial<true>, dim3(nb), dim3(kBlock), 0, s, *d, *b, w, n, co, span, scratch);
   else hipLaunchKernelGGL(k_scan_moments_partial<false>, dim3(nb), dim3(kBlock), 0, s, *d, *b, w, n, co, span, scratch);
-  hipLaunchKernelGGL(k_scan_moments_final, dim3(kScanSlots), dim3(kBlock), 0, s, scratch, nb, out32);
-  return launched("art_detector_scan_moments launch");
+  return fold_partials<kScanSlots, sum_op>(scratch, nb, out32, s, "art_detector_scan_moments launch");
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }
@@ -2654,8 +2577,7 @@ int art_detector_stats(const uint8_t* alive, const double* X, const double* Y, c
   const int nb = red_blocks(n);
   if (w) hipLaunchKernelGGL(k_stats_partial<true>, dim3(nb), dim3(kBlock), 0, s, alive, X, Y, opl, w, n, scratch);
   else hipLaunchKernelGGL(k_stats_partial<false>, dim3(nb), dim3(kBlock), 0, s, alive, X, Y, opl, w, n, scratch);
-  hipLaunchKernelGGL(k_stats_final, dim3(kRedSlots), dim3(kBlock), 0, s, scratch, nb, out16);
-  return launched("art_detector_stats launch");
+  return fold_partials<kRedSlots, stat_op>(scratch, nb, out16, s, "art_detector_stats launch");
 }
 
 int art_detector_moments(const uint8_t* alive, const double* X, const double* Y, const double* opl, const double* w,
@@ -2666,8 +2588,7 @@ int art_detector_moments(const uint8_t* alive, const double* X, const double* Y,
   const int nb = red_blocks(n);
   if (w) hipLaunchKernelGGL(k_moments_partial<true>, dim3(nb), dim3(kBlock), 0, s, alive, X, Y, opl, w, n, cx, cy, co, scratch);
   else hipLaunchKernelGGL(k_moments_partial<false>, dim3(nb), dim3(kBlock), 0, s, alive, X, Y, opl, w, n, cx, cy, co, scratch);
-  hipLaunchKernelGGL(k_sums_final, dim3(kSumSlots), dim3(kBlock), 0, s, scratch, nb, out8);
-  return launched("art_detector_moments launch");
+  return fold_partials<kSumSlots, sum_op>(scratch, nb, out8, s, "art_detector_moments launch");
 }
 
 int art_bundle_sums(const ArtBundleView* bv, const double* w, int64_t n, double* scratch, double* out8, void* stream) {
@@ -2677,12 +2598,21 @@ int art_bundle_sums(const ArtBundleView* bv, const double* w, int64_t n, double*
   const int nb = red_blocks(n);
   if (w) hipLaunchKernelGGL(k_bundle_sums_partial<true>, dim3(nb), dim3(kBlock), 0, s, *bv, w, n, scratch);
   else hipLaunchKernelGGL(k_bundle_sums_partial<false>, dim3(nb), dim3(kBlock), 0, s, *bv, w, n, scratch);
-  hipLaunchKernelGGL(k_sums_final, dim3(kSumSlots), dim3(kBlock), 0, s, scratch, nb, out8);
-  return launched("art_bundle_sums launch");
+  return fold_partials<kSumSlots, sum_op>(scratch, nb, out8, s, "art_bundle_sums launch");
 }
 
 static int gaussian_impl(const ArtBundleView* bv, const double axis[3], const double* axis_sums, double fraction, int64_t n,
                          double* scratch, double* w_out, void* stream);
+
+// the max pair of n > 0 rays (largest angle to the axis, largest distance from the origin) into max2[0 .. 1]; the
+// partials take scratch[0 .. kRedBlocks * kMaxSlots)
+static void max_pass(const ArtBundleView& b, const Axis3 ax, const double* axis_sums, int64_t n, double* scratch, double* max2,
+                     hipStream_t s) {
+  const int nb = red_blocks(n);
+  hipLaunchKernelGGL(k_gauss_max_partial, dim3(nb), dim3(kBlock), 0, s, b, ax, axis_sums, n, scratch);
+  // (at most 4 partials per thread: folded one load at a time)
+  hipLaunchKernelGGL((k_fold_partials<kMaxSlots, 1, max_op>), dim3(kMaxSlots), dim3(kBlock), 0, s, scratch, nb, max2);
+}
 
 int art_gaussian_intensity(const ArtBundleView* bv, const double axis[3], double fraction, int64_t n, double* scratch,
                            double* w_out, void* stream) {
@@ -2707,12 +2637,9 @@ static int gaussian_impl(const ArtBundleView* bv, const double axis[3], const do
   if (!(fraction > 0.0 && fraction < 1.0)) return fail(ART_ERR_BAD_ARG, "fraction must be in (0, 1)");
   if (n == 0) return ART_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int nb = red_blocks(n);
   const Axis3 ax = {axis[0], axis[1], axis[2]};
-  // partials in scratch[0 .. nb*8), the two maxima right behind them
-  double* maxima = scratch + (int64_t)kRedBlocks * kSumSlots;
-  hipLaunchKernelGGL(k_gauss_max_partial, dim3(nb), dim3(kBlock), 0, s, *bv, ax, axis_sums, n, scratch);
-  hipLaunchKernelGGL(k_gauss_max_final, dim3(1), dim3(kBlock), 0, s, scratch, nb, maxima);
+  double* maxima = scratch + (int64_t)kRedBlocks * kMaxSlots;   // right behind the partials
+  max_pass(*bv, ax, axis_sums, n, scratch, maxima, s);
   hipLaunchKernelGGL(k_gauss_weights, dim3(grid_for(n)), dim3(kBlock), 0, s, *bv, ax, axis_sums, -0.5 * log(fraction), maxima, n,
                      w_out);
   return launched("art_gaussian_intensity launch");
@@ -2729,13 +2656,7 @@ int art_bundle_max_angle(const ArtBundleView* bv, const double axis[3], int64_t 
     return ART_OK;
   }
   if (!view_ok(bv)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
-  const int nb = red_blocks(n);
-  const Axis3 ax = {axis[0], axis[1], axis[2]};
-  double* tmp = scratch + (int64_t)kRedBlocks * kSumSlots;   // 8 doubles: the folded partials
-  hipLaunchKernelGGL(k_gauss_max_partial, dim3(nb), dim3(kBlock), 0, s, *bv, ax, (const double*)nullptr, n, scratch);
-  hipLaunchKernelGGL(k_gauss_max_final, dim3(1), dim3(kBlock), 0, s, scratch, nb, tmp);
-  hipError_t e1 = hipMemcpyAsync(out2, tmp, 2 * sizeof(double), hipMemcpyDeviceToDevice, s);
-  if (e1 != hipSuccess) return fail_hip(e1, "hipMemcpyAsync");
+  max_pass(*bv, Axis3{axis[0], axis[1], axis[2]}, nullptr, n, scratch, out2, s);
   return launched("art_bundle_max_angle launch");
 }
 

@@ -194,6 +194,38 @@ def test_gpu_compaction_and_reductions(hip):
     s2 = be.detector_stats(alive, X, Y, O, W, n)
     assert np.array_equal(s, s2), "reductions must be deterministic"
 
+    # n == 0 through the raw ABI (the wrappers return early): the exact bytes each entry writes for an empty bundle
+    import ctypes as C
+    from attosecondraytracing_amd import _abi
+    from attosecondraytracing_amd.bundle import RayBundle
+    sp, red = be.stream_ptr(), be._red_scratch().data_ptr()
+    bundle, alive0, w_out = RayBundle.allocate(1, backend=be), be.zeros(1, torch.uint8), be.empty(1)
+    d, view = _abi.ArtDetectorDesc(), bundle.view()
+    axis = (C.c_double * 3)(0.0, 0.0, 1.0)
+    ident = [np.inf if k in (2, 4, 12) else (-np.inf if k in (3, 5, 13) else 0.0) for k in range(24)]
+
+    def empty_call(size, call):
+        out = torch.full((size,), float("nan"), dtype=torch.float64, device=be.device)
+        assert call(out.data_ptr()) == _abi.ART_OK
+        return out.cpu().numpy().view(np.uint64)
+
+    bits = lambda v: np.asarray(v, dtype=np.float64).view(np.uint64)
+    a0 = alive0.data_ptr()
+    assert np.array_equal(empty_call(16, lambda o: be.fn["art_detector_stats"](a0, None, None, None, None, 0, red, o, sp)),
+                          bits(ident[:16]))
+    assert np.array_equal(empty_call(24, lambda o: be.fn["art_detector_readout"](
+        C.byref(d), C.byref(_abi.ArtBundleView()), None, 0, 0.0, 0.0, 0.0, None, None, None, None, None, None, red, o, sp)),
+        bits(ident))
+    assert np.array_equal(empty_call(8, lambda o: be.fn["art_detector_moments"](a0, None, None, None, None, 0, 0.0, 0.0, 0.0,
+                                                                                  red, o, sp)), bits(np.zeros(8)))
+    assert np.array_equal(empty_call(8, lambda o: be.fn["art_bundle_sums"](C.byref(view), None, 0, red, o, sp)),
+                          bits(np.zeros(8)))
+    assert np.array_equal(empty_call(33, lambda o: be.fn["art_detector_scan_moments"](
+        C.byref(d), C.byref(_abi.ArtBundleView()), None, 0, 0.0, 0.0, red, o, sp)), bits(np.zeros(33)))
+    assert np.array_equal(empty_call(2, lambda o: be.fn["art_bundle_max_angle"](C.byref(view), axis, 0, red, o, sp)),
+                          bits(np.zeros(2)))
+    assert be.fn["art_gaussian_intensity"](C.byref(view), axis, 0.5, 0, red, w_out.data_ptr(), sp) == _abi.ART_OK
+
 
 def test_gpu_sources_match_oracle(hip):
     import ART.ModuleSource as msource
