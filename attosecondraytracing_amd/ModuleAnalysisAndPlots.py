@@ -88,6 +88,24 @@ def MirrorProjection(OpticalChain, ReflectionNumber: int, Detector=None, ColorCo
     return _plots.MirrorProjection(OpticalChain, ReflectionNumber, Detector, ColorCoded)
 
 
+def SpotImage(RayListAnalysed, Detector, Bins=200):
+    """Image of the X-Y histogram of all rays on the detector, binned on the device; left/right move the detector."""
+    from . import _plots
+    return _plots.SpotImage(RayListAnalysed, Detector, Bins)
+
+
+def DelayProfile(RayListAnalysed, Detector, Bins=200):
+    """Histogram of the delays of all rays on the detector, binned on the device; left/right move the detector."""
+    from . import _plots
+    return _plots.DelayProfile(RayListAnalysed, Detector, Bins)
+
+
+def MirrorFootprint(OpticalChain, ReflectionNumber: int, Bins=200):
+    """Image of the footprint of all rays on one optical element, binned on the device, over its support outline."""
+    from . import _plots
+    return _plots.MirrorFootprint(OpticalChain, ReflectionNumber, Bins)
+
+
 def RayRenderGraph(OpticalChain, EndDistance=None, maxRays=300, OEpoints=3000, scale_spheres=5.0, draw_mesh=False,
                    cycle_ray_colors=False):
     """3-D picture of the optical setup and the traced rays (ART/ModuleAnalysisAndPlots.py:616-673)."""

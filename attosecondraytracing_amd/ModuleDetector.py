@@ -222,3 +222,10 @@ class Detector:
         s = r["stats"]
         opl = r["opl"].index_select(0, r["bundle"].index()).cpu().numpy()
         return (opl - s[1] / s[0]) / LightSpeed * 1e15
+
+    def get_Histogram(self, RayList, Axes=("X", "Y"), Bins=100, Range=None):
+        """Histogram (histogram.Histogram) of ALL alive rays, binned on the device: Axes from "X", "Y" (get_PointList2D's
+        coordinates) and "Delay" (get_Delays' fs); Bins an int or one per axis; Range None (min..max of the alive rays)
+        or one (lo, hi) per axis.  Shows intensity sums when the rays carry intensities."""
+        from . import histogram
+        return histogram.detector_histogram(self, RayList, Axes, Bins, Range)

@@ -143,6 +143,12 @@ class OpticalChain:
         re-trace), which is what makes a pose scan on small bundles GPU-bound instead of launch-bound."""
         return self._output_for(self._cache_key(kwargs), kwargs)
 
+    def get_Footprint(self, OEindx, Bins=100, Range=None):
+        """Histogram (histogram.Histogram) of the hit points of ALL rays on element OEindx (get_output_rays()[OEindx]) in
+        its support frame, as MirrorProjection places them; Range defaults to +-_CircumRect()/2 of the support."""
+        from . import histogram
+        return histogram.footprint(self.optical_elements[OEindx], self.get_output_rays()[OEindx], Bins, Range)
+
     def _output_for(self, key, kwargs):
         """get_output_rays for a cache key the caller has computed already (trace_chain_list: once per chain)."""
         if key != self._last_key:

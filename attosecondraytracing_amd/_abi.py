@@ -1,7 +1,7 @@
 """ctypes mirror of include/art_hip.h (structs, enums, prototypes).  Keep in sync with ART_ABI_VERSION."""
 import ctypes as C
 
-ART_ABI_VERSION = 11
+ART_ABI_VERSION = 12
 
 ART_OK = 0
 ART_ERR_BAD_ARG = -1
@@ -102,6 +102,24 @@ class ArtAnalysisJob(C.Structure):
     ]
 
 
+ART_HIST_DETECTOR, ART_HIST_FRAME = range(2)
+ART_HAXIS_X, ART_HAXIS_Y, ART_HAXIS_DELAY = 0, 1, 3
+ART_HIST_MAX_BINS = 1 << 24
+
+
+class ArtHistogramDesc(C.Structure):
+    _fields_ = [
+        ("source", C.c_int32), ("ndim", C.c_int32),
+        ("axis", C.c_int32 * 3),
+        ("bins", C.c_int32 * 3),
+        ("wshift", C.c_int32),
+        ("reserved", C.c_int32),
+        ("lo", C.c_double * 3), ("hi", C.c_double * 3),
+        ("delay_centre", C.c_double),
+        ("map", ArtDetectorDesc),
+    ]
+
+
 # name -> (restype, argtypes); the loader checks every symbol exists (tests/test_abi.py does too)
 PROTOTYPES = {
     "art_abi_version": (C.c_int, []),
@@ -128,6 +146,8 @@ PROTOTYPES = {
     "art_detector_scan_moments": (C.c_int, [C.POINTER(ArtDetectorDesc), C.POINTER(ArtBundleView), C.c_void_p,
                                             C.c_int64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
+    "art_histogram": (C.c_int, [C.POINTER(ArtHistogramDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64, C.c_int32,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_reduce_scratch_doubles": (C.c_int64, []),
     "art_detector_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

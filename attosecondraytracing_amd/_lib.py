@@ -287,6 +287,28 @@ class HipBackend:
                                                         self.stream_ptr()), "art_detector_scan_moments")
         return out.cpu().numpy()
 
+    def histogram(self, hdesc, view, w, n, out=None, shift=None):
+        """art_histogram on the current stream.  hdesc: ArtHistogramDesc; its wshift is set here, to `shift` or to
+        histogram.weight_shift(n, w) (one torch.amax, read back; ValueError for non-finite weights, before the launch).
+        out = (counts, wsums, totals) from an earlier call: ADD to them (accumulate), else new tensors are zeroed.
+        Returns (counts, wsums or None, totals, shift), device int64 tensors."""
+        from . import histogram as hist
+        if shift is None:
+            shift = hist.weight_shift(n, None if w is None else w[:n])
+        hdesc.wshift = int(shift)
+        if out is None:
+            nbins = int(np.prod([hdesc.bins[k] for k in range(max(1, min(3, hdesc.ndim)))]))
+            out = (self.empty(nbins, torch.int64), None if w is None else self.empty(nbins, torch.int64),
+                   self.empty(4, torch.int64))
+            accumulate = 0
+        else:
+            accumulate = 1
+        counts, wsums, totals = out
+        self.check(self.fn["art_histogram"](C.byref(hdesc), C.byref(view), None if (w is None or n == 0) else w.data_ptr(),
+                                            n, accumulate, counts.data_ptr(), None if wsums is None else wsums.data_ptr(),
+                                            totals.data_ptr(), self.stream_ptr()), "art_histogram")
+        return counts, wsums, totals, shift
+
     def _red_scratch(self):
         return self.scratch("red", self.fn["art_reduce_scratch_doubles"](), torch.float64)
 

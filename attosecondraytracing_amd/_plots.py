@@ -247,6 +247,129 @@ def MirrorProjection(OpticalChain, ReflectionNumber: int, Detector=None, ColorCo
     return fig
 
 
+def _binned(h):
+    """What a histogram plot shows: the intensity when the rays carry it, else the counts."""
+    return h.counts if h.intensity is None else h.intensity
+
+
+def _spot_image_data(B, Detector, Bins):
+    """X-Y histogram of all rays on the detector + the bounding-box centre, its size and the spot SD."""
+    h = Detector.get_Histogram(B, ("X", "Y"), Bins)
+    s = Detector.readout(B, store=False, lite=True)["stats"]
+    cx, cy = 0.5 * (s[2] + s[3]), 0.5 * (s[4] + s[5])
+    spot_sd, _ = Detector._spot_duration_from_moments(Detector._scan_moments(B), 0.0, False)
+    extent = ((h.edges[0][0] - cx) * 1e3, (h.edges[0][-1] - cx) * 1e3, (h.edges[1][0] - cy) * 1e3,
+              (h.edges[1][-1] - cy) * 1e3)
+    return h, extent, max(s[3] - s[2], s[5] - s[4]), spot_sd
+
+
+def _interactive(fig, B, Detector, size, redraw):
+    """left/right move a copy of the detector as in SpotDiagram; redraw(detector, distance) re-bins and returns the size."""
+    NA = mp.ReturnNumericalAperture(B, 1)
+    state = {"dist": Detector.get_distance(), "det": Detector.copy_detector(), "step": _dist_step(size, NA)}
+
+    def press(event):
+        new = _shift(state["det"], state["dist"], state["step"], event.key)
+        if new is None:
+            return
+        state["dist"] = new
+        state["step"] = _dist_step(redraw(state["det"], new), NA)
+        fig.canvas.draw_idle()
+
+    fig.canvas.mpl_connect("key_press_event", press)
+    fig._art_press = press
+    fig._art_state = state          # (tests: the distance and step of the next press)
+
+
+def SpotImage(RayListAnalysed, Detector, Bins=200):
+    """Image of the X-Y histogram of ALL rays on the detector (intensity, or counts without intensities), in µm about
+    the bounding-box centre; left/right move the detector and re-bin."""
+    plt = _plt()
+    B = _as_bundle(RayListAnalysed)
+    h, extent, size, spot_sd = _spot_image_data(B, Detector, Bins)
+    plt.ion()
+    fig, ax = plt.subplots()
+    im = ax.imshow(_binned(h).T, origin="lower", extent=extent, aspect="auto", interpolation="nearest")
+    fig.colorbar(im).set_label("Intensity (arb.u.)" if h.intensity is not None else "Rays per bin")
+    key, = ax.plot([], [], " ", label="{:.3f} mm\n{:.1f} μm SD".format(Detector.get_distance(), spot_sd * 1e3))
+    ax.legend(loc="upper right")
+    ax.set_title("Spot image\n press left/right to move detector position")
+    ax.set_xlabel("X (µm)")
+    ax.set_ylabel("Y (µm)")
+    fig._art_hist = h
+
+    def redraw(det, dist):
+        h, extent, size, spot_sd = _spot_image_data(B, det, Bins)
+        im.set_data(_binned(h).T)
+        im.set_extent(extent)
+        im.autoscale()
+        key.set_label("{:.3f} mm\n{:.1f} μm SD".format(dist, spot_sd * 1e3))
+        ax.legend(loc="upper right")
+        fig._art_hist = h
+        return size
+
+    _interactive(fig, B, Detector, size, redraw)
+    plt.show()
+    return fig
+
+
+def _delay_profile_data(B, Detector, Bins):
+    h = Detector.get_Histogram(B, ("Delay",), Bins)
+    s = Detector.readout(B, store=False, lite=True)["stats"]
+    _, dur_sd = Detector._spot_duration_from_moments(Detector._scan_moments(B), 0.0, False)
+    return h, max(s[3] - s[2], s[5] - s[4]), dur_sd
+
+
+def DelayProfile(RayListAnalysed, Detector, Bins=200):
+    """Step plot of the delay histogram of ALL rays on the detector (fs about the mean path; intensity, or counts
+    without intensities); left/right move the detector and re-bin."""
+    plt = _plt()
+    B = _as_bundle(RayListAnalysed)
+    h, size, dur_sd = _delay_profile_data(B, Detector, Bins)
+    plt.ion()
+    fig, ax = plt.subplots()
+    st = ax.stairs(_binned(h), h.edges[0], label="{:.3f} mm\n{:.2f} fs SD".format(Detector.get_distance(), dur_sd))
+    ax.legend(loc="upper right")
+    ax.set_title("Delay profile\n press left/right to move detector position")
+    ax.set_xlabel("Delay (fs)")
+    ax.set_ylabel("Intensity (arb.u.)" if h.intensity is not None else "Rays per bin")
+    fig._art_hist = h
+
+    def redraw(det, dist):
+        h, size, dur_sd = _delay_profile_data(B, det, Bins)
+        st.set_data(_binned(h), h.edges[0])
+        st.set_label("{:.3f} mm\n{:.2f} fs SD".format(dist, dur_sd))
+        ax.relim()
+        ax.autoscale_view()
+        ax.legend(loc="upper right")
+        fig._art_hist = h
+        return size
+
+    _interactive(fig, B, Detector, size, redraw)
+    plt.show()
+    return fig
+
+
+def MirrorFootprint(OpticalChain, ReflectionNumber: int, Bins=200):
+    """Image of the footprint of ALL rays on one optical element (OpticalChain.get_Footprint) over its support
+    outline."""
+    plt = _plt()
+    h = OpticalChain.get_Footprint(ReflectionNumber, Bins)
+    oe = OpticalChain.optical_elements[ReflectionNumber]
+    plt.ion()
+    fig = plt.figure()
+    ax = oe.type.support._ContourSupport(fig)
+    im = ax.imshow(_binned(h).T, origin="lower", extent=(h.edges[0][0], h.edges[0][-1], h.edges[1][0], h.edges[1][-1]),
+                   aspect="auto", interpolation="nearest", zorder=0)
+    fig.colorbar(im, ax=ax).set_label("Intensity (arb.u.)" if h.intensity is not None else "Rays per bin")
+    ax.set_xlabel("x (mm)")
+    ax.set_ylabel("y (mm)")
+    ax.set_title("Footprint on mirror")
+    fig._art_hist = h
+    plt.show()
+    return fig
+
+
 def _same_slots(a, b):
     """Slot i of both bundles is the same source ray (bundles of one trace share their `number` tensor)."""
     return a.n_slots == b.n_slots and a.number is b.number

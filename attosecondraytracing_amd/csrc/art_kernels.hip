@@ -1395,6 +1395,142 @@ __global__ __launch_bounds__(kBlock) void k_scan_moments_partial(const ArtDetect
   block_reduce_store<kScanSlots>(acc, sum_op, scratch + (int64_t)blockIdx.x * kScanSlots);
 }
 
+// ------------------------------------------------------------------------------------------- histogram
+// art_histogram: every alive ray's bin is found in registers and counted with INTEGER atomics (a count and the
+// fixed-point weight q), so the result is the same bytes whatever the order of arrival.  Two forms, chosen by the bin
+// count: up to kHistLdsBins bins each workgroup bins into a private copy in LDS (ds_add_u32 / ds_add_u64) and adds its
+// non-zero bins to the output at the end; a larger image (up to 2^24 bins) cannot sit in LDS, and there every ray adds
+// to the output in global memory directly.  Reads like the fused read-out: two slots per lane through buffer
+// descriptors; the FRAME source gives the direction and path streams descriptors of 0 bytes, so they cost no traffic.
+constexpr int kHistBlocks = 512;      // persistent grid: 2 workgroups per CU, so that the LDS form flushes few copies
+constexpr int kHistLdsBins = 4096;    // 4 B count + 8 B weight sum per bin: 48 KiB of LDS at most
+
+struct HistArg {
+  ArtDetectorDesc map;
+  double lo[3], step[3], inv[3], hi[3];
+  double delay_centre;
+  int32_t bins[3], axis[3];
+  int32_t source, wshift;
+};
+
+// bin of v among the edges i*step + lo (i < nb) and hi (numpy.linspace: two roundings, NO fused multiply-add), with
+// numpy.histogramdd's rule: edge[j] <= v < edge[j+1], v == hi in the last bin; -1 outside (v < lo, v > hi, NaN).  The
+// guess from the uniform formula is off by at most one bin unless the range is so narrow against lo that rounding
+// makes several edges equal; the walks find the last bin whose edge is <= v in every case.
+__device__ __forceinline__ int hist_bin(const double v, const double lo, const double hi, const double step,
+                                        const double inv, const int nb) {
+#pragma clang fp contract(off)
+  if (!(v >= lo && v <= hi)) return -1;
+  if (v == hi) return nb - 1;
+  int j = (int)fmin(fmax((v - lo) * inv, 0.0), (double)(nb - 1));
+  while (j > 0 && v < (double)j * step + lo) --j;
+  while (j < nb - 1 && v >= (double)(j + 1) * step + lo) ++j;
+  return j;
+}
+
+// row-major bin of one ray (axis 0 slowest), -1 if a coordinate is outside its range
+__device__ __forceinline__ int hist_flat(const HistArg& a, const int ndim, const art::Ray& r) {
+  double v[3];
+  if (a.source == ART_HIST_DETECTOR) {
+    double Ix, Iy, Iz, o;
+    art::detector_ray(a.map, r, Ix, Iy, Iz, v[0], v[1], o);
+    v[2] = ((o - a.delay_centre) / 299792458000.0) * 1e15;      // Detector.get_Delays (no multiply-add to contract)
+  } else {
+    art::mat3_apply(a.map.rot, r.ox - a.map.centre[0], r.oy - a.map.centre[1], r.oz - a.map.centre[2], v[0], v[1], v[2]);
+  }
+  int flat = 0;
+  bool in = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (k < ndim) {
+      const int ax = a.axis[k];
+      const double c = ax == 0 ? v[0] : (ax == 1 ? v[1] : v[2]);      // v[2]: FRAME component 2 or the DELAY
+      const int j = hist_bin(c, a.lo[k], a.hi[k], a.step[k], a.inv[k], a.bins[k]);
+      in = in && j >= 0;
+      flat = flat * a.bins[k] + j;
+    }
+  }
+  return in ? flat : -1;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_histogram(const HistArg a, const int ndim, const int nbins,
+                                                      const ArtBundleView b, const double* w, const int64_t n,
+                                                      unsigned long long* counts, unsigned long long* wsums,
+                                                      unsigned long long* totals) {
+  extern __shared__ unsigned long long s_wsum[];        // LDS form: [nbins] weight sums (with w), then [nbins] counts
+  unsigned* const s_cnt = reinterpret_cast<unsigned*>(s_wsum + (w ? nbins : 0));
+  if (LDS) {
+    for (int i = threadIdx.x; i < nbins; i += kBlock) {
+      s_cnt[i] = 0u;
+      if (w) s_wsum[i] = 0ull;
+    }
+    __syncthreads();
+  }
+  const bool det = a.source == ART_HIST_DETECTOR;
+  const unsigned nb8 = (unsigned)(n * 8), nd8 = det ? nb8 : 0u;
+  const __amdgpu_buffer_rsrc_t rox = rsrc_of(b.ox, nb8), roy = rsrc_of(b.oy, nb8), roz = rsrc_of(b.oz, nb8),
+                               rdx = rsrc_of(b.dx, nd8), rdy = rsrc_of(b.dy, nd8), rdz = rsrc_of(b.dz, nd8),
+                               rpa = rsrc_of(b.path, nd8), ral = rsrc_of(b.alive, (unsigned)n),
+                               rw = rsrc_of(const_cast<double*>(w), w ? nb8 : 0u);
+  unsigned long long n_in = 0, n_out = 0, q_in = 0, q_out = 0;
+  const int64_t npairs = (n + 1) / 2;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < npairs; j += stride) {
+    const unsigned o16 = (unsigned)j * 16u, o2 = (unsigned)j * 2u;
+    const D2 ox = ld_2f64(rox, o16), oy = ld_2f64(roy, o16), oz = ld_2f64(roz, o16);
+    const D2 dx = ld_2f64(rdx, o16), dy = ld_2f64(rdy, o16), dz = ld_2f64(rdz, o16);
+    const D2 pa = ld_2f64(rpa, o16), wv = ld_2f64(rw, o16);
+    const unsigned char al[2] = {__builtin_amdgcn_raw_buffer_load_b8(ral, (int)o2, 0, ART_LD_AUX),
+                                 __builtin_amdgcn_raw_buffer_load_b8(ral, (int)o2 + 1, 0, ART_LD_AUX)};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      art::Ray r;
+      r.ox = h ? ox.b : ox.a; r.oy = h ? oy.b : oy.a; r.oz = h ? oz.b : oz.a;
+      r.dx = h ? dx.b : dx.a; r.dy = h ? dy.b : dy.a; r.dz = h ? dz.b : dz.a;
+      r.path = h ? pa.b : pa.a;
+      const bool live = al[h] != 0;
+      const int flat = hist_flat(a, ndim, r);
+      // a dead slot's weight is unspecified (possibly NaN): selected away before the conversion
+      const double wl = live ? (h ? wv.b : wv.a) : 0.0;
+      const unsigned long long q = (unsigned long long)(long long)rint(ldexp(wl, a.wshift));
+      const bool in = live && flat >= 0, out = live && flat < 0;
+      n_in += in ? 1ull : 0ull; q_in += in ? q : 0ull;
+      n_out += out ? 1ull : 0ull; q_out += out ? q : 0ull;
+      if (in) {
+        if (LDS) {
+          atomicAdd(&s_cnt[flat], 1u);
+          if (w) atomicAdd(&s_wsum[flat], q);
+        } else {
+          atomicAdd(&counts[flat], 1ull);
+          if (w) atomicAdd(&wsums[flat], q);
+        }
+      }
+    }
+  }
+  if (LDS) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < nbins; i += kBlock) {
+      const unsigned c = s_cnt[i];
+      if (c) {
+        atomicAdd(&counts[i], (unsigned long long)c);
+        if (w) atomicAdd(&wsums[i], s_wsum[i]);
+      }
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    n_in += __shfl_xor(n_in, off, 64); n_out += __shfl_xor(n_out, off, 64);
+    q_in += __shfl_xor(q_in, off, 64); q_out += __shfl_xor(q_out, off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (n_in) atomicAdd(&totals[0], n_in);
+    if (n_out) atomicAdd(&totals[1], n_out);
+    if (q_in) atomicAdd(&totals[2], q_in);
+    if (q_out) atomicAdd(&totals[3], q_out);
+  }
+}
+
 template <bool HAS_W>
 __global__ __launch_bounds__(kBlock) void k_moments_partial(const uint8_t* alive, const double* X, const double* Y,
                                                             const double* opl, const double* w, const int64_t n,
@@ -2565,6 +2701,67 @@ int art_detector_scan_moments(const ArtDetectorDesc* d, const ArtBundleView* b, 
   if (w) hipLaunchKernelGGL(k_scan_moments_partial<true>, dim3(nb), dim3(kBlock), 0, s, *d, *b, w, n, co, span, scratch);
   else hipLaunchKernelGGL(k_scan_moments_partial<false>, dim3(nb), dim3(kBlock), 0, s, *d, *b, w, n, co, span, scratch);
   return fold_partials<kScanSlots, sum_op>(scratch, nb, out32, s, "art_detector_scan_moments launch");
+}
+
+int art_histogram(const ArtHistogramDesc* h, const ArtBundleView* b, const double* w, int64_t n, int32_t accumulate,
+                  int64_t* counts, int64_t* wsums, int64_t* totals4, void* stream) {
+#pragma clang fp contract(off)
+  if (!h) return fail(ART_ERR_BAD_ARG, "histogram descriptor is NULL");
+  if (h->source != ART_HIST_DETECTOR && h->source != ART_HIST_FRAME) return fail(ART_ERR_BAD_ARG, "unknown histogram source");
+  if (h->ndim < 1 || h->ndim > 3) return fail(ART_ERR_BAD_ARG, "histogram ndim must be 1, 2 or 3");
+  HistArg a;
+  memset(&a, 0, sizeof(a));
+  a.map = h->map;
+  a.delay_centre = h->delay_centre;
+  a.source = h->source;
+  a.wshift = h->wshift;
+  int64_t nbins = 1;
+  for (int k = 0; k < 3; ++k) {
+    a.bins[k] = 1;
+    if (k >= h->ndim) continue;
+    const int ax = h->axis[k];
+    if (ax < 0 || ax > 3 || (ax == 2 && h->source == ART_HIST_DETECTOR)) return fail(ART_ERR_BAD_ARG, "unknown histogram axis");
+    if (h->bins[k] < 1) return fail(ART_ERR_BAD_ARG, "histogram bins must be >= 1");
+    nbins *= h->bins[k];
+    if (nbins > ART_HIST_MAX_BINS) return fail(ART_ERR_UNSUPPORTED, "more than 2^24 histogram bins");
+    const double lo = h->lo[k], hi = h->hi[k], delta = hi - lo, step = delta / (double)h->bins[k];   // numpy.linspace
+    if (!(isfinite(lo) && isfinite(hi) && lo < hi && isfinite(delta) && step > 0.0))
+      return fail(ART_ERR_BAD_ARG, "histogram range: lo < hi must be finite, with a finite non-zero bin width");
+    if (ax == ART_HAXIS_DELAY && h->source == ART_HIST_FRAME)
+      return fail(ART_ERR_BAD_ARG, "a DELAY axis needs the DETECTOR source");
+    a.axis[k] = ax;
+    a.bins[k] = h->bins[k];
+    a.lo[k] = lo; a.hi[k] = hi; a.step[k] = step;
+    a.inv[k] = (double)h->bins[k] / delta;
+  }
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (!counts || !totals4) return fail(ART_ERR_BAD_ARG, "counts/totals4 must not be NULL");
+  if (w && !wsums) return fail(ART_ERR_BAD_ARG, "weights given but wsums is NULL");
+  if (h->wshift < -1074 || h->wshift > 1074) return fail(ART_ERR_BAD_ARG, "wshift outside [-1074, 1074]");
+  if (n > 0 && !view_ok(b)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
+  hipStream_t s = (hipStream_t)stream;
+  if (!accumulate) {
+    hipError_t e = hipMemsetAsync(counts, 0, (size_t)nbins * sizeof(int64_t), s);
+    if (e == hipSuccess && wsums) e = hipMemsetAsync(wsums, 0, (size_t)nbins * sizeof(int64_t), s);
+    if (e == hipSuccess) e = hipMemsetAsync(totals4, 0, 4 * sizeof(int64_t), s);
+    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
+  }
+  if (n == 0) return ART_OK;
+  const bool lds = nbins <= kHistLdsBins;
+  const size_t shmem = lds ? (size_t)nbins * (w ? 12 : 4) : 0;
+  auto* c = reinterpret_cast<unsigned long long*>(counts);
+  auto* ws = reinterpret_cast<unsigned long long*>(wsums);
+  auto* t = reinterpret_cast<unsigned long long*>(totals4);
+  per_launch(n, [&](const int64_t off, const int64_t m) {
+    const int64_t want = ((m + 1) / 2 + kBlock - 1) / kBlock;      // two slots per thread
+    const int nb = (int)(want < 1 ? 1 : (want > kHistBlocks ? kHistBlocks : want));
+    const ArtBundleView v = view_at(*b, off);
+    const double* wo = w ? w + off : nullptr;
+    if (lds) hipLaunchKernelGGL(k_histogram<true>, dim3(nb), dim3(kBlock), shmem, s, a, h->ndim, (int)nbins, v, wo, m, c, ws, t);
+    else hipLaunchKernelGGL(k_histogram<false>, dim3(nb), dim3(kBlock), 0, s, a, h->ndim, (int)nbins, v, wo, m, c, ws, t);
+    return ART_OK;
+  });
+  return launched("art_histogram launch");
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define ART_ABI_VERSION 11
+#define ART_ABI_VERSION 12
 
 /* error codes */
 #define ART_OK 0
@@ -268,6 +268,38 @@ int art_detector_readout(const ArtDetectorDesc* d, const ArtBundleView* b, const
  *        then evaluates the scan positions one by one (a detector scanned through the last optic).            */
 int art_detector_scan_moments(const ArtDetectorDesc* d, const ArtBundleView* b, const double* w, int64_t n, double co,
                               double span, double* scratch, double* out33, void* stream);
+
+/* N-D histogram (N = 1..3) of the ALIVE rays of one bundle, deterministic: integer accumulation only.
+ * Coordinates, by source:
+ *   ART_HIST_DETECTOR: axis ART_HAXIS_X / _Y = (X, Y) of art_detector on `map`; ART_HAXIS_DELAY =
+ *                      ((opl - delay_centre) / 299792458000.0) * 1e15 (fs, Detector.get_Delays' expression);
+ *   ART_HIST_FRAME:    axis k = component k of map.rot * (P - map.centre), P the ray's point (art_transform_bundle).
+ * Bins: edges_k = numpy.linspace(lo_k, hi_k, bins_k + 1) exactly (edge i = i*step + lo, step = (hi - lo)/bins, the
+ * last edge hi); v is in bin j iff edge[j] <= v < edge[j+1], v == hi in the last bin; v < lo, v > hi or NaN is
+ * OUTSIDE.  counts / wsums are row-major, axis 0 slowest (numpy.histogramdd's layout).
+ * Weights: q_i = (int64) rint(ldexp(w_i, wshift)) (half to even); w = NULL: q_i = 0.  The caller picks wshift so that
+ * no sum overflows int64 (e.g. wshift = 62 - ceil(log2(n_total + 1)) - E with max|w| < 2^E) and w must be finite.
+ * Outputs (DEVICE, int64): counts[prod bins], wsums[prod bins] (may be NULL when w is NULL),
+ *   totals4: [0] binned alive rays [1] alive rays outside (or with a non-finite coordinate) [2] sum q binned
+ *            [3] sum q outside.
+ * accumulate = 0: the outputs are zeroed on the stream first; 1: the call adds to them (integers: exact across calls).
+ * Limits: ndim 1..3, bins_k >= 1, prod bins <= 2^24 (ART_ERR_UNSUPPORTED), lo < hi finite with a finite, non-zero
+ * step, no DELAY axis on the FRAME source, wshift in [-1074, 1074]: ART_ERR_BAD_ARG otherwise, with nothing launched. */
+enum ArtHistSource { ART_HIST_DETECTOR = 0, ART_HIST_FRAME = 1 };
+enum ArtHistAxis { ART_HAXIS_X = 0, ART_HAXIS_Y = 1, ART_HAXIS_DELAY = 3 };   /* DETECTOR axes (2 is not one) */
+#define ART_HIST_MAX_BINS (1 << 24)
+typedef struct ArtHistogramDesc {
+  int32_t source, ndim;
+  int32_t axis[3];        /* DETECTOR: ArtHistAxis;  FRAME: component 0/1/2 of rot * (P - centre)          */
+  int32_t bins[3];
+  int32_t wshift;         /* the fixed-point shift of the weights                                          */
+  int32_t reserved;
+  double lo[3], hi[3];
+  double delay_centre;    /* the optical path the DELAY axis is measured from                              */
+  ArtDetectorDesc map;    /* DETECTOR: the detector;  FRAME: rot = M, centre = T                           */
+} ArtHistogramDesc;
+int art_histogram(const ArtHistogramDesc* h, const ArtBundleView* b, const double* w, int64_t n, int32_t accumulate,
+                  int64_t* counts, int64_t* wsums, int64_t* totals4, void* stream);
 
 /* Masked reductions over alive rays, deterministic (fixed two-level tree, no float atomics).
  * out16 (DEVICE, 16 doubles):
