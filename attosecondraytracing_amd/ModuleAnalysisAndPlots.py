@@ -106,6 +106,19 @@ def MirrorFootprint(OpticalChain, ReflectionNumber: int, Bins=200):
     return _plots.MirrorFootprint(OpticalChain, ReflectionNumber, Bins)
 
 
+def FocalSpot(RayListAnalysed, Detector, Size=None, Pixels=128, Log=False):
+    """Image of the coherent focal intensity (Detector.get_FocalField) with the Airy circle and the Strehl ratio;
+    left/right move the detector and re-sum."""
+    from . import _plots
+    return _plots.FocalSpot(RayListAnalysed, Detector, Size, Pixels, Log)
+
+
+def ThroughFocus(RayListAnalysed, Detector, Shifts, Size=None, Pixels=64):
+    """Strehl ratio and peak position of the coherent focal field against the detector shift (all planes in one call)."""
+    from . import _plots
+    return _plots.ThroughFocus(RayListAnalysed, Detector, Shifts, Size, Pixels)
+
+
 def RayRenderGraph(OpticalChain, EndDistance=None, maxRays=300, OEpoints=3000, scale_spheres=5.0, draw_mesh=False,
                    cycle_ray_colors=False):
     """3-D picture of the optical setup and the traced rays (ART/ModuleAnalysisAndPlots.py:616-673)."""

@@ -229,3 +229,12 @@ class Detector:
         or one (lo, hi) per axis.  Shows intensity sums when the rays carry intensities."""
         from . import histogram
         return histogram.detector_histogram(self, RayList, Axes, Bins, Range)
+
+    def get_FocalField(self, RayList, Size=None, Pixels=128, Centre=None, Shifts=None, Wavelength=None, RefPath=None):
+        """Coherent focal field (focal.FocalField) of ALL alive rays, summed on the device as local plane waves on a
+        Pixels grid of Size (mm; scalars or one per axis; default 16 Airy radii) about Centre (detector coordinates;
+        default the bounding-box centre of get_PointList2DCentre), in the planes this detector would occupy after
+        shiftByDistance(s) for s in Shifts (default (0,)).  Wavelength defaults to the bundle's, RefPath (the path of
+        phase 0) to the mean optical path of the alive rays."""
+        from . import focal
+        return focal.focal_field(self, RayList, Size, Pixels, Centre, Shifts, Wavelength, RefPath)

@@ -1,7 +1,7 @@
 """ctypes mirror of include/art_hip.h (structs, enums, prototypes).  Keep in sync with ART_ABI_VERSION."""
 import ctypes as C
 
-ART_ABI_VERSION = 12
+ART_ABI_VERSION = 13
 
 ART_OK = 0
 ART_ERR_BAD_ARG = -1
@@ -120,6 +120,23 @@ class ArtHistogramDesc(C.Structure):
     ]
 
 
+ART_FOCAL_MAX_PIXELS = 2048
+ART_FOCAL_MAX_PLANES = 64
+
+
+class ArtFocalDesc(C.Structure):
+    _fields_ = [
+        ("det", ArtDetectorDesc),
+        ("k", C.c_double), ("L_ref", C.c_double),
+        ("x0", C.c_double), ("dx", C.c_double),
+        ("y0", C.c_double), ("dy", C.c_double),
+        ("nx", C.c_int32), ("ny", C.c_int32),
+        ("planes", C.c_int32),
+        ("reserved", C.c_int32),
+        ("shift", C.c_double * ART_FOCAL_MAX_PLANES),
+    ]
+
+
 # name -> (restype, argtypes); the loader checks every symbol exists (tests/test_abi.py does too)
 PROTOTYPES = {
     "art_abi_version": (C.c_int, []),
@@ -148,6 +165,9 @@ PROTOTYPES = {
                                             C.c_void_p]),
     "art_histogram": (C.c_int, [C.POINTER(ArtHistogramDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64, C.c_int32,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "art_focal_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "art_focal_field": (C.c_int, [C.POINTER(ArtFocalDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
     "art_reduce_scratch_doubles": (C.c_int64, []),
     "art_detector_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -309,6 +309,19 @@ class HipBackend:
                                             totals.data_ptr(), self.stream_ptr()), "art_histogram")
         return counts, wsums, totals, shift
 
+    def focal_field(self, fdesc, view, w, n):
+        """art_focal_field on the current stream: a new device complex128 tensor [planes, ny, nx] (scratch reused per
+        stream)."""
+        field = torch.empty((fdesc.planes, fdesc.ny, fdesc.nx), dtype=torch.complex128, device=self.device)
+        ns = self.fn["art_focal_scratch_doubles"](fdesc.nx, fdesc.ny, fdesc.planes, n)
+        if ns < 0:
+            raise ArtError(f"art_focal_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self.scratch("focal", ns, torch.float64)
+        self.check(self.fn["art_focal_field"](C.byref(fdesc), C.byref(view), None if (w is None or n == 0) else w.data_ptr(),
+                                              n, scratch.data_ptr(), field.data_ptr(), self.stream_ptr()),
+                   "art_focal_field")
+        return field
+
     def _red_scratch(self):
         return self.scratch("red", self.fn["art_reduce_scratch_doubles"](), torch.float64)
 

@@ -350,6 +350,75 @@ def DelayProfile(RayListAnalysed, Detector, Bins=200):
     return fig
 
 
+def _focal_spot_data(B, Detector, Size, Pixels, Log):
+    """The focal field on the detector, the image to show (log10 of the intensity over its peak with Log) and its
+    extent in µm, and the size of the geometric spot (for the step of the next detector move)."""
+    f = Detector.get_FocalField(B, Size=Size, Pixels=Pixels)
+    img = f.intensity[0]
+    if Log:
+        img = np.log10(np.maximum(img / max(img.max(), np.finfo(float).tiny), 1e-12))
+    dx = 0.5 * (f.x[1] - f.x[0]) if len(f.x) > 1 else 0.5
+    dy = 0.5 * (f.y[1] - f.y[0]) if len(f.y) > 1 else 0.5
+    extent = ((f.x[0] - dx) * 1e3, (f.x[-1] + dx) * 1e3, (f.y[0] - dy) * 1e3, (f.y[-1] + dy) * 1e3)
+    s = Detector.readout(B, store=False, lite=True)["stats"]
+    return f, img, extent, max(s[3] - s[2], s[5] - s[4], f.x[-1] - f.x[0])
+
+
+def FocalSpot(RayListAnalysed, Detector, Size=None, Pixels=128, Log=False):
+    """Image of the coherent focal intensity (Detector.get_FocalField) in µm, detector coordinates, with the Airy circle
+    about the grid centre and the Strehl ratio in the title; left/right move the detector and re-sum."""
+    plt = _plt()
+    B = _as_bundle(RayListAnalysed)
+    f, img, extent, size = _focal_spot_data(B, Detector, Size, Pixels, Log)
+    airy = mp.ReturnAiryRadius(f.wavelength, mp.ReturnNumericalAperture(B, 1)) * 1e3
+    cx, cy = 0.5 * (extent[0] + extent[1]), 0.5 * (extent[2] + extent[3])
+    plt.ion()
+    fig, ax = plt.subplots()
+    im = ax.imshow(img, origin="lower", extent=extent, aspect="equal", interpolation="nearest")
+    fig.colorbar(im).set_label("log10 intensity / peak" if Log else "Intensity (arb.u.)")
+    if airy > 0:
+        ax.add_patch(plt.Circle((cx, cy), airy, facecolor="none", edgecolor="w", linestyle="--", label="Airy radius"))
+    title = "Focal spot, {:.3f} mm, Strehl {:.3f}\n press left/right to move detector position"
+    ax.set_title(title.format(Detector.get_distance(), f.strehl[0]))
+    ax.set_xlabel("X (µm)")
+    ax.set_ylabel("Y (µm)")
+    fig._art_focal = f
+
+    def redraw(det, dist):
+        f, img, extent, size = _focal_spot_data(B, det, Size, Pixels, Log)
+        im.set_data(img)
+        im.set_extent(extent)
+        im.autoscale()
+        ax.set_title(title.format(dist, f.strehl[0]))
+        fig._art_focal = f
+        return size
+
+    _interactive(fig, B, Detector, size, redraw)
+    plt.show()
+    return fig
+
+
+def ThroughFocus(RayListAnalysed, Detector, Shifts, Size=None, Pixels=64):
+    """Strehl ratio and peak position (µm, detector coordinates) of the coherent focal field against the detector shift
+    (mm, Detector.shiftByDistance's sign); all planes are summed in one device call."""
+    plt = _plt()
+    B = _as_bundle(RayListAnalysed)
+    f = Detector.get_FocalField(B, Size=Size, Pixels=Pixels, Shifts=Shifts)
+    plt.ion()
+    fig, (a1, a2) = plt.subplots(2, 1, sharex=True)
+    a1.plot(f.shifts, f.strehl, "o-")
+    a1.set_ylabel("Strehl ratio")
+    a1.set_title("Through focus, {:.3f} mm".format(Detector.get_distance()))
+    a2.plot(f.shifts, f.peak[:, 0] * 1e3, "o-", label="X")
+    a2.plot(f.shifts, f.peak[:, 1] * 1e3, "s-", label="Y")
+    a2.set_ylabel("Peak position (µm)")
+    a2.set_xlabel("Detector shift (mm)")
+    a2.legend(loc="upper right")
+    fig._art_focal = f
+    plt.show()
+    return fig
+
+
 def MirrorFootprint(OpticalChain, ReflectionNumber: int, Bins=200):
     """Image of the footprint of ALL rays on one optical element (OpticalChain.get_Footprint) over its support
     outline."""

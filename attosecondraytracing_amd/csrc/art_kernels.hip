@@ -1531,6 +1531,159 @@ __global__ __launch_bounds__(kBlock) void k_histogram(const HistArg a, const int
   }
 }
 
+// ------------------------------------------------------------------------------------------- focal field
+// art_focal_field: E_q = V^T diag(c_q) U, a complex GEMM over the rays in which U and V are never stored.
+// k_focal_prep writes, per slot, the amplitude and the phase coefficients of the ray into kFocalRows rows of scratch (a
+// dead slot gets amplitude 0).  k_focal_field: one workgroup per (64 x 64 pixel tile, plane, slice of the rays); per
+// chunk of kFocalChunk rays it forms the chunk's column phasors U and row phasors c_q V in LDS -- fp64 sincos at every
+// kFocalSeg-th pixel, rotations by the ray's one-pixel step in between (at most kFocalSeg - 1 of them: ~1e-15 rad) --
+// and every lane accumulates a 4 x 4 block of pixels with fp64 FMAs.  k_focal_fold adds the slices' partials in slice
+// order.  No float atomics: the same bytes on every call.
+constexpr int kFocalRows = 9;         // amp, base, k d.e1, k d.e2, k d.n, exp(i k d.e1 dx) (2), exp(i k d.e2 dy) (2)
+constexpr int kFocalTile = 64;        // pixels per tile side
+constexpr int kFocalLanes = 16;       // lanes per tile side: lane (lx, ly) owns columns lx + 16u and rows ly + 16v
+constexpr int kFocalMicro = kFocalTile / kFocalLanes;
+constexpr int kFocalChunk = 32;       // rays per LDS stage: 2 x 32 KiB of phasors
+constexpr int kFocalSeg = 16;         // phasors per sincos: kBlock / 2 lanes build 32 rays x 4 segments of each kind
+constexpr int kFocalMaxSlices = 64;
+constexpr int kFocalWantBlocks = 2048;   // 8 workgroups per CU when the grid has enough tiles x planes x slices
+static_assert(kFocalChunk * (kFocalTile / kFocalSeg) * 2 == kBlock, "one phasor segment per lane");
+
+struct FocalArg {
+  double k, L_ref, x0, dx, y0, dy;
+  double C[3], nrm[3], e1[3], e2[3];
+  int64_t stride, per_slice, n;   // scratch row stride; rays per slice; slots
+  int32_t nx, ny, planes, tiles_x;
+  double shift[ART_FOCAL_MAX_PLANES];
+};
+
+inline int64_t focal_stride(int64_t n) { return (n + 63) / 64 * 64; }
+
+// slices of the rays: enough workgroups to fill the machine, at least 4 chunks of rays per slice
+inline int focal_slices(int nx, int ny, int planes, int64_t n) {
+  const int64_t wgs = (int64_t)((nx + kFocalTile - 1) / kFocalTile) * ((ny + kFocalTile - 1) / kFocalTile) * planes;
+  int64_t s = (kFocalWantBlocks + wgs - 1) / wgs;
+  const int64_t by_rays = (n + 4 * kFocalChunk - 1) / (4 * kFocalChunk);
+  if (s > by_rays) s = by_rays;
+  if (s > kFocalMaxSlices) s = kFocalMaxSlices;
+  return s < 1 ? 1 : (int)s;
+}
+
+__global__ __launch_bounds__(kBlock) void k_focal_prep(const FocalArg a, const ArtBundleView b, const double* w,
+                                                       const int64_t m, double* rows) {
+#pragma clang fp contract(off)
+  const int64_t st = a.stride;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
+    const bool live = b.alive[i] != 0;
+    const double px = b.ox[i], py = b.oy[i], pz = b.oz[i], dx = b.dx[i], dy = b.dy[i], dz = b.dz[i];
+    // a dead slot's values are unspecified (possibly NaN): selected away
+    const double amp = live ? (w ? sqrt(w[i]) : 1.0) : 0.0;
+    const double base = live ? a.k * ((b.path[i] - a.L_ref) + ((dx * (a.C[0] - px) + dy * (a.C[1] - py)) + dz * (a.C[2] - pz)))
+                             : 0.0;
+    const double ka = live ? a.k * ((dx * a.e1[0] + dy * a.e1[1]) + dz * a.e1[2]) : 0.0;
+    const double kb = live ? a.k * ((dx * a.e2[0] + dy * a.e2[1]) + dz * a.e2[2]) : 0.0;
+    const double kc = live ? a.k * ((dx * a.nrm[0] + dy * a.nrm[1]) + dz * a.nrm[2]) : 0.0;
+    double sa, ca, sb, cb;
+    sincos(ka * a.dx, &sa, &ca);
+    sincos(kb * a.dy, &sb, &cb);
+    rows[i] = amp; rows[st + i] = base; rows[2 * st + i] = ka; rows[3 * st + i] = kb; rows[4 * st + i] = kc;
+    rows[5 * st + i] = ca; rows[6 * st + i] = sa; rows[7 * st + i] = cb; rows[8 * st + i] = sb;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_focal_field(const FocalArg a, const double* __restrict__ rows,
+                                                        double* __restrict__ out) {
+  __shared__ double2 sU[kFocalChunk][kFocalTile];     // exp(i X_j k d.e1)
+  __shared__ double2 sW[kFocalChunk][kFocalTile];     // amp exp(i (base + s_q k d.n + Y_l k d.e2))
+  const int q = blockIdx.y, slice = blockIdx.z;
+  const int tx0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * kFocalTile, ty0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * kFocalTile;
+  const int t = threadIdx.x, lx = t % kFocalLanes, ly = t / kFocalLanes;
+  const int64_t st = a.stride, r0 = (int64_t)slice * a.per_slice;
+  const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
+  const double sh = a.shift[q];
+  // staging role of this lane: rows (W) or columns (U), ray sr of the chunk, segment sg of the tile
+  const bool colw = t < kBlock / 2;
+  const int sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg), sg = t % (kFocalTile / kFocalSeg);
+  double acc_re[kFocalMicro][kFocalMicro], acc_im[kFocalMicro][kFocalMicro];
+#pragma unroll
+  for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+    for (int u = 0; u < kFocalMicro; ++u) acc_re[v][u] = acc_im[v][u] = 0.0;
+
+  for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
+    const int64_t r = c0 + sr;
+    const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
+    double ph, amp, s_re, s_im;
+    int p0;
+    if (colw) {
+      p0 = tx0 + sg * kFocalSeg;
+      const double ka = in ? rows[2 * st + r] : 0.0;
+      ph = ka * (a.x0 + (double)p0 * a.dx);
+      amp = 1.0;
+      s_re = in ? rows[5 * st + r] : 1.0; s_im = in ? rows[6 * st + r] : 0.0;
+    } else {
+      p0 = ty0 + sg * kFocalSeg;
+      const double base = in ? rows[st + r] : 0.0, kb = in ? rows[3 * st + r] : 0.0, kc = in ? rows[4 * st + r] : 0.0;
+      ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
+      amp = in ? rows[r] : 0.0;
+      s_re = in ? rows[7 * st + r] : 1.0; s_im = in ? rows[8 * st + r] : 0.0;
+    }
+    double sn, cs;
+    sincos(ph, &sn, &cs);
+    double z_re = amp * cs, z_im = amp * sn;
+    double2* dst = colw ? &sU[sr][sg * kFocalSeg] : &sW[sr][sg * kFocalSeg];
+#pragma unroll
+    for (int m = 0; m < kFocalSeg; ++m) {
+      dst[m] = make_double2(z_re, z_im);
+      const double n_re = z_re * s_re - z_im * s_im;
+      z_im = z_re * s_im + z_im * s_re;
+      z_re = n_re;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int rr = 0; rr < kFocalChunk; ++rr) {
+      double2 uu[kFocalMicro], vv[kFocalMicro];
+#pragma unroll
+      for (int i = 0; i < kFocalMicro; ++i) {
+        uu[i] = sU[rr][lx + kFocalLanes * i];
+        vv[i] = sW[rr][ly + kFocalLanes * i];
+      }
+#pragma unroll
+      for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+        for (int u = 0; u < kFocalMicro; ++u) {
+          acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
+          acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
+          acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
+          acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
+        }
+    }
+    __syncthreads();
+  }
+  double2* o = reinterpret_cast<double2*>(out) + ((int64_t)slice * a.planes + q) * a.ny * a.nx;
+#pragma unroll
+  for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+    for (int u = 0; u < kFocalMicro; ++u) {
+      const int l = ty0 + ly + kFocalLanes * v, j = tx0 + lx + kFocalLanes * u;
+      if (l < a.ny && j < a.nx) o[(int64_t)l * a.nx + j] = make_double2(acc_re[v][u], acc_im[v][u]);
+    }
+}
+
+// field[p] = sum over the slices in slice order of partial[slice][p]
+__global__ __launch_bounds__(kBlock) void k_focal_fold(const double2* __restrict__ part, const int slices,
+                                                       const int64_t pixels, double2* __restrict__ field) {
+  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < pixels; p += (int64_t)gridDim.x * kBlock) {
+    double re = 0.0, im = 0.0;
+    for (int s = 0; s < slices; ++s) {
+      const double2 v = part[(int64_t)s * pixels + p];
+      re += v.x;
+      im += v.y;
+    }
+    field[p] = make_double2(re, im);
+  }
+}
+
 template <bool HAS_W>
 __global__ __launch_bounds__(kBlock) void k_moments_partial(const uint8_t* alive, const double* X, const double* Y,
                                                             const double* opl, const double* w, const int64_t n,
@@ -2762,6 +2915,64 @@ int art_histogram(const ArtHistogramDesc* h, const ArtBundleView* b, const doubl
     return ART_OK;
   });
   return launched("art_histogram launch");
+}
+
+int64_t art_focal_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int64_t n) {
+  if (nx < 1 || ny < 1 || nx > ART_FOCAL_MAX_PIXELS || ny > ART_FOCAL_MAX_PIXELS || planes < 1 ||
+      planes > ART_FOCAL_MAX_PLANES || n < 0)
+    return fail(ART_ERR_BAD_ARG, "focal scratch: nx, ny in [1, 2048], planes in [1, 64], n >= 0");
+  const int S = focal_slices(nx, ny, planes, n);
+  return (int64_t)kFocalRows * focal_stride(n) + (S > 1 ? (int64_t)S * planes * ny * nx * 2 : 0);
+}
+
+int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
+                    double* field, void* stream) {
+  if (!f) return fail(ART_ERR_BAD_ARG, "focal descriptor is NULL");
+  if (f->nx < 1 || f->ny < 1 || f->nx > ART_FOCAL_MAX_PIXELS || f->ny > ART_FOCAL_MAX_PIXELS)
+    return fail(ART_ERR_BAD_ARG, "focal grid: nx and ny must be in [1, 2048]");
+  if (f->planes < 1 || f->planes > ART_FOCAL_MAX_PLANES) return fail(ART_ERR_BAD_ARG, "focal planes must be in [1, 64]");
+  if (!(isfinite(f->k) && f->k > 0.0)) return fail(ART_ERR_BAD_ARG, "focal k must be finite and > 0");
+  if (!(isfinite(f->dx) && isfinite(f->dy))) return fail(ART_ERR_BAD_ARG, "focal pixel pitch must be finite");
+  for (int q = 0; q < f->planes; ++q)
+    if (!isfinite(f->shift[q])) return fail(ART_ERR_BAD_ARG, "focal plane shifts must be finite");
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (n > 0 && (!field || !scratch)) return fail(ART_ERR_BAD_ARG, "focal field/scratch must not be NULL");
+  if (n > 0 && !view_ok(b)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t pixels = (int64_t)f->planes * f->ny * f->nx;
+  if (n == 0) {
+    if (!field) return ART_OK;
+    const hipError_t e = hipMemsetAsync(field, 0, (size_t)pixels * 2 * sizeof(double), s);
+    return e == hipSuccess ? ART_OK : fail_hip(e, "hipMemsetAsync");
+  }
+  FocalArg a;
+  memset(&a, 0, sizeof(a));
+  a.k = f->k; a.L_ref = f->L_ref; a.x0 = f->x0; a.dx = f->dx; a.y0 = f->y0; a.dy = f->dy;
+  for (int c = 0; c < 3; ++c) {
+    a.C[c] = f->det.centre[c]; a.nrm[c] = f->det.normal[c];
+    a.e1[c] = f->det.rot[c]; a.e2[c] = f->det.rot[3 + c];
+  }
+  const int S = focal_slices(f->nx, f->ny, f->planes, n);
+  a.stride = focal_stride(n);
+  a.per_slice = (n + S - 1) / S;
+  a.n = n;
+  a.nx = f->nx; a.ny = f->ny; a.planes = f->planes;
+  a.tiles_x = (f->nx + kFocalTile - 1) / kFocalTile;
+  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
+  for (int q = 0; q < f->planes; ++q) a.shift[q] = f->shift[q];
+  per_launch(n, [&](const int64_t off, const int64_t m) {
+    hipLaunchKernelGGL(k_focal_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off), w ? w + off : nullptr,
+                       m, scratch + off);
+    return ART_OK;
+  });
+  double* part = S > 1 ? scratch + (int64_t)kFocalRows * a.stride : field;
+  hipLaunchKernelGGL(k_focal_field, dim3(tiles, f->planes, S), dim3(kBlock), 0, s, a, (const double*)scratch, part);
+  if (S > 1) {
+    const int64_t want = (pixels + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_focal_fold, dim3((int)(want > kMaxBlocks ? kMaxBlocks : want)), dim3(kBlock), 0, s,
+                       (const double2*)part, S, pixels, reinterpret_cast<double2*>(field));
+  }
+  return launched("art_focal_field launch");
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define ART_ABI_VERSION 12
+#define ART_ABI_VERSION 13
 
 /* error codes */
 #define ART_OK 0
@@ -300,6 +300,37 @@ typedef struct ArtHistogramDesc {
 } ArtHistogramDesc;
 int art_histogram(const ArtHistogramDesc* h, const ArtBundleView* b, const double* w, int64_t n, int32_t accumulate,
                   int64_t* counts, int64_t* wsums, int64_t* totals4, void* stream);
+
+/* Coherent focal field of the ALIVE rays of one bundle on a pixel grid of up to 64 planes (the Debye / angular-spectrum
+ * picture: every ray is a local plane wave).  With e1, e2 = rows 0 and 1 of det.rot, n = det.normal, C = det.centre:
+ *     x_qjl    = C + shift[q] n + X_j e1 + Y_l e2,     X_j = x0 + j*dx,  Y_l = y0 + l*dy
+ *     E_q[l,j] = sum_r sqrt(w_r) exp(i k [(path_r - L_ref) + d_r . (x_qjl - p_r)])
+ * p_r, d_r, path_r the ray's point, direction and path; w_r = w[r] (w = NULL: 1); dead slots contribute nothing.  At
+ * a ray's own hit point the phase is k (opl_r - L_ref), opl_r the value of art_detector.  The phase is separated as
+ *     base_r = k * ((path_r - L_ref) + ((d_x (C_x - p_x) + d_y (C_y - p_y)) + d_z (C_z - p_z)))   (this order, no fma)
+ *     phase  = base_r + shift[q] * k (d.n) + X_j * k (d.e1) + Y_l * k (d.e2)
+ * field (DEVICE, complex128 = (re, im) doubles, [planes][ny][nx]) is written, not added to; n = 0 writes zeros.  The
+ * sum runs in a fixed order (no float atomics): the same bytes on every call with the same arguments.
+ * scratch: DEVICE, art_focal_scratch_doubles(nx, ny, planes, n) doubles.
+ * Limits: 1 <= nx, ny <= ART_FOCAL_MAX_PIXELS, 1 <= planes <= ART_FOCAL_MAX_PLANES, k > 0 finite, dx, dy and the
+ * shifts finite, field and scratch non-NULL when n > 0: ART_ERR_BAD_ARG otherwise, with nothing launched and field
+ * untouched. */
+#define ART_FOCAL_MAX_PIXELS 2048
+#define ART_FOCAL_MAX_PLANES 64
+typedef struct ArtFocalDesc {
+  ArtDetectorDesc det;
+  double k;               /* 2 pi / wavelength, 1/mm                                                       */
+  double L_ref;           /* the optical path of phase 0                                                   */
+  double x0, dx;          /* pixel centres X_j = x0 + j*dx, detector coordinates (mm)                      */
+  double y0, dy;
+  int32_t nx, ny;
+  int32_t planes;
+  int32_t reserved;
+  double shift[ART_FOCAL_MAX_PLANES];   /* plane q lies at C + shift[q] * det.normal                      */
+} ArtFocalDesc;
+int64_t art_focal_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int64_t n);
+int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
+                    double* field, void* stream);
 
 /* Masked reductions over alive rays, deterministic (fixed two-level tree, no float atomics).
  * out16 (DEVICE, 16 doubles):
