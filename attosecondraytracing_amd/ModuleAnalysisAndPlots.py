@@ -119,6 +119,19 @@ def ThroughFocus(RayListAnalysed, Detector, Shifts, Size=None, Pixels=64):
     return _plots.ThroughFocus(RayListAnalysed, Detector, Shifts, Size, Pixels)
 
 
+def PulseAtFocus(RayListAnalysed, Detector, DeltaFT, Size=None, Pixels=64):
+    """The pulse at focus (Detector.get_FocalPulse): I(X, t) along the peak row, I(Y, t) along the peak column, and the
+    on-peak and pixel-integrated temporal profiles against the Fourier-limited Gaussian of DeltaFT (fs)."""
+    from . import _plots
+    return _plots.PulseAtFocus(RayListAnalysed, Detector, DeltaFT, Size, Pixels)
+
+
+def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pixels=64):
+    """Space-time Strehl ratio and on-peak duration of the pulse against the detector shift (all planes in one call)."""
+    from . import _plots
+    return _plots.PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size, Pixels)
+
+
 def RayRenderGraph(OpticalChain, EndDistance=None, maxRays=300, OEpoints=3000, scale_spheres=5.0, draw_mesh=False,
                    cycle_ray_colors=False):
     """3-D picture of the optical setup and the traced rays (ART/ModuleAnalysisAndPlots.py:616-673)."""

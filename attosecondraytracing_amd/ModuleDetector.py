@@ -238,3 +238,14 @@ class Detector:
         phase 0) to the mean optical path of the alive rays."""
         from . import focal
         return focal.focal_field(self, RayList, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+
+    def get_FocalPulse(self, RayList, DeltaFT, Size=None, Pixels=64, Centre=None, Shifts=None, Wavelength=None,
+                       RefPath=None, Spectrum=None, TimeWindow=None, Times=256):
+        """Space-time focal field of a pulse (pulse.FocalPulse): the focal fields of get_FocalField (same Size, Pixels,
+        Centre, Shifts, Wavelength, RefPath) at the frequencies of a pulse of Fourier-limited duration DeltaFT (fs),
+        summed on the device in one call, and their Fourier sum at Times instants of a window TimeWindow (fs) about
+        t = RefPath / c.  Spectrum: a callable omega (rad/fs) -> complex amplitude replacing the transform-limited
+        Gaussian (e.g. a chirp).  Gives I(x, y, t), the space-time Strehl ratio, the duration and the pulse front."""
+        from . import pulse
+        return pulse.focal_pulse(self, RayList, DeltaFT, Size, Pixels, Centre, Shifts, Wavelength, RefPath, Spectrum,
+                                 TimeWindow, Times)

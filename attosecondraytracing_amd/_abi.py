@@ -1,7 +1,7 @@
 """ctypes mirror of include/art_hip.h (structs, enums, prototypes).  Keep in sync with ART_ABI_VERSION."""
 import ctypes as C
 
-ART_ABI_VERSION = 13
+ART_ABI_VERSION = 14
 
 ART_OK = 0
 ART_ERR_BAD_ARG = -1
@@ -137,6 +137,18 @@ class ArtFocalDesc(C.Structure):
     ]
 
 
+ART_FOCAL_MAX_WAVENUMBERS = 1024
+
+
+class ArtFocalSpectrumDesc(C.Structure):
+    _fields_ = [
+        ("f", ArtFocalDesc),
+        ("dk", C.c_double),
+        ("nk", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 # name -> (restype, argtypes); the loader checks every symbol exists (tests/test_abi.py does too)
 PROTOTYPES = {
     "art_abi_version": (C.c_int, []),
@@ -168,6 +180,9 @@ PROTOTYPES = {
     "art_focal_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "art_focal_field": (C.c_int, [C.POINTER(ArtFocalDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64, C.c_void_p,
                                   C.c_void_p, C.c_void_p]),
+    "art_focal_spectrum_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "art_focal_spectrum": (C.c_int, [C.POINTER(ArtFocalSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_reduce_scratch_doubles": (C.c_int64, []),
     "art_detector_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -322,6 +322,20 @@ class HipBackend:
                    "art_focal_field")
         return field
 
+    def focal_spectrum(self, sdesc, view, w, n):
+        """art_focal_spectrum on the current stream: a new device complex128 tensor [planes, nk, ny, nx] (scratch
+        reused per stream)."""
+        f = sdesc.f
+        field = torch.empty((f.planes, sdesc.nk, f.ny, f.nx), dtype=torch.complex128, device=self.device)
+        ns = self.fn["art_focal_spectrum_scratch_doubles"](f.nx, f.ny, f.planes, sdesc.nk, n)
+        if ns < 0:
+            raise ArtError(f"art_focal_spectrum_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self.scratch("focal", ns, torch.float64)
+        self.check(self.fn["art_focal_spectrum"](C.byref(sdesc), C.byref(view), None if (w is None or n == 0) else
+                                                 w.data_ptr(), n, scratch.data_ptr(), field.data_ptr(),
+                                                 self.stream_ptr()), "art_focal_spectrum")
+        return field
+
     def _red_scratch(self):
         return self.scratch("red", self.fn["art_reduce_scratch_doubles"](), torch.float64)
 

@@ -419,6 +419,67 @@ def ThroughFocus(RayListAnalysed, Detector, Shifts, Size=None, Pixels=64):
     return fig
 
 
+def PulseAtFocus(RayListAnalysed, Detector, DeltaFT, Size=None, Pixels=64):
+    """Three panels of the pulse at focus (Detector.get_FocalPulse): I(X, t) along the row of the space-time peak,
+    I(Y, t) along its column (µm, fs), and the on-peak and pixel-integrated temporal profiles, each over its maximum,
+    against the Fourier-limited Gaussian of DeltaFT centred on the peak."""
+    plt = _plt()
+    B = _as_bundle(RayListAnalysed)
+    p = Detector.get_FocalPulse(B, DeltaFT, Size=Size, Pixels=Pixels)
+    I = p.intensity[0]
+    n, l, j = np.unravel_index(int(np.argmax(I)), I.shape)
+    t = p.t
+    dt = 0.5 * (t[1] - t[0]) if len(t) > 1 else 0.5
+
+    def extent(a):
+        da = 0.5 * (a[1] - a[0]) if len(a) > 1 else 0.5
+        return ((a[0] - da) * 1e3, (a[-1] + da) * 1e3, t[0] - dt, t[-1] + dt)
+
+    plt.ion()
+    fig, (a1, a2, a3) = plt.subplots(1, 3, figsize=(15, 4.5))
+    for ax, img, axis, name in ((a1, I[:, l, :], p.x, "X"), (a2, I[:, :, j], p.y, "Y")):
+        im = ax.imshow(img, origin="lower", extent=extent(axis), aspect="auto", interpolation="nearest")
+        fig.colorbar(im, ax=ax).set_label("Intensity (arb.u.)")
+        ax.set_xlabel(f"{name} (µm)")
+        ax.set_ylabel("t (fs)")
+        ax.set_title(f"I({name}, t) through the peak")
+    peak_t = p.peak[0, 2] if np.isfinite(p.peak[0, 2]) else 0.0
+    a3.plot(t, I[:, l, j] / max(I[:, l, j].max(), np.finfo(float).tiny), label=f"on peak, FWHM {p.duration[0]:.3g} fs")
+    a3.plot(t, p.profile[0] / max(p.profile[0].max(), np.finfo(float).tiny),
+            label=f"integrated, FWHM {p.duration_integrated[0]:.3g} fs")
+    a3.plot(t, np.exp(-4 * np.log(2) * (t - peak_t) ** 2 / DeltaFT ** 2), "k--",
+            label=f"Fourier limit, {DeltaFT:.3g} fs")
+    a3.set_xlabel("t (fs)")
+    a3.set_ylabel("Intensity / maximum")
+    a3.legend(loc="upper right")
+    a3.set_title("Pulse at {:.3f} mm, Strehl {:.3f}".format(Detector.get_distance(), p.strehl[0]))
+    fig._art_pulse = p
+    plt.show()
+    return fig
+
+
+def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pixels=64):
+    """Space-time Strehl ratio and on-peak duration (fs) of the pulse against the detector shift (mm,
+    Detector.shiftByDistance's sign); all planes and frequencies are summed in one device call."""
+    plt = _plt()
+    B = _as_bundle(RayListAnalysed)
+    p = Detector.get_FocalPulse(B, DeltaFT, Size=Size, Pixels=Pixels, Shifts=Shifts)
+    plt.ion()
+    fig, (a1, a2) = plt.subplots(2, 1, sharex=True)
+    a1.plot(p.shifts, p.strehl, "o-")
+    a1.set_ylabel("Space-time Strehl ratio")
+    a1.set_title("Pulse through focus, {:.3f} mm".format(Detector.get_distance()))
+    a2.plot(p.shifts, p.duration, "o-", label="on peak")
+    a2.plot(p.shifts, p.duration_integrated, "s-", label="integrated")
+    a2.axhline(DeltaFT, color="k", linestyle="--", label="Fourier limit")
+    a2.set_ylabel("Duration (fs)")
+    a2.set_xlabel("Detector shift (mm)")
+    a2.legend(loc="upper right")
+    fig._art_pulse = p
+    plt.show()
+    return fig
+
+
 def MirrorFootprint(OpticalChain, ReflectionNumber: int, Bins=200):
     """Image of the footprint of ALL rays on one optical element (OpticalChain.get_Footprint) over its support
     outline."""

@@ -1684,6 +1684,130 @@ __global__ __launch_bounds__(kBlock) void k_focal_fold(const double2* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------- focal spectrum
+// art_focal_spectrum: the focal field at nk wavenumbers k_j = k_0 + j dk from one bundle (mirrors are achromatic, so
+// only the phase k (optical path) changes with k).  k_focal_spectrum_prep writes the k-independent rows of each slot
+// (amp, base / k, d.e1, d.e2, d.n; a dead slot gets amplitude 0).  k_focal_spectrum_field is k_focal_field with
+// (plane, wavenumber) on the grid's y dimension: its staging lanes scale the rows by k_j and form the one-pixel step
+// phasor themselves (one more sincos per lane and chunk), with the operations and their order of k_focal_prep /
+// k_focal_field, so that a slice equals art_focal_field's at k = k_j.  The slices' partials go through k_focal_fold.
+// It is a kernel of its own: k_focal_field, refactored into shared inline helpers, compiles to other instructions.
+constexpr int kFocalSpecRows = 5;     // amp, base / k, d.e1, d.e2, d.n
+
+// a product that is never contracted into an FMA: k_j * row rounds as k * (...) does in k_focal_prep
+__device__ __forceinline__ double focal_mul(const double a, const double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// k_j = k_0 + j * dk, unfused (k_0 exactly at j = 0); the host's validation forms it the same way
+__host__ __device__ inline double focal_kj(const double k0, const int j, const double dk) {
+#pragma clang fp contract(off)
+  return k0 + (double)j * dk;
+}
+
+__global__ __launch_bounds__(kBlock) void k_focal_spectrum_prep(const FocalArg a, const ArtBundleView b,
+                                                                const double* w, const int64_t m, double* rows) {
+#pragma clang fp contract(off)
+  const int64_t st = a.stride;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
+    const bool live = b.alive[i] != 0;
+    const double px = b.ox[i], py = b.oy[i], pz = b.oz[i], dx = b.dx[i], dy = b.dy[i], dz = b.dz[i];
+    // a dead slot's values are unspecified (possibly NaN): selected away
+    const double amp = live ? (w ? sqrt(w[i]) : 1.0) : 0.0;
+    const double base = live ? (b.path[i] - a.L_ref) + ((dx * (a.C[0] - px) + dy * (a.C[1] - py)) + dz * (a.C[2] - pz))
+                             : 0.0;
+    const double da = live ? (dx * a.e1[0] + dy * a.e1[1]) + dz * a.e1[2] : 0.0;
+    const double db = live ? (dx * a.e2[0] + dy * a.e2[1]) + dz * a.e2[2] : 0.0;
+    const double dc = live ? (dx * a.nrm[0] + dy * a.nrm[1]) + dz * a.nrm[2] : 0.0;
+    rows[i] = amp; rows[st + i] = base; rows[2 * st + i] = da; rows[3 * st + i] = db; rows[4 * st + i] = dc;
+  }
+}
+
+// blockIdx.y = q * nk + j (plane q, wavenumber j): out is [slice][planes][nk][ny][nx]
+__global__ __launch_bounds__(kBlock) void k_focal_spectrum_field(const FocalArg a, const double dk, const int nk,
+                                                                 const double* __restrict__ rows,
+                                                                 double* __restrict__ out) {
+  __shared__ double2 sU[kFocalChunk][kFocalTile];     // exp(i X_j k d.e1)
+  __shared__ double2 sW[kFocalChunk][kFocalTile];     // amp exp(i (base + s_q k d.n + Y_l k d.e2))
+  const int qj = blockIdx.y, q = qj / nk, slice = blockIdx.z;
+  const double kj = focal_kj(a.k, qj - q * nk, dk);
+  const int tx0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * kFocalTile, ty0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * kFocalTile;
+  const int t = threadIdx.x, lx = t % kFocalLanes, ly = t / kFocalLanes;
+  const int64_t st = a.stride, r0 = (int64_t)slice * a.per_slice;
+  const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
+  const double sh = a.shift[q];
+  // staging role of this lane: rows (W) or columns (U), ray sr of the chunk, segment sg of the tile
+  const bool colw = t < kBlock / 2;
+  const int sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg), sg = t % (kFocalTile / kFocalSeg);
+  double acc_re[kFocalMicro][kFocalMicro], acc_im[kFocalMicro][kFocalMicro];
+#pragma unroll
+  for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+    for (int u = 0; u < kFocalMicro; ++u) acc_re[v][u] = acc_im[v][u] = 0.0;
+
+  for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
+    const int64_t r = c0 + sr;
+    const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
+    double ph, amp, s_re, s_im;
+    int p0;
+    if (colw) {
+      p0 = tx0 + sg * kFocalSeg;
+      const double ka = focal_mul(kj, in ? rows[2 * st + r] : 0.0);
+      ph = ka * (a.x0 + (double)p0 * a.dx);
+      amp = 1.0;
+      sincos(focal_mul(ka, a.dx), &s_im, &s_re);
+    } else {
+      p0 = ty0 + sg * kFocalSeg;
+      const double base = focal_mul(kj, in ? rows[st + r] : 0.0), kb = focal_mul(kj, in ? rows[3 * st + r] : 0.0),
+                   kc = focal_mul(kj, in ? rows[4 * st + r] : 0.0);
+      ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
+      amp = in ? rows[r] : 0.0;
+      sincos(focal_mul(kb, a.dy), &s_im, &s_re);
+    }
+    double sn, cs;
+    sincos(ph, &sn, &cs);
+    double z_re = amp * cs, z_im = amp * sn;
+    double2* dst = colw ? &sU[sr][sg * kFocalSeg] : &sW[sr][sg * kFocalSeg];
+#pragma unroll
+    for (int m = 0; m < kFocalSeg; ++m) {
+      dst[m] = make_double2(z_re, z_im);
+      // the fused forms the compiler picks for k_focal_field's contracted expressions: the same roundings
+      const double n_re = fma(z_re, s_re, -(z_im * s_im));
+      z_im = fma(z_re, s_im, z_im * s_re);
+      z_re = n_re;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int rr = 0; rr < kFocalChunk; ++rr) {
+      double2 uu[kFocalMicro], vv[kFocalMicro];
+#pragma unroll
+      for (int i = 0; i < kFocalMicro; ++i) {
+        uu[i] = sU[rr][lx + kFocalLanes * i];
+        vv[i] = sW[rr][ly + kFocalLanes * i];
+      }
+#pragma unroll
+      for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+        for (int u = 0; u < kFocalMicro; ++u) {
+          acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
+          acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
+          acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
+          acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
+        }
+    }
+    __syncthreads();
+  }
+  double2* o = reinterpret_cast<double2*>(out) + ((int64_t)slice * gridDim.y + qj) * a.ny * a.nx;
+#pragma unroll
+  for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+    for (int u = 0; u < kFocalMicro; ++u) {
+      const int l = ty0 + ly + kFocalLanes * v, j = tx0 + lx + kFocalLanes * u;
+      if (l < a.ny && j < a.nx) o[(int64_t)l * a.nx + j] = make_double2(acc_re[v][u], acc_im[v][u]);
+    }
+}
+
 template <bool HAS_W>
 __global__ __launch_bounds__(kBlock) void k_moments_partial(const uint8_t* alive, const double* X, const double* Y,
                                                             const double* opl, const double* w, const int64_t n,
@@ -2925,9 +3049,8 @@ int64_t art_focal_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int64_
   return (int64_t)kFocalRows * focal_stride(n) + (S > 1 ? (int64_t)S * planes * ny * nx * 2 : 0);
 }
 
-int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
-                    double* field, void* stream) {
-  if (!f) return fail(ART_ERR_BAD_ARG, "focal descriptor is NULL");
+// the checks of an ArtFocalDesc that do not depend on the call's other arguments
+static int focal_desc_check(const ArtFocalDesc* f) {
   if (f->nx < 1 || f->ny < 1 || f->nx > ART_FOCAL_MAX_PIXELS || f->ny > ART_FOCAL_MAX_PIXELS)
     return fail(ART_ERR_BAD_ARG, "focal grid: nx and ny must be in [1, 2048]");
   if (f->planes < 1 || f->planes > ART_FOCAL_MAX_PLANES) return fail(ART_ERR_BAD_ARG, "focal planes must be in [1, 64]");
@@ -2935,16 +3058,27 @@ int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double*
   if (!(isfinite(f->dx) && isfinite(f->dy))) return fail(ART_ERR_BAD_ARG, "focal pixel pitch must be finite");
   for (int q = 0; q < f->planes; ++q)
     if (!isfinite(f->shift[q])) return fail(ART_ERR_BAD_ARG, "focal plane shifts must be finite");
+  return ART_OK;
+}
+
+// the checks of the rays and buffers, and the zeros of an empty call (*done = true then)
+static int focal_call_check(const ArtBundleView* b, int64_t n, const double* scratch, double* field, int64_t pixels,
+                            hipStream_t s, bool* done) {
+  *done = true;
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   if (n > 0 && (!field || !scratch)) return fail(ART_ERR_BAD_ARG, "focal field/scratch must not be NULL");
   if (n > 0 && !view_ok(b)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t pixels = (int64_t)f->planes * f->ny * f->nx;
   if (n == 0) {
     if (!field) return ART_OK;
     const hipError_t e = hipMemsetAsync(field, 0, (size_t)pixels * 2 * sizeof(double), s);
     return e == hipSuccess ? ART_OK : fail_hip(e, "hipMemsetAsync");
   }
+  *done = false;
+  return ART_OK;
+}
+
+// the kernels' argument for n > 0 rays in S slices
+static FocalArg focal_arg(const ArtFocalDesc* f, int64_t n, int S) {
   FocalArg a;
   memset(&a, 0, sizeof(a));
   a.k = f->k; a.L_ref = f->L_ref; a.x0 = f->x0; a.dx = f->dx; a.y0 = f->y0; a.dy = f->dy;
@@ -2952,14 +3086,26 @@ int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double*
     a.C[c] = f->det.centre[c]; a.nrm[c] = f->det.normal[c];
     a.e1[c] = f->det.rot[c]; a.e2[c] = f->det.rot[3 + c];
   }
-  const int S = focal_slices(f->nx, f->ny, f->planes, n);
   a.stride = focal_stride(n);
   a.per_slice = (n + S - 1) / S;
   a.n = n;
   a.nx = f->nx; a.ny = f->ny; a.planes = f->planes;
   a.tiles_x = (f->nx + kFocalTile - 1) / kFocalTile;
-  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
   for (int q = 0; q < f->planes; ++q) a.shift[q] = f->shift[q];
+  return a;
+}
+
+int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
+                    double* field, void* stream) {
+  if (!f) return fail(ART_ERR_BAD_ARG, "focal descriptor is NULL");
+  if (const int e = focal_desc_check(f)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t pixels = (int64_t)f->planes * f->ny * f->nx;
+  bool done;
+  if (const int e = focal_call_check(b, n, scratch, field, pixels, s, &done); e || done) return e;
+  const int S = focal_slices(f->nx, f->ny, f->planes, n);
+  const FocalArg a = focal_arg(f, n, S);
+  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
   per_launch(n, [&](const int64_t off, const int64_t m) {
     hipLaunchKernelGGL(k_focal_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off), w ? w + off : nullptr,
                        m, scratch + off);
@@ -2973,6 +3119,55 @@ int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double*
                        (const double2*)part, S, pixels, reinterpret_cast<double2*>(field));
   }
   return launched("art_focal_field launch");
+}
+
+// the checks an ArtFocalSpectrumDesc adds to focal_desc_check
+static int focal_spectrum_check(const ArtFocalSpectrumDesc* d) {
+  if (d->nk < 1 || d->nk > ART_FOCAL_MAX_WAVENUMBERS) return fail(ART_ERR_BAD_ARG, "focal spectrum: nk must be in [1, 1024]");
+  if (!isfinite(d->dk)) return fail(ART_ERR_BAD_ARG, "focal spectrum: dk must be finite");
+  const double k_last = focal_kj(d->f.k, d->nk - 1, d->dk);   // k_j is linear in j: its ends bound it
+  if (!(isfinite(k_last) && k_last > 0.0)) return fail(ART_ERR_BAD_ARG, "focal spectrum: every k_j must be finite and > 0");
+  if ((int64_t)d->f.planes * d->nk > 65535) return fail(ART_ERR_BAD_ARG, "focal spectrum: planes * nk must be <= 65535");
+  return ART_OK;
+}
+
+int64_t art_focal_spectrum_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int32_t nk, int64_t n) {
+  if (nx < 1 || ny < 1 || nx > ART_FOCAL_MAX_PIXELS || ny > ART_FOCAL_MAX_PIXELS || planes < 1 ||
+      planes > ART_FOCAL_MAX_PLANES || nk < 1 || nk > ART_FOCAL_MAX_WAVENUMBERS || n < 0)
+    return fail(ART_ERR_BAD_ARG, "focal spectrum scratch: nx, ny in [1, 2048], planes in [1, 64], nk in [1, 1024], n >= 0");
+  const int S = focal_slices(nx, ny, planes * nk, n);
+  return (int64_t)kFocalSpecRows * focal_stride(n) + (S > 1 ? (int64_t)S * planes * nk * ny * nx * 2 : 0);
+}
+
+int art_focal_spectrum(const ArtFocalSpectrumDesc* d, const ArtBundleView* b, const double* w, int64_t n,
+                       double* scratch, double* field, void* stream) {
+  if (!d) return fail(ART_ERR_BAD_ARG, "focal spectrum descriptor is NULL");
+  const ArtFocalDesc* f = &d->f;
+  if (const int e = focal_desc_check(f)) return e;
+  if (const int e = focal_spectrum_check(d)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  const int planes = f->planes * d->nk;      // (plane, wavenumber) pairs
+  const int64_t pixels = (int64_t)planes * f->ny * f->nx;
+  bool done;
+  if (const int e = focal_call_check(b, n, scratch, field, pixels, s, &done); e || done) return e;
+  // the slices of art_focal_field at nk = 1: the same partial sums, so the same bytes
+  const int S = focal_slices(f->nx, f->ny, planes, n);
+  const FocalArg a = focal_arg(f, n, S);
+  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
+  per_launch(n, [&](const int64_t off, const int64_t m) {
+    hipLaunchKernelGGL(k_focal_spectrum_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off),
+                       w ? w + off : nullptr, m, scratch + off);
+    return ART_OK;
+  });
+  double* part = S > 1 ? scratch + (int64_t)kFocalSpecRows * a.stride : field;
+  hipLaunchKernelGGL(k_focal_spectrum_field, dim3(tiles, planes, S), dim3(kBlock), 0, s, a, d->dk, (int)d->nk,
+                     (const double*)scratch, part);
+  if (S > 1) {
+    const int64_t want = (pixels + kBlock - 1) / kBlock;
+    hipLaunchKernelGGL(k_focal_fold, dim3((int)(want > kMaxBlocks ? kMaxBlocks : want)), dim3(kBlock), 0, s,
+                       (const double2*)part, S, pixels, reinterpret_cast<double2*>(field));
+  }
+  return launched("art_focal_spectrum launch");
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }

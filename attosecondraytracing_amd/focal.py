@@ -103,13 +103,9 @@ def amplitude_sum(B):
     return float(torch.where(alive, torch.sqrt(torch.where(alive, B.intensity, 0.0)), 0.0).sum())
 
 
-def focal_field(det, RayList, Size=None, Pixels=128, Centre=None, Shifts=None, Wavelength=None, RefPath=None):
-    """Detector.get_FocalField (see the module's docstring).  Pixel centres: Centre + linspace(-Size/2, Size/2, Pixels)
-    per axis (Size, Pixels scalars or one per axis); Centre defaults to the alive rays' bounding-box centre
-    (get_PointList2DCentre's), Size to 16 Airy radii (ReturnAiryRadius(wavelength, ReturnNumericalAperture)), Shifts to
-    (0,), Wavelength to the bundle's, RefPath to the mean optical path of the alive rays (what get_Delays subtracts).
-    All planes are summed in one device call."""
-    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+def focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath):
+    """get_FocalField's arguments resolved for bundle B on det (see focal_field): (ArtFocalDesc, x, y, shifts, wavelength,
+    ref_path, stats), stats the lite read-out's statistics."""
     wavelength = B.wavelength if Wavelength is None else float(Wavelength)
     s = det.readout(B, store=False, lite=True)["stats"]
     alive = s[0] > 0
@@ -128,5 +124,16 @@ def focal_field(det, RayList, Size=None, Pixels=128, Centre=None, Shifts=None, W
     fd.planes = len(shifts)
     for q, v in enumerate(shifts):
         fd.shift[q] = -v          # shiftByDistance(v) moves the plane to centre - v * normal
+    return fd, x, y, shifts, wavelength, ref, s
+
+
+def focal_field(det, RayList, Size=None, Pixels=128, Centre=None, Shifts=None, Wavelength=None, RefPath=None):
+    """Detector.get_FocalField (see the module's docstring).  Pixel centres: Centre + linspace(-Size/2, Size/2, Pixels)
+    per axis (Size, Pixels scalars or one per axis); Centre defaults to the alive rays' bounding-box centre
+    (get_PointList2DCentre's), Size to 16 Airy radii (ReturnAiryRadius(wavelength, ReturnNumericalAperture)), Shifts to
+    (0,), Wavelength to the bundle's, RefPath to the mean optical path of the alive rays (what get_Delays subtracts).
+    All planes are summed in one device call."""
+    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+    fd, x, y, shifts, wavelength, ref, _ = focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
     field = B.backend.focal_field(fd, B.view(), B.intensity, B.n_slots)
     return FocalField(field, x, y, shifts, wavelength, ref, amplitude_sum(B))
