@@ -132,6 +132,20 @@ def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pix
     return _plots.PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size, Pixels)
 
 
+def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston", "tilt")):
+    """The fitted wavefront (Detector.get_Wavefront) on the pupil, in waves, with the terms in `Remove` taken out, and a
+    bar chart of the Zernike terms' rms contributions in waves."""
+    from . import _plots
+    return _plots.WavefrontMap(RayListAnalysed, Detector, Order, Pixels, Remove)
+
+
+def WavefrontScan(OpticalChainList, Detectors, Terms=((2, 0), (2, 1), (2, 2), (3, 1), (3, 2)), Order=8):
+    """Chosen Zernike terms (waves) and the rms at the best reference point against each chain's loop_variable_value,
+    for the last bundle of every chain on its detector, all chains in one device call."""
+    from . import _plots
+    return _plots.WavefrontScan(OpticalChainList, Detectors, Terms, Order)
+
+
 def RayRenderGraph(OpticalChain, EndDistance=None, maxRays=300, OEpoints=3000, scale_spheres=5.0, draw_mesh=False,
                    cycle_ray_colors=False):
     """3-D picture of the optical setup and the traced rays (ART/ModuleAnalysisAndPlots.py:616-673)."""

@@ -249,3 +249,16 @@ class Detector:
         from . import pulse
         return pulse.focal_pulse(self, RayList, DeltaFT, Size, Pixels, Centre, Shifts, Wavelength, RefPath, Spectrum,
                                  TimeWindow, Times)
+
+    def get_Wavefront(self, RayList, Order=8, Centre=None, Shift=0.0, RefPath=None, PupilCentre=None, PupilRadius=None,
+                      Wavelength=None, PerRay=False):
+        """Wavefront error of ALL alive rays about a reference point, fitted with Zernike polynomials on the device
+        (wavefront.Wavefront): the point is pixel Centre (detector coordinates, default (0, 0)) of get_FocalField in the
+        plane this detector would occupy after shiftByDistance(Shift); pupil coordinates are the rays' direction
+        cosines about PupilCentre (default the detector axis) over PupilRadius (default: the largest); Order <= 10.
+        RefPath (the path of zero error) defaults to the mean optical path, Wavelength to the bundle's.  Gives the
+        coefficients in mm and waves, the rms before and after the fit, the best reference point and its rms, the
+        Marechal Strehl ratio; PerRay=True keeps the per-ray error and pupil coordinates on the device."""
+        from . import wavefront
+        return wavefront.wavefront(self, RayList, Order, Centre, Shift, RefPath, PupilCentre, PupilRadius, Wavelength,
+                                   PerRay)

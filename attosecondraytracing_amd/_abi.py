@@ -149,6 +149,29 @@ class ArtFocalSpectrumDesc(C.Structure):
     ]
 
 
+ART_WAVEFRONT_MAX_ORDER = 10
+ART_WAVEFRONT_MAX_COLS = 68
+ART_WAVEFRONT_DOUBLES = 2360
+
+
+class ArtWavefrontJob(C.Structure):
+    _fields_ = [
+        ("det", ArtDetectorDesc),
+        ("b", ArtBundleView),
+        ("w", C.c_void_p),
+        ("n", C.c_int64),
+        ("ref", C.c_double * 3),
+        ("L_ref", C.c_double),
+        ("pupil", C.c_double * 3),
+        ("order", C.c_int32),
+        ("reserved", C.c_int32),
+        ("opd", C.c_void_p),
+        ("pupil_x", C.c_void_p),
+        ("pupil_y", C.c_void_p),
+        ("out", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); the loader checks every symbol exists (tests/test_abi.py does too)
 PROTOTYPES = {
     "art_abi_version": (C.c_int, []),
@@ -183,6 +206,8 @@ PROTOTYPES = {
     "art_focal_spectrum_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "art_focal_spectrum": (C.c_int, [C.POINTER(ArtFocalSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "art_wavefront_scratch_doubles": (C.c_int64, [C.POINTER(ArtWavefrontJob), C.c_int32]),
+    "art_wavefront": (C.c_int, [C.c_void_p, C.POINTER(ArtWavefrontJob), C.c_int32, C.c_void_p, C.c_void_p]),
     "art_reduce_scratch_doubles": (C.c_int64, []),
     "art_detector_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -465,11 +465,8 @@ class HipBackend:
             self.check(self.fn["art_trace_guides"](darr, m, rays.data_ptr() + 64 * k0, alive.data_ptr() + k0, sp),
                        "art_trace_guides")
 
-    def analyse_bundles(self, jobs, n):
-        """art_analyse_bundles for a list of ArtAnalysisJob (host structs): uploads the job table, enqueues the four
-        launches and returns the DEVICE tensor out[len(jobs), 64] -- nothing is read back here."""
-        c = len(jobs)
-        arr = (_abi.ArtAnalysisJob * c)(*jobs)
+    def _upload_table(self, arr):
+        """A DEVICE copy of the ctypes job table `arr`, enqueued on the current stream."""
         nb = C.sizeof(arr)
         # pinned staging + device table from a per-size pool (pinning host memory costs milliseconds): the pinned image is
         # rewritten only after its previous upload has completed, the device table is read by launches enqueued before
@@ -486,6 +483,30 @@ class HipBackend:
         dev.copy_(host, non_blocking=True)
         pair[2] = torch.cuda.Event()
         pair[2].record()
+        return dev
+
+    def wavefront(self, jobs):
+        """art_wavefront for a list of ArtWavefrontJob (host structs; their `out` is set here): uploads the job table,
+        enqueues the three launches and returns the DEVICE tensor out[len(jobs), ART_WAVEFRONT_DOUBLES]."""
+        c = len(jobs)
+        out = torch.empty((c, _abi.ART_WAVEFRONT_DOUBLES), dtype=torch.float64, device=self.device)
+        for k, j in enumerate(jobs):
+            j.out = out.data_ptr() + 8 * _abi.ART_WAVEFRONT_DOUBLES * k
+        arr = (_abi.ArtWavefrontJob * c)(*jobs)
+        ns = self.fn["art_wavefront_scratch_doubles"](arr, c)
+        if ns < 0:
+            raise ArtError(f"art_wavefront_scratch_doubles failed with code {ns}: {self.last_error()}")
+        dev = self._upload_table(arr)
+        scratch = self.scratch("wavefront", ns, torch.float64)
+        self.check(self.fn["art_wavefront"](dev.data_ptr(), arr, c, scratch.data_ptr(), self.stream_ptr()), "art_wavefront")
+        return out
+
+    def analyse_bundles(self, jobs, n):
+        """art_analyse_bundles for a list of ArtAnalysisJob (host structs): uploads the job table, enqueues the four
+        launches and returns the DEVICE tensor out[len(jobs), 64] -- nothing is read back here."""
+        c = len(jobs)
+        arr = (_abi.ArtAnalysisJob * c)(*jobs)
+        dev = self._upload_table(arr)
         out = torch.empty((c, _abi.ART_ANALYSIS_DOUBLES), dtype=torch.float64, device=self.device)
         # (jobs that bring their sums along need no per-tile partials, but the area is sized for the general case)
         scratch = self.scratch("analysis", self.fn["art_analysis_scratch_doubles"](c, int(n)), torch.float64)

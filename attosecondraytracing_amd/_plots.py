@@ -480,6 +480,67 @@ def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pix
     return fig
 
 
+def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston", "tilt")):
+    """The fitted wavefront on the unit pupil in waves (Detector.get_Wavefront, `Remove`d terms taken out) beside a bar
+    chart of every term's rms contribution in waves; rms, rms at the best reference point and the Marechal Strehl ratio
+    in the title.  Without a wavelength the numbers are in nm."""
+    plt = _plt()
+    B = _as_bundle(RayListAnalysed)
+    wf = Detector.get_Wavefront(B, Order=Order)
+    scale, unit = (1.0 / wf.wavelength, "waves") if np.isfinite(wf.wavelength) else (1e6, "nm")
+    img = wf.map(Pixels, remove=Remove) * scale
+    plt.ion()
+    fig, (a1, a2) = plt.subplots(1, 2, figsize=(12, 5))
+    im = a1.imshow(img, origin="lower", extent=(-1, 1, -1, 1), aspect="equal", interpolation="nearest")
+    fig.colorbar(im, ax=a1).set_label(f"W ({unit})")
+    a1.set_xlabel("pupil x")
+    a1.set_ylabel("pupil y")
+    a1.set_title("Wavefront, {:.3f} mm, without {}".format(Detector.get_distance(), ", ".join(Remove) or "nothing"))
+    keys = [k for k in wf.coefficients if k != (0, 0)]
+    a2.bar(range(len(keys)), [wf.term_rms[k] * scale for k in keys])
+    a2.set_xticks(range(len(keys)))
+    a2.set_xticklabels([f"{n},{m}" for n, m in keys], rotation=90, fontsize=7)
+    a2.set_xlabel("Zernike term (n, m)")
+    a2.set_ylabel(f"rms on the pupil ({unit})")
+    a2.set_title("rms {:.3g}, best focus {:.3g} {}, Strehl (Marechal) {:.3f}".format(
+        wf.rms * scale, wf.rms_best * scale, unit, wf.strehl_marechal))
+    fig._art_wavefront = wf
+    plt.show()
+    return fig
+
+
+def WavefrontScan(OpticalChainList, Detectors, Terms=((2, 0), (2, 1), (2, 2), (3, 1), (3, 2)), Order=8):
+    """Chosen Zernike terms and the rms at the best reference point (waves, or nm without a wavelength) against each
+    chain's loop_variable_value (its index if it has none), for the last bundle of every chain on its detector
+    (`Detectors`: one for all chains, or one per chain); all bundles in one device call (wavefront.wavefronts)."""
+    from . import wavefront
+    plt = _plt()
+    chains = list(OpticalChainList)
+    dets = list(Detectors) if isinstance(Detectors, (list, tuple)) else [Detectors] * len(chains)
+    if len(dets) != len(chains):
+        raise ValueError("Detectors: one detector, or one per chain")
+    wfs = wavefront.wavefronts([(c.get_output_rays()[-1], d, {"Order": Order}) for c, d in zip(chains, dets)])
+    xs = [c.loop_variable_value if c.loop_variable_value is not None else k for k, c in enumerate(chains)]
+    name = chains[0].loop_variable_name if chains and chains[0].loop_variable_name else "chain"
+    wl = wfs[0].wavelength if wfs else float("nan")
+    scale, unit = (1.0 / wl, "waves") if np.isfinite(wl) else (1e6, "nm")
+    plt.ion()
+    fig, (a1, a2) = plt.subplots(2, 1, sharex=True)
+    for key in Terms:
+        a1.plot(xs, [w.coefficients.get(tuple(key), np.nan) * scale for w in wfs], "o-", label="Z{},{}".format(*key))
+    a1.set_ylabel(f"coefficient ({unit})")
+    a1.legend(loc="upper right", fontsize=8)
+    a1.set_title("Wavefront terms against " + str(name))
+    a2.plot(xs, [w.rms_best * scale for w in wfs], "o-", label="rms at best focus")
+    a2.plot(xs, [w.rms * scale for w in wfs], "s--", label="rms at the detector centre")
+    a2.set_ylabel(f"rms ({unit})")
+    a2.set_xlabel(str(name))
+    a2.legend(loc="upper right")
+    fig._art_wavefronts = wfs
+    plt.show()
+    return fig
+
+
 def MirrorFootprint(OpticalChain, ReflectionNumber: int, Bins=200):
     """Image of the footprint of ALL rays on one optical element (OpticalChain.get_Footprint) over its support
     outline."""

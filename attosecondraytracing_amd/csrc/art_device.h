@@ -412,6 +412,40 @@ ART_HD void zernike_recurrence(const double* tab, double px, double py, bool wan
   gY = sy * iR;
 }
 
+// Every Zernike polynomial of orders 0..N at (x, y) -- the values of zernike_recurrence's rows, no gradients -- handed
+// to put(j, Z_j) in table order j = n (n + 1) / 2 + m (the wavefront fit, art_wavefront).  N is a template parameter and
+// every loop unrolls, so the three rows live in registers under compile-time indices: no per-lane arrays in memory.
+template <int N, typename F>
+ART_HD void zernike_values(const double x, const double y, F&& put) {
+  double Zd[N + 2], Zb[N + 2], Za[N + 2];     // rows n - 2, n - 1, n
+  put(0, 1.0);
+  Zd[0] = 1.0;
+  if (N >= 1) {
+    Zb[0] = y; Zb[1] = x;
+    put(1, y);
+    put(2, x);
+  }
+#pragma unroll
+  for (int n = 2; n <= N; ++n) {
+#pragma unroll
+    for (int m = 0; m <= n; ++m) {
+      double z;
+      if (m == 0) z = x * Zb[0] + y * Zb[n - 1];
+      else if (m == n) z = x * Zb[n - 1] - y * Zb[0];
+      else if ((n & 1) && 2 * m == n - 1) z = y * Zb[n - 1 - m] + x * Zb[m - 1] - y * Zb[n - m] - Zd[m - 1];
+      else if ((n & 1) && 2 * m == n + 1) z = x * Zb[m] + y * Zb[n - 1 - m] + x * Zb[m - 1] - Zd[m - 1];
+      else if (!(n & 1) && 2 * m == n) z = 2.0 * x * Zb[m] + 2.0 * y * Zb[m - 1] - Zd[m - 1];
+      else z = x * Zb[m] + y * Zb[n - 1 - m] + x * Zb[m - 1] - y * Zb[n - m] - Zd[m - 1];
+      Za[m] = z;
+      put(n * (n + 1) / 2 + m, z);
+    }
+#pragma unroll
+    for (int m = 0; m < n; ++m) Zd[m] = Zb[m];
+#pragma unroll
+    for (int m = 0; m <= n; ++m) Zb[m] = Za[m];
+  }
+}
+
 // Gridded height map: bilinear lookup (ART/ModuleDefects.py:131-137; SciPy RegularGridInterpolator, linear)
 ART_HD double grid_offset(const ArtGridDefect& g, double px, double py) {
   // Cell coordinates clamped to the grid BEFORE the integer conversion (a NaN or huge coordinate must not reach the

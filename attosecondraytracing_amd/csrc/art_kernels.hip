@@ -1808,6 +1808,299 @@ __global__ __launch_bounds__(kBlock) void k_focal_spectrum_field(const FocalArg 
     }
 }
 
+// ------------------------------------------------------------------------------------------- wavefront
+// art_wavefront: per job the Gram matrix G = sum_r w_r v_r v_r^T of the rows v_r = [Z_0 .. Z_{J-1}, d.n, W_r]
+// (include/art_hip.h); the Zernike fit and the best reference point are small dense algebra on G, done by the caller.
+// k_wavefront_prep: one pass per job over its slots into kWfRows rows of scratch (w, W, d.e1 - a1, d.e2 - a2, d.n; a
+// slot that is not alive gets W = NaN and zeros elsewhere) and, per workgroup, the largest (d.e1 - a1)^2 + (d.e2 - a2)^2
+// of its alive rays (the default pupil radius).  k_wavefront_gram<N>: grid = (ray slices, jobs of order N).  Per chunk
+// of kWfChunk rays, kWfStage lanes of every wave stage one ray each -- pupil coordinates, all J polynomials by the
+// recurrences (zernike_values), the K columns into LDS once scaled by w and once not -- then the lanes own 4 x 4 blocks
+// of the K x K upper triangle (K padded to KP = 4 B) and accumulate them with fp64 FMAs, in kBlock / (B (B + 1) / 2)
+// lane groups that take turns over the chunk's rays.  At the end of its slice a workgroup adds the groups' blocks in
+// group order and writes the packed triangle and the slice's statistics.  k_wavefront_fold adds the slices of every job
+// in slice order.  No float atomics; a job's slicing depends on its own n: the same bytes whichever jobs share the call.
+constexpr int kWfRows = 5;
+constexpr int kWfChunk = 64;          // rays per LDS stage
+constexpr int kWfStage = 16;          // staging lanes per wave: the staging work is spread over the four SIMDs
+constexpr int kWfPrepBlocks = 1024;   // workgroups per job of the prep at most (one radius partial each)
+constexpr int kWfMaxSlices = 512;     // two workgroups per CU for one large job
+constexpr int kWfStats = 8;           // per slice behind the triangle: used, outside, sum w, rho, min W, max W, 0, 0
+static_assert(kWfStage * (kBlock / 64) == kWfChunk, "one staged ray per staging lane");
+
+__host__ __device__ inline int wf_cols(const int order) { return (order + 1) * (order + 2) / 2 + 2; }
+__host__ __device__ inline int64_t wf_stride(const int64_t n) { return (n + 63) / 64 * 64; }
+// slices of a job: at least 4 chunks of rays each, kWfMaxSlices at most; whole chunks per slice
+__host__ __device__ inline int wf_slices(const int64_t n) {
+  const int64_t s = (n + 4 * kWfChunk - 1) / (4 * kWfChunk);
+  return s < 1 ? 1 : (s > kWfMaxSlices ? kWfMaxSlices : (int)s);
+}
+__host__ __device__ inline int64_t wf_per_slice(const int64_t n, const int slices) {
+  const int64_t p = (n + slices - 1) / slices;
+  return p < 1 ? kWfChunk : (p + kWfChunk - 1) / kWfChunk * kWfChunk;
+}
+inline int64_t wf_per_job(const int64_t nmax, const int kmax) {
+  return kWfRows * wf_stride(nmax) + kWfPrepBlocks + (int64_t)wf_slices(nmax) * (kmax * (kmax + 1) / 2 + kWfStats);
+}
+
+struct WfArg {
+  int64_t per_job;      // scratch doubles per job: rows (kWfRows x stride), radius partials, slice partials
+  int64_t stride;       // row stride of the prep rows
+  int32_t prep_blocks;  // workgroups per job of the prep
+  int32_t job0;         // first job of a gram launch
+};
+
+template <int N>
+struct WfShape {
+  static constexpr int J = (N + 1) * (N + 2) / 2, K = J + 2, T = K * (K + 1) / 2;
+  static constexpr int KP = (K + 3) / 4 * 4, B = KP / 4, NB = B * (B + 1) / 2;
+  static constexpr int G = kBlock / NB;            // lane groups
+  static constexpr int HALF = KP / 2;              // doubles per ray in each half of a stage
+  static constexpr int STAGE = 4 * kWfChunk * HALF;
+  static constexpr int LDS = STAGE > G * NB * 16 ? STAGE : G * NB * 16;
+  static_assert(G >= 1, "at most kBlock blocks");
+};
+
+__global__ __launch_bounds__(kBlock) void k_wavefront_prep(const ArtWavefrontJob* __restrict__ jobs, const WfArg a,
+                                                           double* scratch) {
+#pragma clang fp contract(off)
+  __shared__ double red[kBlock];
+  const ArtWavefrontJob& jb = jobs[blockIdx.y];
+  const int t = threadIdx.x;
+  const int64_t n = jb.n, st = a.stride;
+  double* rows = scratch + (int64_t)blockIdx.y * a.per_job;
+  const double* C = jb.det.centre;
+  const double* e1 = jb.det.rot;
+  const double* e2 = jb.det.rot + 3;
+  const double* nr = jb.det.normal;
+  const double R0 = ((C[0] + jb.ref[0] * e1[0]) + jb.ref[1] * e2[0]) - jb.ref[2] * nr[0];
+  const double R1 = ((C[1] + jb.ref[0] * e1[1]) + jb.ref[1] * e2[1]) - jb.ref[2] * nr[1];
+  const double R2 = ((C[2] + jb.ref[0] * e1[2]) + jb.ref[1] * e2[2]) - jb.ref[2] * nr[2];
+  const double a1 = jb.pupil[0], a2 = jb.pupil[1], L = jb.L_ref;
+  double m2 = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + t; i < n; i += (int64_t)gridDim.x * kBlock) {
+    const bool live = jb.b.alive[i] != 0;
+    const double px = jb.b.ox[i], py = jb.b.oy[i], pz = jb.b.oz[i], dx = jb.b.dx[i], dy = jb.b.dy[i], dz = jb.b.dz[i];
+    // a dead slot's values are unspecified (possibly NaN): selected away
+    const double W = (jb.b.path[i] - L) + ((dx * (R0 - px) + dy * (R1 - py)) + dz * (R2 - pz));
+    const double xr = ((dx * e1[0] + dy * e1[1]) + dz * e1[2]) - a1;
+    const double yr = ((dx * e2[0] + dy * e2[1]) + dz * e2[2]) - a2;
+    const double dn = (dx * nr[0] + dy * nr[1]) + dz * nr[2];
+    rows[i] = live ? (jb.w ? jb.w[i] : 1.0) : 0.0;
+    rows[st + i] = live ? W : NAN;
+    rows[2 * st + i] = live ? xr : 0.0;
+    rows[3 * st + i] = live ? yr : 0.0;
+    rows[4 * st + i] = live ? dn : 0.0;
+    if (live) m2 = fmax(m2, xr * xr + yr * yr);
+  }
+  red[t] = m2;
+  __syncthreads();
+  for (int h = kBlock / 2; h > 0; h >>= 1) {
+    if (t < h) red[t] = fmax(red[t], red[t + h]);
+    __syncthreads();
+  }
+  if (t == 0) rows[kWfRows * st + blockIdx.x] = red[0];
+}
+
+template <int N>
+__global__ __launch_bounds__(kBlock) void k_wavefront_gram(const ArtWavefrontJob* __restrict__ jobs, const WfArg a,
+                                                           double* scratch) {
+#pragma clang fp contract(off)
+  using S = WfShape<N>;
+  __shared__ __attribute__((aligned(16))) double lds[S::LDS];
+  __shared__ double red[kBlock];
+  const int j = a.job0 + (int)blockIdx.y, slice = blockIdx.x, t = threadIdx.x;
+  const ArtWavefrontJob& jb = jobs[j];
+  const int64_t n = jb.n, st = a.stride;
+  const int nslices = wf_slices(n);
+  if (slice >= nslices) return;                         // (the launch covers the largest job of the run)
+  const double* rows = scratch + (int64_t)j * a.per_job;
+  double* part = scratch + (int64_t)j * a.per_job + kWfRows * st + kWfPrepBlocks + (int64_t)slice * (S::T + kWfStats);
+  // the pupil radius: given, or the largest transverse distance over the prep's partials (a max: any order)
+  double rho = jb.pupil[2];
+  const bool given = rho > 0.0;
+  if (!given) {
+    double m = 0.0;
+    for (int p = t; p < a.prep_blocks; p += kBlock) m = fmax(m, rows[kWfRows * st + p]);
+    red[t] = m;
+    __syncthreads();
+    for (int h = kBlock / 2; h > 0; h >>= 1) {
+      if (t < h) red[t] = fmax(red[t], red[t + h]);
+      __syncthreads();
+    }
+    rho = red[0] > 0.0 ? sqrt(red[0]) : 1.0;
+    __syncthreads();
+  }
+  const int64_t per = wf_per_slice(n, nslices), r0 = (int64_t)slice * per;
+  const int64_t r1 = (r0 + per < n) ? r0 + per : n;
+  // staging role: ray sr of the chunk
+  const bool stager = (t & 63) < kWfStage;
+  const int sr = (t >> 6) * kWfStage + (t & 63);
+  // accumulating role: group g, block (bi, bj) of the upper triangle of blocks
+  const int g = t / S::NB, blk = t % S::NB;
+  const bool worker = g < S::G;
+  int bi = 0, q = blk;
+  while (q >= S::B - bi) { q -= S::B - bi; ++bi; }
+  const int bj = bi + q;
+  double* sA = lds;                          // w v, halves [2][kWfChunk][HALF]: columns 4b + {0, 1} | 4b + {2, 3}
+  double* sB = lds + 2 * kWfChunk * S::HALF; // v
+  double acc[4][4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int v = 0; v < 4; ++v) acc[u][v] = 0.0;
+  double used_n = 0.0, out_n = 0.0, wmin = INFINITY, wmax = -INFINITY;
+
+  for (int64_t c0 = r0; c0 < r1; c0 += kWfChunk) {
+    if (stager) {
+      const int64_t r = c0 + sr;
+      double w = 0.0, W = 0.0, x = 0.0, y = 0.0, dn = 0.0;
+      bool used = false;
+      if (r < r1) {
+        W = rows[st + r];
+        if (W == W) {                                   // alive
+          x = rows[2 * st + r] / rho;
+          y = rows[3 * st + r] / rho;
+          used = !given || x * x + y * y <= 1.0;
+          if (used) {
+            w = rows[r];
+            dn = rows[4 * st + r];
+            used_n += 1.0;
+            wmin = fmin(wmin, W);
+            wmax = fmax(wmax, W);
+          } else {
+            out_n += 1.0;
+          }
+        }
+        if (jb.opd) jb.opd[r] = used ? W : NAN;
+        if (jb.pupil_x) jb.pupil_x[r] = used ? x : NAN;
+        if (jb.pupil_y) jb.pupil_y[r] = used ? y : NAN;
+      }
+      if (!used) x = y = 0.0;
+      auto put = [&](const int col, const double z) {
+        const double v = used ? z : 0.0;
+        const int off = (((col >> 1) & 1) * kWfChunk + sr) * S::HALF + (col >> 2) * 2 + (col & 1);
+        sB[off] = v;
+        sA[off] = w * v;
+      };
+      art::zernike_values<N>(x, y, put);
+      put(S::J, dn);
+      put(S::J + 1, W);
+#pragma unroll
+      for (int col = S::K; col < S::KP; ++col) put(col, 0.0);
+    }
+    __syncthreads();
+    if (worker) {
+#pragma unroll 2
+      for (int rr = g; rr < kWfChunk; rr += S::G) {
+        const double2 a0 = *reinterpret_cast<const double2*>(sA + rr * S::HALF + 2 * bi);
+        const double2 a1 = *reinterpret_cast<const double2*>(sA + (kWfChunk + rr) * S::HALF + 2 * bi);
+        const double2 b0 = *reinterpret_cast<const double2*>(sB + rr * S::HALF + 2 * bj);
+        const double2 b1 = *reinterpret_cast<const double2*>(sB + (kWfChunk + rr) * S::HALF + 2 * bj);
+        const double av[4] = {a0.x, a0.y, a1.x, a1.y}, bv[4] = {b0.x, b0.y, b1.x, b1.y};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int v = 0; v < 4; ++v) acc[u][v] = fma(av[u], bv[v], acc[u][v]);
+      }
+    }
+    __syncthreads();
+  }
+  // the groups' blocks, added in group order; the stagers' statistics in lane order
+  if (worker) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) lds[(g * S::NB + blk) * 16 + u * 4 + v] = acc[u][v];
+  }
+  if (stager) {
+    red[sr] = used_n;
+    red[kWfChunk + sr] = out_n;
+    red[2 * kWfChunk + sr] = wmin;
+    red[3 * kWfChunk + sr] = wmax;
+  }
+  __syncthreads();
+  for (int e = t; e < S::NB * 16; e += kBlock) {
+    const int bb = e >> 4, k = e & 15;
+    int i0 = 0, qq = bb;
+    while (qq >= S::B - i0) { qq -= S::B - i0; ++i0; }
+    const int i = 4 * i0 + (k >> 2), jj = 4 * (i0 + qq) + (k & 3);
+    if (i <= jj && jj < S::K) {
+      double s = 0.0;
+      for (int gg = 0; gg < S::G; ++gg) s += lds[(gg * S::NB + bb) * 16 + k];
+      part[i * (2 * S::K - i - 1) / 2 + jj] = s;
+      if (e == 0) part[S::T + 2] = s;                 // sum w = G[0][0] (Z_0 = 1)
+    }
+  }
+  if (t == 0) {
+    double c = 0.0, o = 0.0, lo = INFINITY, hi = -INFINITY;
+    for (int l = 0; l < kWfChunk; ++l) {
+      c += red[l];
+      o += red[kWfChunk + l];
+      lo = fmin(lo, red[2 * kWfChunk + l]);
+      hi = fmax(hi, red[3 * kWfChunk + l]);
+    }
+    part[S::T] = c;
+    part[S::T + 1] = o;
+    part[S::T + 3] = rho;
+    part[S::T + 4] = lo;
+    part[S::T + 5] = hi;
+    part[S::T + 6] = 0.0;
+    part[S::T + 7] = 0.0;
+  }
+}
+
+// out = [used, outside, sum w, rho, min W, max W, K, 0, G packed, zeros]: every job's slices added in slice order (the
+// loads of a thread are independent, so they are unrolled ahead of its additions: the fold is latency-bound otherwise)
+__global__ __launch_bounds__(kBlock) void k_wavefront_fold(const ArtWavefrontJob* __restrict__ jobs, const WfArg a,
+                                                           const double* scratch) {
+  const int j = blockIdx.y;
+  const ArtWavefrontJob& jb = jobs[j];
+  const int K = wf_cols(jb.order), T = K * (K + 1) / 2, S = wf_slices(jb.n);
+  const int64_t ps = T + kWfStats;
+  const double* part = scratch + (int64_t)j * a.per_job + kWfRows * a.stride + kWfPrepBlocks;
+  for (int e = blockIdx.x * kBlock + threadIdx.x; e < ART_WAVEFRONT_DOUBLES; e += gridDim.x * kBlock) {
+    double v = 0.0;
+    if (e >= 8 && e < 8 + T) {
+#pragma unroll 16
+      for (int s = 0; s < S; ++s) v += part[s * ps + (e - 8)];
+    } else if (e < 6) {
+      double used = 0.0;
+#pragma unroll 16
+      for (int s = 0; s < S; ++s) used += part[s * ps + T];
+      if (e == 0) {
+        v = used;
+      } else if (e == 3) {
+        v = part[T + 3];
+      } else if (e == 4) {
+        v = INFINITY;
+#pragma unroll 16
+        for (int s = 0; s < S; ++s) v = fmin(v, part[s * ps + T + 4]);
+      } else if (e == 5) {
+        v = -INFINITY;
+#pragma unroll 16
+        for (int s = 0; s < S; ++s) v = fmax(v, part[s * ps + T + 5]);
+      } else {
+#pragma unroll 16
+        for (int s = 0; s < S; ++s) v += part[s * ps + T + e];
+      }
+      if (used == 0.0 && e >= 2) v = 0.0;
+    } else if (e == 6) {
+      v = (double)K;
+    }
+    jb.out[e] = v;
+  }
+}
+
+template <int N>
+void launch_wf_gram(const dim3 grid, hipStream_t s, const ArtWavefrontJob* jobs, const WfArg a, double* scratch) {
+  hipLaunchKernelGGL(k_wavefront_gram<N>, grid, dim3(kBlock), 0, s, jobs, a, scratch);
+}
+using WfGramLaunch = void (*)(dim3, hipStream_t, const ArtWavefrontJob*, WfArg, double*);
+constexpr WfGramLaunch kWfGram[ART_WAVEFRONT_MAX_ORDER + 1] = {
+    launch_wf_gram<0>, launch_wf_gram<1>, launch_wf_gram<2>, launch_wf_gram<3>, launch_wf_gram<4>, launch_wf_gram<5>,
+    launch_wf_gram<6>, launch_wf_gram<7>, launch_wf_gram<8>, launch_wf_gram<9>, launch_wf_gram<10>};
+
 template <bool HAS_W>
 __global__ __launch_bounds__(kBlock) void k_moments_partial(const uint8_t* alive, const double* X, const double* Y,
                                                             const double* opl, const double* w, const int64_t n,
@@ -3168,6 +3461,69 @@ int art_focal_spectrum(const ArtFocalSpectrumDesc* d, const ArtBundleView* b, co
                        (const double2*)part, S, pixels, reinterpret_cast<double2*>(field));
   }
   return launched("art_focal_spectrum launch");
+}
+
+// validates a job table; *nmax, *kmax: the largest slot count and column count
+static int wf_check(const ArtWavefrontJob* jobs, int32_t n_jobs, int64_t* nmax, int* kmax) {
+  if (!jobs) return fail(ART_ERR_BAD_ARG, "wavefront job table is NULL");
+  if (n_jobs < 1 || n_jobs > 65535) return fail(ART_ERR_BAD_ARG, "n_jobs must be in 1..65535");
+  *nmax = 0;
+  *kmax = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const ArtWavefrontJob& jb = jobs[j];
+    if (jb.n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+    if (jb.n > kMaxRaysPerLaunchHw) return fail(ART_ERR_UNSUPPORTED, "more than 2^28 rays per bundle in one wavefront call");
+    if (jb.order < 0 || jb.order > ART_WAVEFRONT_MAX_ORDER) return fail(ART_ERR_BAD_ARG, "wavefront order must be in [0, 10]");
+    *nmax = jb.n > *nmax ? jb.n : *nmax;
+    *kmax = wf_cols(jb.order) > *kmax ? wf_cols(jb.order) : *kmax;
+  }
+  return ART_OK;
+}
+
+int64_t art_wavefront_scratch_doubles(const ArtWavefrontJob* jobs_host, int32_t n_jobs) {
+  int64_t nmax;
+  int kmax;
+  const int rc = wf_check(jobs_host, n_jobs, &nmax, &kmax);
+  return rc ? rc : (int64_t)n_jobs * wf_per_job(nmax, kmax);
+}
+
+int art_wavefront(const ArtWavefrontJob* jobs_dev, const ArtWavefrontJob* jobs_host, int32_t n_jobs, double* scratch,
+                  void* stream) {
+  if (!jobs_dev || !scratch) return fail(ART_ERR_BAD_ARG, "NULL argument");
+  int64_t nmax;
+  int kmax;
+  const int rc = wf_check(jobs_host, n_jobs, &nmax, &kmax);
+  if (rc) return rc;
+  for (int j = 0; j < n_jobs; ++j) {
+    const ArtWavefrontJob& jb = jobs_host[j];
+    if (!jb.out) return fail(ART_ERR_BAD_ARG, "a wavefront job's output row is NULL");
+    if (jb.n > 0 && !view_ok(&jb.b)) return fail(ART_ERR_BAD_ARG, "a job's bundle view has a NULL array");
+    bool finite = isfinite(jb.L_ref);
+    for (int c = 0; c < 3; ++c) finite = finite && isfinite(jb.ref[c]) && isfinite(jb.pupil[c]);
+    if (!finite) return fail(ART_ERR_BAD_ARG, "a wavefront job's reference point, L_ref or pupil is not finite");
+    if (jb.pupil[2] < 0.0) return fail(ART_ERR_BAD_ARG, "a wavefront job's pupil radius is negative");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  WfArg a;
+  a.stride = wf_stride(nmax);
+  a.per_job = wf_per_job(nmax, kmax);
+  const int64_t pb = (nmax + kBlock - 1) / kBlock;
+  a.prep_blocks = pb < 1 ? 1 : (pb > kWfPrepBlocks ? kWfPrepBlocks : (int)pb);
+  a.job0 = 0;
+  hipLaunchKernelGGL(k_wavefront_prep, dim3(a.prep_blocks, n_jobs), dim3(kBlock), 0, s, jobs_dev, a, scratch);
+  for (int j0 = 0; j0 < n_jobs;) {        // one launch per run of consecutive jobs of one order
+    const int order = jobs_host[j0].order;
+    int j1 = j0, slices = 1;
+    for (; j1 < n_jobs && jobs_host[j1].order == order; ++j1)
+      slices = wf_slices(jobs_host[j1].n) > slices ? wf_slices(jobs_host[j1].n) : slices;
+    a.job0 = j0;
+    kWfGram[order](dim3(slices, j1 - j0), s, jobs_dev, a, scratch);
+    j0 = j1;
+  }
+  a.job0 = 0;
+  hipLaunchKernelGGL(k_wavefront_fold, dim3((ART_WAVEFRONT_DOUBLES + kBlock - 1) / kBlock, n_jobs), dim3(kBlock), 0, s,
+                     jobs_dev, a, (const double*)scratch);
+  return launched("art_wavefront launch");
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }

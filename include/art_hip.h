@@ -356,6 +356,56 @@ int64_t art_focal_spectrum_scratch_doubles(int32_t nx, int32_t ny, int32_t plane
 int art_focal_spectrum(const ArtFocalSpectrumDesc* s, const ArtBundleView* b, const double* w, int64_t n,
                        double* scratch, double* field, void* stream);
 
+/* Wavefront aberrations of MANY bundles in one call (added under ABI 14: ArtWavefrontJob, art_wavefront,
+ * art_wavefront_scratch_doubles).  Per job, with C = det.centre, e1, e2 = rows 0, 1 of det.rot, n = det.normal (the
+ * frame of art_focal_field):
+ *   reference point  R = C + X e1 + Y e2 - s n       (ref = {X, Y, s}: pixel (X, Y) of art_focal_field in the plane
+ *                                                     of shift -s, i.e. Detector.shiftByDistance(s); formed on the
+ *                                                     device as ((C + X e1) + Y e2) - s n, unfused: ref = 0 gives C)
+ *   wavefront error  W_r = (path_r - L_ref) + ((d_x (R_x - p_x) + d_y (R_y - p_y)) + d_z (R_z - p_z))
+ *                    (k_focal_prep's order, no fma: k W_r is art_focal_field's phase of ray r at R, to rounding)
+ *   pupil            x_r = (d.e1 - a1) / rho,  y_r = (d.e2 - a2) / rho,   d.e = (d_x e_x + d_y e_y) + d_z e_z
+ *                    pupil = {a1, a2, rho}; rho = 0: the largest sqrt((d.e1 - a1)^2 + (d.e2 - a2)^2) over the alive
+ *                    rays, found on the device (1 if that is 0).  With an explicit rho a ray with x^2 + y^2 > 1 is not
+ *                    used and counted `outside`; with the computed one no ray is outside.
+ *   row              v_r = [Z_0 .. Z_{J-1}, d.n, W_r],  K = J + 2 columns, J = (N+1)(N+2)/2, N = order
+ *                    Z_j: the unnormalised Zernike polynomials of ART/recursive_zernike_generator.py (Andersen 2018)
+ *                    at (x_r, y_r), j = N'(N'+1)/2 + m for the key (N', m) (Z_0 = 1, Z_1 = y, Z_2 = x)
+ *   weights          w_r = w[r] (w = NULL: 1) for the USED rays (alive and not outside), 0 for every other slot
+ * out (DEVICE, ART_WAVEFRONT_DOUBLES doubles, written):
+ *   [0] rays used  [1] rays outside  [2] sum w  [3] rho used  [4] min W  [5] max W  (over the used rays)
+ *   [6] K  [7] 0  [8 + i K - i (i - 1) / 2 + (j - i)] = G[i][j] = sum_r w_r v_r[i] v_r[j]  for 0 <= i <= j < K
+ * A job with no used ray (n = 0, all slots dead, all outside) gets 0 in [0], [2..5] and G.  Per-ray outputs (optional,
+ * DEVICE, n doubles each, NULL to skip): opd[r] = W_r, pupil_x[r] = x_r, pupil_y[r] = y_r for used slots, NaN for the others.
+ * Three launches per call (prep over all jobs, the Gram sums per run of jobs of one order, the fold over all jobs); fixed
+ * summation order, no float atomics, and a job's slicing depends on its own n and order only: every job gets the same
+ * bytes whichever jobs share its call.  jobs_dev: DEVICE copy of the HOST array jobs_host (read for validation and the
+ * launch plan; both must hold the same contents).  scratch: DEVICE, art_wavefront_scratch_doubles(jobs_host, n_jobs).
+ * Limits: 1 <= n_jobs <= 65535, 0 <= n <= 2^28, 0 <= order <= ART_WAVEFRONT_MAX_ORDER, out non-NULL, finite ref,
+ * L_ref and pupil, rho >= 0, views complete when n > 0: ART_ERR_BAD_ARG (ART_ERR_UNSUPPORTED for n) otherwise, with
+ * nothing launched.                                                                                                    */
+#define ART_WAVEFRONT_MAX_ORDER 10
+#define ART_WAVEFRONT_MAX_COLS 68         /* K at ART_WAVEFRONT_MAX_ORDER                                              */
+#define ART_WAVEFRONT_DOUBLES 2360        /* 8 + K (K + 1) / 2 at K = 68, padded                                       */
+typedef struct ArtWavefrontJob {
+  ArtDetectorDesc det;
+  ArtBundleView b;
+  const double* w;        /* DEVICE weights (Ray.intensity) or NULL (w = 1)                                         */
+  int64_t n;              /* slots of b                                                                             */
+  double ref[3];          /* X, Y, s of the reference point R (mm)                                                  */
+  double L_ref;           /* the optical path of W = 0                                                              */
+  double pupil[3];        /* a1, a2 (direction cosines), rho (0 = computed)                                         */
+  int32_t order;          /* N, 0 .. ART_WAVEFRONT_MAX_ORDER                                                        */
+  int32_t reserved;
+  double* opd;            /* DEVICE, n doubles, or NULL                                                             */
+  double* pupil_x;        /* DEVICE, n doubles, or NULL                                                             */
+  double* pupil_y;        /* DEVICE, n doubles, or NULL                                                             */
+  double* out;            /* DEVICE, ART_WAVEFRONT_DOUBLES doubles                                                  */
+} ArtWavefrontJob;
+int64_t art_wavefront_scratch_doubles(const ArtWavefrontJob* jobs_host, int32_t n_jobs);
+int art_wavefront(const ArtWavefrontJob* jobs_dev, const ArtWavefrontJob* jobs_host, int32_t n_jobs, double* scratch,
+                  void* stream);
+
 /* Masked reductions over alive rays, deterministic (fixed two-level tree, no float atomics).
  * out16 (DEVICE, 16 doubles):
  *   [0] count  [1] sum opl  [2] min X [3] max X [4] min Y [5] max Y  [6] sum X [7] sum Y
