@@ -149,6 +149,15 @@ class OpticalChain:
         from . import histogram
         return histogram.footprint(self.optical_elements[OEindx], self.get_output_rays()[OEindx], Bins, Range)
 
+    def get_Polarisation(self, Coatings, Polarisation=None, Detector=None, Wavelength=None, PerRay=False):
+        """Mirror coatings and polarisation along the chain (polarisation.Polarisation), one device pass over
+        get_output_rays() and source_rays.  Coatings: one coating.Coating for every mirror, or one entry per element
+        (None for masks).  Polarisation: a complex lab-frame 3-vector, or None for unpolarised light; Detector: the frame
+        of the Stokes sums; Wavelength: overrides the bundle's; PerRay: also the complex field per ray.  A lazy history
+        is materialised by its own mechanism, which costs one re-trace."""
+        from . import polarisation
+        return polarisation.polarisation(self, Coatings, Polarisation, Detector, Wavelength, PerRay)
+
     def _output_for(self, key, kwargs):
         """get_output_rays for a cache key the caller has computed already (trace_chain_list: once per chain)."""
         if key != self._last_key:

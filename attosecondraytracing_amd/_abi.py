@@ -172,6 +172,53 @@ class ArtWavefrontJob(C.Structure):
     ]
 
 
+ART_COATING_MAX_LAYERS = 256
+ART_COATING_MAX_MATERIALS = 6
+ART_POLARISATION_MAX_ELEMS = 64
+ART_POLARISATION_DOUBLES = 16
+
+
+class ArtCoatingMaterial(C.Structure):
+    _fields_ = [("n", C.c_double), ("kappa", C.c_double)]
+
+
+class ArtCoatingLayer(C.Structure):
+    _fields_ = [("thickness", C.c_double), ("roughness", C.c_double), ("material", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ArtCoating(C.Structure):
+    _fields_ = [
+        ("ideal", C.c_int32),
+        ("n_materials", C.c_int32),
+        ("n_layers", C.c_int32),
+        ("substrate", C.c_int32),
+        ("roughness", C.c_double),
+        ("reserved", C.c_double),
+        ("materials", ArtCoatingMaterial * ART_COATING_MAX_MATERIALS),
+        ("layers", ArtCoatingLayer * ART_COATING_MAX_LAYERS),
+    ]
+
+
+class ArtPolarisationJob(C.Structure):
+    _fields_ = [
+        ("views", C.c_void_p),
+        ("coating", C.c_int32 * ART_POLARISATION_MAX_ELEMS),
+        ("n_elems", C.c_int32),
+        ("polarised", C.c_int32),
+        ("n", C.c_int64),
+        ("pol", C.c_double * 6),
+        ("k", C.c_double),
+        ("has_det", C.c_int32),
+        ("reserved", C.c_int32),
+        ("det", ArtDetectorDesc),
+        ("w0", C.c_void_p),
+        ("w", C.c_void_p),
+        ("w_out", C.c_void_p),
+        ("field", C.c_void_p),
+        ("out", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); the loader checks every symbol exists (tests/test_abi.py does too)
 PROTOTYPES = {
     "art_abi_version": (C.c_int, []),
@@ -208,6 +255,9 @@ PROTOTYPES = {
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_wavefront_scratch_doubles": (C.c_int64, [C.POINTER(ArtWavefrontJob), C.c_int32]),
     "art_wavefront": (C.c_int, [C.c_void_p, C.POINTER(ArtWavefrontJob), C.c_int32, C.c_void_p, C.c_void_p]),
+    "art_polarisation_scratch_doubles": (C.c_int64, [C.POINTER(ArtPolarisationJob), C.c_int32]),
+    "art_polarisation": (C.c_int, [C.c_void_p, C.POINTER(ArtPolarisationJob), C.c_int32, C.c_void_p,
+                                   C.POINTER(ArtCoating), C.c_int32, C.c_void_p, C.c_void_p]),
     "art_reduce_scratch_doubles": (C.c_int64, []),
     "art_detector_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

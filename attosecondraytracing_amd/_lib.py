@@ -465,13 +465,14 @@ class HipBackend:
             self.check(self.fn["art_trace_guides"](darr, m, rays.data_ptr() + 64 * k0, alive.data_ptr() + k0, sp),
                        "art_trace_guides")
 
-    def _upload_table(self, arr):
-        """A DEVICE copy of the ctypes job table `arr`, enqueued on the current stream."""
+    def _upload_table(self, arr, purpose=None):
+        """A DEVICE copy of the ctypes job table `arr`, enqueued on the current stream.  `purpose`: a second table that
+        the same launches read (its own pool entry, so that two tables of one size never share a device copy)."""
         nb = C.sizeof(arr)
         # pinned staging + device table from a per-size pool (pinning host memory costs milliseconds): the pinned image is
         # rewritten only after its previous upload has completed, the device table is read by launches enqueued before
         # the next upload on the same stream
-        pkey = (nb, self.stream_key())
+        pkey = (nb, self.stream_key()) if purpose is None else (purpose, nb, self.stream_key())
         pair = self._job_pool.get(pkey)
         if pair is None:
             pair = self._job_pool[pkey] = [torch.empty(nb, dtype=torch.uint8, pin_memory=True),
@@ -499,6 +500,32 @@ class HipBackend:
         dev = self._upload_table(arr)
         scratch = self.scratch("wavefront", ns, torch.float64)
         self.check(self.fn["art_wavefront"](dev.data_ptr(), arr, c, scratch.data_ptr(), self.stream_ptr()), "art_wavefront")
+        return out
+
+    def polarisation(self, jobs, views, coatings):
+        """art_polarisation for a list of ArtPolarisationJob (host structs; their `views` and `out` are set here), the
+        HOST ctypes arrays of every job's K + 1 views and a list of ArtCoating: uploads views, coatings and job table,
+        enqueues the two launches and returns the DEVICE tensor out[len(jobs), ART_POLARISATION_DOUBLES]."""
+        c = len(jobs)
+        out = torch.empty((c, _abi.ART_POLARISATION_DOUBLES), dtype=torch.float64, device=self.device)
+        blob = b"".join(bytes(v) for v in views) + b"".join(bytes(k) for k in coatings)
+        dev = self._upload_table((C.c_char * len(blob)).from_buffer_copy(blob), "polarisation views")
+        off = 0
+        jarr = (_abi.ArtPolarisationJob * c)()
+        for k, (j, v) in enumerate(zip(jobs, views)):
+            jarr[k] = j
+            jarr[k].views = dev.data_ptr() + off
+            jarr[k].out = out.data_ptr() + 8 * _abi.ART_POLARISATION_DOUBLES * k
+            off += C.sizeof(v)
+        carr = (_abi.ArtCoating * max(len(coatings), 1))(*coatings)
+        cdev = dev.data_ptr() + off if coatings else None
+        ns = self.fn["art_polarisation_scratch_doubles"](jarr, c)
+        if ns < 0:
+            raise ArtError(f"art_polarisation_scratch_doubles failed with code {ns}: {self.last_error()}")
+        jdev = self._upload_table(jarr)
+        scratch = self.scratch("polarisation", ns, torch.float64)
+        self.check(self.fn["art_polarisation"](jdev.data_ptr(), jarr, c, cdev, carr, len(coatings), scratch.data_ptr(),
+                                               self.stream_ptr()), "art_polarisation")
         return out
 
     def analyse_bundles(self, jobs, n):

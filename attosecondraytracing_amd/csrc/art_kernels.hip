@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "art_device.h"
+#include "art_coating.h"
 #include "art_scene.h"
 
 // The -DART_ZERN_LDS comparison build keeps a persistent grid whose last pass may leave part of a workgroup idle: no
@@ -2101,6 +2102,159 @@ constexpr WfGramLaunch kWfGram[ART_WAVEFRONT_MAX_ORDER + 1] = {
     launch_wf_gram<0>, launch_wf_gram<1>, launch_wf_gram<2>, launch_wf_gram<3>, launch_wf_gram<4>, launch_wf_gram<5>,
     launch_wf_gram<6>, launch_wf_gram<7>, launch_wf_gram<8>, launch_wf_gram<9>, launch_wf_gram<10>};
 
+// ------------------------------------------------------------------------------------------- polarisation
+// art_polarisation: one pass over a traced chain's history per job (include/art_hip.h; the per-ray math is art_coating.h).
+// k_polarisation: grid (tiles of 256 slots, jobs), one ray per lane.  The slot's alive bytes in the source and the final
+// bundle are read first; every other stream of a slot that is dead at the end is requested at an out-of-range offset
+// (no traffic, reads 0, selected away).
+// Job, views and coating table are wave-uniform: scalar loads.  Per tile kPolStats partials (block_reduce_store), folded
+// per job in tile order by k_polarisation_fold (fold_range).  A job's tiles depend on its own n: same bytes in any batch.
+constexpr int kPolStats = 11;   // [0] alive [1] sum w0 [2] sum w_out [3] min T [4] max T [5..9] Stokes, |E.n|^2 [10] min |P_perp|
+__host__ __device__ inline int64_t pol_tiles(const int64_t n) { return n < 1 ? 1 : (n + kBlock - 1) / kBlock; }
+constexpr int pol_op(const int q) { return (q == 3 || q == 10) ? RMIN : (q == 4 ? RMAX : RSUM); }
+
+// The views are read through the constant address space: scalar loads (a pointer fetched from the job table is a
+// generic one, and a generic load of a descriptor's base would need a waterfall loop around every buffer access)
+typedef const ArtBundleView __attribute__((address_space(4)))* pol_view_t;
+__device__ __forceinline__ void pol_dirs(const ArtBundleView* views, const int e, const unsigned nb8, const unsigned o8,
+                                         double* d) {
+  const pol_view_t v = (pol_view_t)views + e;
+  d[0] = ld_f64(rsrc_of(v->dx, nb8), o8);
+  d[1] = ld_f64(rsrc_of(v->dy, nb8), o8);
+  d[2] = ld_f64(rsrc_of(v->dz, nb8), o8);
+}
+__device__ __forceinline__ uint8_t* pol_alive(const ArtBundleView* views, const int e) { return ((pol_view_t)views + e)->alive; }
+
+__global__ __launch_bounds__(kBlock, 4) void k_polarisation(const ArtPolarisationJob* __restrict__ jobs,
+                                                         const ArtCoating* __restrict__ coats, const int64_t per_job,
+                                                         double* scratch) {
+  __shared__ artc::cplx s_kz[ART_COATING_MAX_MATERIALS * kBlock];   // kz / k per material, one column per lane
+  __shared__ double s_dir[6 * kBlock];                                     // d_in, d_out, one column per lane
+  const ArtPolarisationJob& jb = jobs[blockIdx.y];
+  const int64_t n = jb.n;
+  if ((int64_t)blockIdx.x >= pol_tiles(n)) return;     // (the grid covers the largest job)
+  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned nb8 = (unsigned)(n * 8), nb1 = (unsigned)n;   // n <= 2^28 (checked by the host)
+  const int K = jb.n_elems;
+  const ArtBundleView* views = jb.views;
+  const bool live = __builtin_amdgcn_raw_buffer_load_b8(rsrc_of(pol_alive(views, K), nb1), (int)i, 0, ART_LD_AUX) != 0;
+  const bool live0 = __builtin_amdgcn_raw_buffer_load_b8(rsrc_of(pol_alive(views, 0), nb1), (int)i, 0, ART_LD_AUX) != 0;
+  const unsigned o8 = live ? i * 8u : kDropOffset, o8s = live0 ? i * 8u : kDropOffset;
+  const double w = jb.w ? ld_f64(rsrc_of(const_cast<double*>(jb.w), nb8), o8) : 1.0;
+  const double w0 = jb.w0 ? ld_f64(rsrc_of(const_cast<double*>(jb.w0), nb8), o8s) : 1.0;
+  double din[3];
+  pol_dirs(views, 0, nb8, o8, din);
+  const bool pol = jb.polarised != 0;
+  // the input state(s), transverse to the source direction
+  double er0[3], ei0[3], er1[3], ei1[3];
+  double pmin = INFINITY;
+  if (pol) {
+    const double* P = jb.pol;
+    const double pr = P[0] * din[0] + P[2] * din[1] + P[4] * din[2], pi = P[1] * din[0] + P[3] * din[1] + P[5] * din[2];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      er0[q] = P[2 * q] - pr * din[q];
+      ei0[q] = P[2 * q + 1] - pi * din[q];
+    }
+    const double m = sqrt(er0[0] * er0[0] + er0[1] * er0[1] + er0[2] * er0[2] + ei0[0] * ei0[0] + ei0[1] * ei0[1] +
+                          ei0[2] * ei0[2]);
+    pmin = m;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { er0[q] /= m; ei0[q] /= m; er1[q] = ei1[q] = 0.0; }
+  } else {
+    artc::perp_unit(din[0], din[1], din[2], er0[0], er0[1], er0[2]);
+    er1[0] = din[1] * er0[2] - din[2] * er0[1];
+    er1[1] = din[2] * er0[0] - din[0] * er0[2];
+    er1[2] = din[0] * er0[1] - din[1] * er0[0];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) ei0[q] = ei1[q] = 0.0;
+  }
+  for (int e = 0; e < K; ++e) {
+    double dout[3];
+    pol_dirs(views, e + 1, nb8, o8, dout);
+    const int c = jb.coating[e];
+    if (c >= 0) {                                         // (a mask leaves E unchanged)
+      // the two directions wait in LDS while the coefficients are formed (the Parratt loop needs every register)
+      double* sd = s_dir + threadIdx.x;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) { sd[q * kBlock] = din[q]; sd[(3 + q) * kBlock] = dout[q]; }
+      artc::cplx rs, rp;
+      artc::coating_rs_rp(coats[c], artc::sin2_incidence(din, dout), jb.k, s_kz + threadIdx.x, kBlock, rs, rp);
+      asm volatile("" ::: "memory");                      // (read them back: do not keep them in registers)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) { din[q] = sd[q * kBlock]; dout[q] = sd[(3 + q) * kBlock]; }
+      artc::Frame f;                                      // (formed after the coefficients: fewer registers live)
+      artc::reflection_frame(din, dout, f);
+      artc::prt_step(f, rs, rp, er0, ei0);
+      if (!pol) artc::prt_step(f, rs, rp, er1, ei1);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) din[q] = dout[q];
+  }
+  const double T0 = (er0[0] * er0[0] + er0[1] * er0[1] + er0[2] * er0[2]) + (ei0[0] * ei0[0] + ei0[1] * ei0[1] + ei0[2] * ei0[2]);
+  const double T1 = (er1[0] * er1[0] + er1[1] * er1[1] + er1[2] * er1[2]) + (ei1[0] * ei1[0] + ei1[1] * ei1[1] + ei1[2] * ei1[2]);
+  const double T = pol ? T0 : 0.5 * (T0 + T1);
+  const double wout = live ? w * T : 0.0;
+  st_f64(rsrc_of(jb.w_out, nb8), i * 8u, wout);           // (slots >= n fall outside the descriptor)
+  if (jb.field && (int64_t)i < n) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      jb.field[2 * ((int64_t)q * n + i)] = live ? er0[q] : 0.0;
+      jb.field[2 * ((int64_t)q * n + i) + 1] = live ? ei0[q] : 0.0;
+    }
+  }
+  double acc[kPolStats];
+  acc[0] = live ? 1.0 : 0.0;
+  acc[1] = live0 ? w0 : 0.0;
+  acc[2] = wout;
+  acc[3] = live ? T : INFINITY;
+  acc[4] = live ? T : -INFINITY;
+  double st[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  if (jb.has_det) {
+    const double* e1 = jb.det.rot;
+    const double* e2 = jb.det.rot + 3;
+    const double* nd = jb.det.normal;
+    auto stokes = [&](const double* er, const double* ei, const double scale) {
+      const double xr = er[0] * e1[0] + er[1] * e1[1] + er[2] * e1[2], xi = ei[0] * e1[0] + ei[1] * e1[1] + ei[2] * e1[2];
+      const double yr = er[0] * e2[0] + er[1] * e2[1] + er[2] * e2[2], yi = ei[0] * e2[0] + ei[1] * e2[1] + ei[2] * e2[2];
+      const double zr = er[0] * nd[0] + er[1] * nd[1] + er[2] * nd[2], zi = ei[0] * nd[0] + ei[1] * nd[1] + ei[2] * nd[2];
+      const double ix = xr * xr + xi * xi, iy = yr * yr + yi * yi;
+      st[0] += scale * (ix + iy);
+      st[1] += scale * (ix - iy);
+      st[2] += scale * (2.0 * (xr * yr + xi * yi));
+      st[3] += scale * (2.0 * (xr * yi - xi * yr));
+      st[4] += scale * (zr * zr + zi * zi);
+    };
+    const double ws = live ? w : 0.0;
+    stokes(er0, ei0, pol ? ws : 0.5 * ws);
+    if (!pol) stokes(er1, ei1, 0.5 * ws);
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) acc[5 + q] = (live && jb.has_det) ? st[q] : 0.0;
+  acc[10] = (live && pol) ? pmin : INFINITY;
+  block_reduce_store<kPolStats>(acc, pol_op, scratch + (int64_t)blockIdx.y * per_job + (int64_t)blockIdx.x * kPolStats);
+}
+
+// grid (ART_POLARISATION_DOUBLES, jobs): workgroup (q, j) folds statistic q of job j's tiles in tile order
+__global__ __launch_bounds__(kFoldBlock) void k_polarisation_fold(const ArtPolarisationJob* __restrict__ jobs,
+                                                                  const int64_t per_job, const double* scratch) {
+  const int q = blockIdx.x;
+  const ArtPolarisationJob& jb = jobs[blockIdx.y];
+  if (q >= kPolStats) {
+    if (threadIdx.x == 0) jb.out[q] = 0.0;
+    return;
+  }
+  const double* part = scratch + (int64_t)blockIdx.y * per_job;
+  const int64_t tiles = pol_tiles(jb.n);
+  double v = 0.0, cnt = 1.0;
+  fold_range(part + q, 0, tiles, pol_op(q), &v, kPolStats);
+  if (q == 3 || q == 4 || q == 10) {                      // a minimum or maximum over no ray is 0
+    __syncthreads();
+    fold_range(part, 0, tiles, RSUM, &cnt, kPolStats);
+  }
+  if (threadIdx.x == 0) jb.out[q] = (cnt == 0.0 || (q == 10 && !jb.polarised)) ? 0.0 : v;
+}
+
 template <bool HAS_W>
 __global__ __launch_bounds__(kBlock) void k_moments_partial(const uint8_t* alive, const double* X, const double* Y,
                                                             const double* opl, const double* w, const int64_t n,
@@ -3524,6 +3678,81 @@ int art_wavefront(const ArtWavefrontJob* jobs_dev, const ArtWavefrontJob* jobs_h
   hipLaunchKernelGGL(k_wavefront_fold, dim3((ART_WAVEFRONT_DOUBLES + kBlock - 1) / kBlock, n_jobs), dim3(kBlock), 0, s,
                      jobs_dev, a, (const double*)scratch);
   return launched("art_wavefront launch");
+}
+
+// validates a polarisation job table (not its coatings); *nmax: the largest slot count
+static int pol_check_jobs(const ArtPolarisationJob* jobs, int32_t n_jobs, int64_t* nmax) {
+  if (!jobs) return fail(ART_ERR_BAD_ARG, "polarisation job table is NULL");
+  if (n_jobs < 1 || n_jobs > 65535) return fail(ART_ERR_BAD_ARG, "n_jobs must be in 1..65535");
+  *nmax = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const ArtPolarisationJob& jb = jobs[j];
+    if (jb.n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+    if (jb.n > kMaxRaysPerLaunchHw) return fail(ART_ERR_UNSUPPORTED, "more than 2^28 rays per chain in one polarisation call");
+    if (jb.n_elems < 1 || jb.n_elems > ART_POLARISATION_MAX_ELEMS)
+      return fail(ART_ERR_BAD_ARG, "a polarisation job must have 1..ART_POLARISATION_MAX_ELEMS elements");
+    *nmax = jb.n > *nmax ? jb.n : *nmax;
+  }
+  return ART_OK;
+}
+
+static int coating_check(const ArtCoating& c) {
+  if (c.ideal) return ART_OK;
+  if (c.n_materials < 1 || c.n_materials > ART_COATING_MAX_MATERIALS)
+    return fail(ART_ERR_BAD_ARG, "a coating must name 1..ART_COATING_MAX_MATERIALS materials");
+  if (c.n_layers < 0 || c.n_layers > ART_COATING_MAX_LAYERS)
+    return fail(ART_ERR_BAD_ARG, "a coating must have 0..ART_COATING_MAX_LAYERS layers");
+  if (c.substrate < 0 || c.substrate >= c.n_materials) return fail(ART_ERR_BAD_ARG, "coating substrate index out of range");
+  if (!(isfinite(c.roughness) && c.roughness >= 0.0)) return fail(ART_ERR_BAD_ARG, "coating roughness must be finite and >= 0");
+  for (int m = 0; m < c.n_materials; ++m)
+    if (!(isfinite(c.materials[m].n) && isfinite(c.materials[m].kappa) && c.materials[m].kappa >= 0.0))
+      return fail(ART_ERR_BAD_ARG, "a coating material must have finite n and finite kappa >= 0");
+  for (int l = 0; l < c.n_layers; ++l) {
+    const ArtCoatingLayer& ly = c.layers[l];
+    if (ly.material < 0 || ly.material >= c.n_materials) return fail(ART_ERR_BAD_ARG, "coating layer material out of range");
+    if (!(isfinite(ly.thickness) && ly.thickness >= 0.0 && isfinite(ly.roughness) && ly.roughness >= 0.0))
+      return fail(ART_ERR_BAD_ARG, "coating layer thickness and roughness must be finite and >= 0");
+  }
+  return ART_OK;
+}
+
+int64_t art_polarisation_scratch_doubles(const ArtPolarisationJob* jobs_host, int32_t n_jobs) {
+  int64_t nmax;
+  const int rc = pol_check_jobs(jobs_host, n_jobs, &nmax);
+  return rc ? rc : (int64_t)n_jobs * kPolStats * pol_tiles(nmax);
+}
+
+int art_polarisation(const ArtPolarisationJob* jobs_dev, const ArtPolarisationJob* jobs_host, int32_t n_jobs,
+                     const ArtCoating* coatings_dev, const ArtCoating* coatings_host, int32_t n_coatings, double* scratch,
+                     void* stream) {
+  if (!jobs_dev || !scratch) return fail(ART_ERR_BAD_ARG, "NULL argument");
+  int64_t nmax;
+  const int rc = pol_check_jobs(jobs_host, n_jobs, &nmax);
+  if (rc) return rc;
+  if (n_coatings < 0 || n_coatings > 65535) return fail(ART_ERR_BAD_ARG, "n_coatings must be in 0..65535");
+  if (n_coatings > 0 && (!coatings_dev || !coatings_host)) return fail(ART_ERR_BAD_ARG, "coating table is NULL");
+  for (int c = 0; c < n_coatings; ++c) {
+    const int cr = coating_check(coatings_host[c]);
+    if (cr) return cr;
+  }
+  for (int j = 0; j < n_jobs; ++j) {
+    const ArtPolarisationJob& jb = jobs_host[j];
+    if (!jb.out || !jb.w_out || !jb.views) return fail(ART_ERR_BAD_ARG, "a polarisation job's views, w_out or out is NULL");
+    if (!(isfinite(jb.k) && jb.k > 0.0)) return fail(ART_ERR_BAD_ARG, "a polarisation job's wave number must be finite and > 0");
+    bool finite = true;
+    for (int q = 0; q < 6; ++q) finite = finite && isfinite(jb.pol[q]);
+    if (!finite) return fail(ART_ERR_BAD_ARG, "a polarisation job's input state is not finite");
+    if (jb.field && !jb.polarised) return fail(ART_ERR_BAD_ARG, "the per-ray field needs a polarised input");
+    for (int e = 0; e < jb.n_elems; ++e)
+      if (jb.coating[e] < -1 || jb.coating[e] >= n_coatings) return fail(ART_ERR_BAD_ARG, "coating index out of range");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t per_job = kPolStats * pol_tiles(nmax);
+  hipLaunchKernelGGL(k_polarisation, dim3((unsigned)pol_tiles(nmax), n_jobs), dim3(kBlock), 0, s, jobs_dev, coatings_dev,
+                     per_job, scratch);
+  hipLaunchKernelGGL(k_polarisation_fold, dim3(ART_POLARISATION_DOUBLES, n_jobs), dim3(kFoldBlock), 0, s, jobs_dev, per_job,
+                     (const double*)scratch);
+  return launched("art_polarisation launch");
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }

@@ -406,6 +406,87 @@ int64_t art_wavefront_scratch_doubles(const ArtWavefrontJob* jobs_host, int32_t 
 int art_wavefront(const ArtWavefrontJob* jobs_dev, const ArtWavefrontJob* jobs_host, int32_t n_jobs, double* scratch,
                   void* stream);
 
+/* Mirror coatings and polarisation of MANY traced chains in one call (added under ABI 14: ArtCoatingMaterial,
+ * ArtCoatingLayer, ArtCoating, ArtPolarisationJob, art_polarisation, art_polarisation_scratch_doubles).  One streaming
+ * pass over a chain's existing history; the tracing kernels are not involved.  Time dependence exp(-i w t).
+ * Per ray and reflecting element, with d_in, d_out the unit directions before and after it (views[e], views[e + 1]):
+ *   n = normalize(d_out - d_in), cos t = |d_out - d_in| / 2, sin^2 t = 1 - cos^2 t
+ *   s = normalize(d_in x d_out) (|d_in x d_out| < 1e-12: normalize(d_in x a), a the lab axis of d_in's smallest
+ *   |component|, the first of equals), p_in = d_in x s, p_out = d_out x s
+ *   E' = rs (E.s) s + rp (E.p_in) p_out           (bilinear dot products, no conjugation)
+ * A mask (coating index -1) leaves E unchanged.  rs, rp of a coating: N = n + i kappa per material, medium 0 vacuum,
+ * layers 1..L top down, L + 1 the substrate, kz_j = k sqrt(N_j^2 - sin^2 t) with Im kz_j >= 0, k = 2 pi / wavelength;
+ *   r^s_{j,j+1} = (kz_j - kz_{j+1}) / (kz_j + kz_{j+1}),
+ *   r^p_{j,j+1} = (N_{j+1}^2 kz_j - N_j^2 kz_{j+1}) / (N_{j+1}^2 kz_j + N_j^2 kz_{j+1}),
+ *   both times exp(-2 kz_j kz_{j+1} sigma_{j,j+1}^2) (Nevot-Croce) where sigma > 0;
+ *   R_{L+1} = 0, R_j = (r_{j,j+1} + R_{j+1} X) / (1 + r_{j,j+1} R_{j+1} X), X = exp(2 i kz_{j+1} t_{j+1});  rs = R^s_0,
+ *   rp = R^p_0.  `ideal`: the perfect conductor, rs = -1, rp = +1.
+ * kz is formed once per material, ray and element (a periodic stack names few materials), then one Parratt step per layer.
+ * Input state: polarised -> E0 = P - (P.d0) d0 over its norm (P = pol, complex, lab frame; d0 the source direction);
+ * unpolarised -> the two states u1 = normalize(d0 x a) (a as for s above), u2 = d0 x u1, whose intensities and Stokes
+ * sums are averaged.  Per slot, for the rays alive in views[K] (others: w_out = 0, field = 0):
+ *   T = |E_K|^2 (unpolarised: the mean of the two states),  w_out = w T  (w = w[r], or 1 when w is NULL)
+ *   field (optional, polarised only): E_K as complex128 [3][n] (component c of slot r at 2 (c n + r), re then im)
+ * out (DEVICE, ART_POLARISATION_DOUBLES doubles, written):
+ *   [0] rays alive in views[K]  [1] sum w0 over the rays alive in views[0] (w0 NULL: their count)  [2] sum w_out
+ *   [3] min T  [4] max T  (0 when no ray is alive)
+ *   [5..8] S0..S3 = sum w (|Ex|^2 + |Ey|^2), sum w (|Ex|^2 - |Ey|^2), sum w 2 Re(conj(Ex) Ey), sum w 2 Im(conj(Ex) Ey)
+ *   [9] sum w |E.nd|^2   with Ex = E.e1, Ey = E.e2, e1, e2 = rows 0, 1 of det.rot, nd = det.normal (0 without has_det)
+ *   [10] min over the alive rays of |P - (P.d0) d0| (polarised; 0 otherwise or when no ray is alive)  [11..15] 0
+ * Fixed summation order, no float atomics; a job's slicing depends on its own n only: every job gets the same bytes
+ * whichever jobs share its call.  jobs_dev / coatings_dev: DEVICE copies of the HOST arrays jobs_host / coatings_host
+ * (read for validation and the launch plan).  scratch: DEVICE, art_polarisation_scratch_doubles(jobs_host, n_jobs).
+ * Limits: 1 <= n_jobs <= 65535, 0 <= n <= 2^28, 1 <= n_elems <= ART_POLARISATION_MAX_ELEMS, coating indices in
+ * [-1, n_coatings), 0 <= n_coatings <= 65535, finite k > 0 and pol, w_out and out non-NULL, views non-NULL; per coating
+ * 1 <= n_materials <= ART_COATING_MAX_MATERIALS, 0 <= n_layers <= ART_COATING_MAX_LAYERS, material indices in range,
+ * finite n, kappa >= 0, thickness >= 0, roughness >= 0: ART_ERR_BAD_ARG (ART_ERR_UNSUPPORTED for n) otherwise, with
+ * nothing launched.  The views' arrays hold n slots each; the rays are read at the slots alive in views[K].         */
+#define ART_COATING_MAX_LAYERS 256
+#define ART_COATING_MAX_MATERIALS 6
+#define ART_POLARISATION_MAX_ELEMS 64
+#define ART_POLARISATION_DOUBLES 16
+typedef struct ArtCoatingMaterial {
+  double n;               /* N = n + i kappa                                                                        */
+  double kappa;           /* >= 0                                                                                   */
+} ArtCoatingMaterial;
+typedef struct ArtCoatingLayer {
+  double thickness;       /* mm, >= 0                                                                               */
+  double roughness;       /* sigma (mm, >= 0) of the interface at the TOP of this layer                             */
+  int32_t material;       /* index into materials                                                                   */
+  int32_t reserved;
+} ArtCoatingLayer;
+typedef struct ArtCoating {
+  int32_t ideal;          /* 1: perfect conductor (the rest is ignored)                                             */
+  int32_t n_materials;
+  int32_t n_layers;       /* L                                                                                      */
+  int32_t substrate;      /* material index of the substrate                                                        */
+  double roughness;       /* sigma (mm) of the substrate's top interface                                            */
+  double reserved;
+  ArtCoatingMaterial materials[ART_COATING_MAX_MATERIALS];
+  ArtCoatingLayer layers[ART_COATING_MAX_LAYERS];   /* top first                                                     */
+} ArtCoating;
+typedef struct ArtPolarisationJob {
+  const ArtBundleView* views;  /* DEVICE array of n_elems + 1 views: the source, then the bundle after each element  */
+  int32_t coating[ART_POLARISATION_MAX_ELEMS];     /* per element: index into the coatings, -1 for a mask          */
+  int32_t n_elems;        /* K                                                                                      */
+  int32_t polarised;      /* 1: E0 from pol; 0: unpolarised                                                         */
+  int64_t n;              /* slots of every view                                                                    */
+  double pol[6];          /* P: re x, im x, re y, im y, re z, im z                                                  */
+  double k;               /* 2 pi / wavelength (1/mm)                                                               */
+  int32_t has_det;        /* 1: Stokes sums in det's frame                                                          */
+  int32_t reserved;
+  ArtDetectorDesc det;
+  const double* w0;       /* DEVICE weights of the source (views[0]) or NULL                                        */
+  const double* w;        /* DEVICE weights of the final bundle (views[K]) or NULL                                  */
+  double* w_out;          /* DEVICE, n doubles                                                                      */
+  double* field;          /* DEVICE, 6 n doubles (complex128 [3][n]), or NULL                                       */
+  double* out;            /* DEVICE, ART_POLARISATION_DOUBLES doubles                                               */
+} ArtPolarisationJob;
+int64_t art_polarisation_scratch_doubles(const ArtPolarisationJob* jobs_host, int32_t n_jobs);
+int art_polarisation(const ArtPolarisationJob* jobs_dev, const ArtPolarisationJob* jobs_host, int32_t n_jobs,
+                     const ArtCoating* coatings_dev, const ArtCoating* coatings_host, int32_t n_coatings, double* scratch,
+                     void* stream);
+
 /* Masked reductions over alive rays, deterministic (fixed two-level tree, no float atomics).
  * out16 (DEVICE, 16 doubles):
  *   [0] count  [1] sum opl  [2] min X [3] max X [4] min Y [5] max Y  [6] sum X [7] sum Y

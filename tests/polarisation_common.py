@@ -1,0 +1,134 @@
+"""The NumPy oracle of art_polarisation: per-layer Parratt recursion plus the 3x3 polarisation
+ray-tracing step, complex128, written independently of the device code and of coating.Coating.reflectance."""
+import numpy as np
+
+
+def index_of(v):
+    return complex(1 - v[0], v[1]) if isinstance(v, (tuple, list)) else complex(v)
+
+
+def parratt(media, thick, sigma, s2, k):
+    """rs, rp of media [N_0 = vacuum, N_1 .. N_L, N_sub] (thick[j] of medium j, 1 <= j <= L; sigma[j] of interface
+    j, j + 1) at sin^2 t = s2 (array), wave number k."""
+    s2 = np.asarray(s2, dtype=float)
+    kz = []
+    for N in media:
+        q = np.sqrt(complex(N) ** 2 - s2.astype(complex))
+        kz.append(k * np.where(q.imag < 0, -q, q))
+    L = len(media) - 2
+    Rs = np.zeros(s2.shape, complex)
+    Rp = np.zeros(s2.shape, complex)
+    for j in range(L, -1, -1):
+        e0, e1 = complex(media[j]) ** 2, complex(media[j + 1]) ** 2
+        rs = (kz[j] - kz[j + 1]) / (kz[j] + kz[j + 1])
+        rp = (e1 * kz[j] - e0 * kz[j + 1]) / (e1 * kz[j] + e0 * kz[j + 1])
+        if sigma[j] > 0:
+            f = np.exp(-2 * kz[j] * kz[j + 1] * sigma[j] ** 2)
+            rs, rp = rs * f, rp * f
+        X = np.exp(2j * kz[j + 1] * thick[j + 1]) if j < L else 0
+        Rs = (rs + Rs * X) / (1 + rs * Rs * X)
+        Rp = (rp + Rp * X) / (1 + rp * Rp * X)
+    return Rs, Rp
+
+
+def coating_rs_rp(c, s2, k):
+    """rs, rp of a coating.Coating (its fields only) at sin^2 t = s2."""
+    if c.is_ideal:
+        return np.full(np.shape(s2), -1.0 + 0j), np.full(np.shape(s2), 1.0 + 0j)
+    media = [1.0] + [ly[0] for ly in c.layers] + [c.substrate]
+    thick = [0.0] + [ly[1] for ly in c.layers] + [0.0]
+    sigma = [ly[2] for ly in c.layers] + [c.roughness]
+    return parratt(media, thick, sigma, s2, k)
+
+
+def perp_unit(d):
+    """normalize(d x a), a the lab axis of d's smallest |component| (the first of equals), per row of d [n, 3]."""
+    a = np.abs(d)
+    ax = np.where((a[:, 0] <= a[:, 1]) & (a[:, 0] <= a[:, 2]), 0, np.where(a[:, 1] <= a[:, 2], 1, 2))
+    e = np.eye(3)[ax]
+    s = np.cross(d, e)
+    return s / np.linalg.norm(s, axis=1)[:, None]
+
+
+def propagate(dirs, coats, E, k):
+    """dirs: [K + 1] arrays [n, 3]; coats: K entries (Coating or None = mask); E [n, 3] complex -> E_K."""
+    E = E.astype(complex)
+    for e, c in enumerate(coats):
+        a, b = dirs[e], dirs[e + 1]
+        if c is None:
+            continue
+        cos = np.linalg.norm(b - a, axis=1) / 2
+        s2 = 1 - cos * cos
+        rs, rp = coating_rs_rp(c, s2, k)
+        s = np.cross(a, b)
+        m = np.linalg.norm(s, axis=1)
+        near = m < 1e-12
+        s = np.where(near[:, None], perp_unit(a), s / np.where(near, 1.0, m)[:, None])
+        pin, pout = np.cross(a, s), np.cross(b, s)
+        Es = np.sum(E * s, axis=1)
+        Ep = np.sum(E * pin, axis=1)
+        E = (rs * Es)[:, None] * s + (rp * Ep)[:, None] * pout
+    return E
+
+
+def run(dirs, alive_src, alive, coats, k, P=None, w=None, w0=None, det=None, basis=None):
+    """The oracle of one chain: dict with T [n], w_out [n], E [n, 3] (polarised), the statistics row of
+    art_polarisation (16 doubles).  basis: the two unpolarised states [2][n, 3] (default: the device's choice)."""
+    n = len(alive)
+    d0 = dirs[0]
+    wv = np.ones(n) if w is None else np.asarray(w, float)
+    w0v = np.ones(n) if w0 is None else np.asarray(w0, float)
+    if P is not None:
+        P = np.asarray(P, complex)
+        Ep = P[None, :] - np.sum(P[None, :] * d0, axis=1)[:, None] * d0
+        m = np.sqrt(np.sum(np.abs(Ep) ** 2, axis=1))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            states = [Ep / m[:, None]]
+    else:
+        if basis is None:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                u1 = perp_unit(d0)
+            basis = [u1, np.cross(d0, u1)]
+        states = [b.astype(complex) for b in basis]
+        m = None
+    with np.errstate(invalid="ignore", divide="ignore"):      # (dead slots carry unspecified directions)
+        outs = [propagate(dirs, coats, S, k) for S in states]
+    T = np.where(alive.astype(bool), np.mean([np.sum(np.abs(E) ** 2, axis=1) for E in outs], axis=0), 0.0)
+    a = alive.astype(bool)
+    wout = np.where(a, wv * T, 0.0)
+    row = np.zeros(16)
+    row[0] = a.sum()
+    row[1] = w0v[alive_src.astype(bool)].sum()
+    row[2] = wout.sum()
+    if a.any():
+        row[3], row[4] = T[a].min(), T[a].max()
+        if P is not None:
+            row[10] = m[a].min()
+    if det is not None:
+        e1, e2, nd = det
+        for E in outs:
+            E = np.where(a[:, None], E, 0)
+            Ex, Ey, En = E @ e1, E @ e2, E @ nd
+            ww = np.where(a, wv, 0.0) / len(outs)
+            row[5] += np.sum(ww * (abs(Ex) ** 2 + abs(Ey) ** 2))
+            row[6] += np.sum(ww * (abs(Ex) ** 2 - abs(Ey) ** 2))
+            row[7] += np.sum(ww * 2 * (np.conj(Ex) * Ey).real)
+            row[8] += np.sum(ww * 2 * (np.conj(Ex) * Ey).imag)
+            row[9] += np.sum(ww * abs(En) ** 2)
+    return {"T": T, "w_out": wout, "E": np.where(a[:, None], outs[0], 0) if P is not None else None, "row": row}
+
+
+def gold(wavelength=13.5e-6):
+    """A gold-like single metal layer on glass (illustrative XUV constants)."""
+    from attosecondraytracing_amd.coating import Coating
+    return Coating((0.02, 0.01), [((0.1, 0.06), 40e-6, 0.5e-6)], Roughness=0.3e-6)
+
+
+def mosi(periods=40):
+    """A Mo/Si-like periodic stack on Si (illustrative constants at 13.5 nm), 2 x periods layers with roughness."""
+    from attosecondraytracing_amd.coating import Coating
+    mo, si = (0.0769, 0.0064), (0.0010, 0.0018)
+    layers = []
+    for _ in range(periods):
+        layers += [(si, 4.1e-6, 0.3e-6), (mo, 2.8e-6, 0.3e-6)]
+    return Coating(si, layers, Roughness=0.3e-6)
