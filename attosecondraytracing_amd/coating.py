@@ -76,12 +76,12 @@ class Coating:
         if self.is_ideal:
             return np.full(th.shape, -1.0 + 0j), np.full(th.shape, 1.0 + 0j)
         k = 2 * math.pi / wl
-        s2 = np.sin(th) ** 2
+        c2 = np.cos(th) ** 2           # kz / k = sqrt(N^2 - 1 + cos^2 theta): 1 - sin^2 would lose digits at grazing
         media = [1.0 + 0j] + [ly[0] for ly in self.layers] + [self.substrate]
         sig = [ly[2] for ly in self.layers] + [self.roughness]     # interface j, j + 1 has sig[j]
         kz = []
         for N in media:
-            q = np.sqrt(N * N - s2 + 0j)
+            q = np.sqrt((N - 1) * (N + 1) + c2 + 0j)
             kz.append(k * np.where(q.imag < 0, -q, q))
         rs = np.zeros(th.shape, complex)
         rp = np.zeros(th.shape, complex)

@@ -3,7 +3,9 @@
 // polarisation ray-tracing step E' = rs (E.s) s + rp (E.p_in) p_out.
 //
 // Conventions: time dependence exp(-i w t); N = n + i kappa with kappa >= 0; kz_j = k sqrt(N_j^2 - sin^2 t)
-// on the branch Im kz_j >= 0; medium 0 is vacuum, layers 1..L run top down, L + 1 is the substrate;
+// on the branch Im kz_j >= 0, formed from cos t as k sqrt((n - 1)(n + 1) - kappa^2 + cos^2 t + 2 i n kappa), vacuum k cos t
+// (never from sin^2 t = 1 - cos^2 t, which at a grazing angle g loses log10(1 / g^2) digits); medium 0 is vacuum,
+// layers 1..L run top down, L + 1 is the substrate;
 //   r^s_{j,j+1} = (kz_j - kz_{j+1}) / (kz_j + kz_{j+1})
 //   r^p_{j,j+1} = (N_{j+1}^2 kz_j - N_j^2 kz_{j+1}) / (N_{j+1}^2 kz_j + N_j^2 kz_{j+1})
 //   each times exp(-2 kz_j kz_{j+1} sigma_{j,j+1}^2) where the interface has a roughness sigma;
@@ -106,17 +108,18 @@ ART_HD cplx csqrt_up(const cplx z) {
   return cmk(z.im / (2.0 * t), t);              // Re z < 0: |Im w| = t, Re w = Im z / (2 Im w)
 }
 ART_HD cplx eps_of(const ArtCoatingMaterial& m) { return cmk(m.n * m.n - m.kappa * m.kappa, 2.0 * m.n * m.kappa); }
+// (kz / k)^2 = N^2 - 1 + cos^2 t, with N^2 - 1 as (n - 1)(n + 1) - kappa^2: no cancellation for n near 1 or small cos t
+ART_HD cplx kz2_of(const ArtCoatingMaterial& m, const double ct) {
+  return cmk((m.n - 1.0) * (m.n + 1.0) - m.kappa * m.kappa + ct * ct, 2.0 * m.n * m.kappa);
+}
 
 // kz / k of every material of a coating, into kz[m * stride]: the caller's per-lane table (the kernel keeps it in LDS,
 // one column per lane, so a wave-uniform material index is one read; no selects).  Vacuum (index -1) is formed where used.
-ART_HD void kz_table(const ArtCoating& c, const double s2, cplx* kz, const int stride) {
-  for (int m = 0; m < c.n_materials; ++m) {
-    const cplx e = eps_of(c.materials[m]);
-    kz[m * stride] = csqrt_up(cmk(e.re - s2, e.im));
-  }
+ART_HD void kz_table(const ArtCoating& c, const double ct, cplx* kz, const int stride) {
+  for (int m = 0; m < c.n_materials; ++m) kz[m * stride] = csqrt_up(kz2_of(c.materials[m], ct));
 }
-ART_HD cplx kz_of(const cplx* kz, const int stride, const int m, const double s2) {
-  return m < 0 ? cmk(sqrt(1.0 - s2), 0.0) : kz[m * stride];     // (1 - s2 = cos^2 t >= 0)
+ART_HD cplx kz_of(const cplx* kz, const int stride, const int m, const double ct) {
+  return m < 0 ? cmk(ct, 0.0) : kz[m * stride];     // (vacuum: kz / k = cos t >= 0)
 }
 ART_HD cplx eps_pick(const ArtCoating& c, const int m) {
   return m < 0 ? cmk(1.0, 0.0) : eps_of(c.materials[m]);
@@ -135,20 +138,20 @@ ART_HD void interface_rs_rp(const cplx qa, const cplx qb, const cplx ea, const c
   }
 }
 
-// rs, rp of coating c at sin^2 t = s2, wave number k (1/mm).  Everything is done in units of k: kz / k, k t, k sigma.
-ART_HD void coating_rs_rp(const ArtCoating& c, const double s2, const double k, cplx* kz, const int stride, cplx& rs,
+// rs, rp of coating c at cos t = ct, wave number k (1/mm).  Everything is done in units of k: kz / k, k t, k sigma.
+ART_HD void coating_rs_rp(const ArtCoating& c, const double ct, const double k, cplx* kz, const int stride, cplx& rs,
                           cplx& rp) {
   if (c.ideal) {
     rs = cmk(-1.0, 0.0);
     rp = cmk(1.0, 0.0);
     return;
   }
-  kz_table(c, s2, kz, stride);
+  kz_table(c, ct, kz, stride);
   const int L = c.n_layers;
   int mb = c.substrate;
   int ma = L > 0 ? c.layers[L - 1].material : -1;
-  cplx qb = kz_of(kz, stride, mb, s2);
-  cplx qa = kz_of(kz, stride, ma, s2);
+  cplx qb = kz_of(kz, stride, mb, ct);
+  cplx qa = kz_of(kz, stride, ma, ct);
   interface_rs_rp(qa, qb, eps_pick(c, ma), eps_pick(c, mb), k * c.roughness, rs, rp);
 #pragma unroll 1
   for (int l = L - 1; l >= 0; --l) {
@@ -156,7 +159,7 @@ ART_HD void coating_rs_rp(const ArtCoating& c, const double s2, const double k, 
     mb = ma;
     qb = qa;
     ma = l > 0 ? c.layers[l - 1].material : -1;
-    qa = kz_of(kz, stride, ma, s2);
+    qa = kz_of(kz, stride, ma, ct);
     cplx r_s, r_p;
     interface_rs_rp(qa, qb, eps_pick(c, ma), eps_pick(c, mb), k * ly.roughness, r_s, r_p);
     const double kt = 2.0 * k * ly.thickness;
@@ -178,18 +181,16 @@ ART_HD void perp_unit(const double dx, const double dy, const double dz, double&
   sx *= r; sy *= r; sz *= r;
 }
 
-// sin^2 t of the reflection from a to b: cos t = |b - a| / 2
-ART_HD double sin2_incidence(const double* a, const double* b) {
+// cos t of the reflection from a to b: |b - a| / 2 (accurate to a few ulp at any angle, grazing included)
+ART_HD double cos_incidence(const double* a, const double* b) {
   const double ux = b[0] - a[0], uy = b[1] - a[1], uz = b[2] - a[2];
-  const double c = 0.5 * sqrt(ux * ux + uy * uy + uz * uz);
-  return 1.0 - c * c;
+  return 0.5 * sqrt(ux * ux + uy * uy + uz * uz);
 }
-// The reflection frame of one element: s, p_in, p_out and sin^2 t from the unit directions before (a) and after (b)
+// The reflection frame of one element: s, p_in, p_out from the unit directions before (a) and after (b)
 struct Frame {
-  double s[3], pi[3], po[3], s2;
+  double s[3], pi[3], po[3];
 };
 ART_HD void reflection_frame(const double* a, const double* b, Frame& f) {
-  f.s2 = sin2_incidence(a, b);
   double sx = a[1] * b[2] - a[2] * b[1], sy = a[2] * b[0] - a[0] * b[2], sz = a[0] * b[1] - a[1] * b[0];
   const double m = sqrt(sx * sx + sy * sy + sz * sz);
   if (m < 1e-12) {

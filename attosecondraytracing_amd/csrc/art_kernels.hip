@@ -2179,7 +2179,7 @@ __global__ __launch_bounds__(kBlock, 4) void k_polarisation(const ArtPolarisatio
 #pragma unroll
       for (int q = 0; q < 3; ++q) { sd[q * kBlock] = din[q]; sd[(3 + q) * kBlock] = dout[q]; }
       artc::cplx rs, rp;
-      artc::coating_rs_rp(coats[c], artc::sin2_incidence(din, dout), jb.k, s_kz + threadIdx.x, kBlock, rs, rp);
+      artc::coating_rs_rp(coats[c], artc::cos_incidence(din, dout), jb.k, s_kz + threadIdx.x, kBlock, rs, rp);
       asm volatile("" ::: "memory");                      // (read them back: do not keep them in registers)
 #pragma unroll
       for (int q = 0; q < 3; ++q) { din[q] = sd[q * kBlock]; dout[q] = sd[(3 + q) * kBlock]; }

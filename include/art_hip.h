@@ -410,12 +410,12 @@ int art_wavefront(const ArtWavefrontJob* jobs_dev, const ArtWavefrontJob* jobs_h
  * ArtCoatingLayer, ArtCoating, ArtPolarisationJob, art_polarisation, art_polarisation_scratch_doubles).  One streaming
  * pass over a chain's existing history; the tracing kernels are not involved.  Time dependence exp(-i w t).
  * Per ray and reflecting element, with d_in, d_out the unit directions before and after it (views[e], views[e + 1]):
- *   n = normalize(d_out - d_in), cos t = |d_out - d_in| / 2, sin^2 t = 1 - cos^2 t
+ *   n = normalize(d_out - d_in), cos t = |d_out - d_in| / 2
  *   s = normalize(d_in x d_out) (|d_in x d_out| < 1e-12: normalize(d_in x a), a the lab axis of d_in's smallest
  *   |component|, the first of equals), p_in = d_in x s, p_out = d_out x s
  *   E' = rs (E.s) s + rp (E.p_in) p_out           (bilinear dot products, no conjugation)
  * A mask (coating index -1) leaves E unchanged.  rs, rp of a coating: N = n + i kappa per material, medium 0 vacuum,
- * layers 1..L top down, L + 1 the substrate, kz_j = k sqrt(N_j^2 - sin^2 t) with Im kz_j >= 0, k = 2 pi / wavelength;
+ * layers 1..L top down, L + 1 the substrate, kz_j = k sqrt(N_j^2 - 1 + cos^2 t) with Im kz_j >= 0, k = 2 pi / wavelength;
  *   r^s_{j,j+1} = (kz_j - kz_{j+1}) / (kz_j + kz_{j+1}),
  *   r^p_{j,j+1} = (N_{j+1}^2 kz_j - N_j^2 kz_{j+1}) / (N_{j+1}^2 kz_j + N_j^2 kz_{j+1}),
  *   both times exp(-2 kz_j kz_{j+1} sigma_{j,j+1}^2) (Nevot-Croce) where sigma > 0;

@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../attosecondraytracing_amd/csrc/art_device.h"
 #include "../../attosecondraytracing_amd/csrc/art_scene.h"
+#include "../../attosecondraytracing_amd/csrc/art_coating.h"
 
 #include <string.h>
 
@@ -262,6 +263,87 @@ void art_cpu_atan01(const double* q, int64_t n, double* out) {
 void art_cpu_prepare_element(const ArtElementDesc* in, ArtElementDesc* out) {
   *out = *in;
   art::prepare_element(*out);
+}
+
+// ------------------------------------------------------------------ coatings and polarisation (art_coating.h)
+// tests/test_coating_truth.py: the per-ray math of k_polarisation, run on host arrays.
+// rs, rp (re, im pairs) of coating c for the n reflections from a[3 i] to b[3 i], as k_polarisation forms them
+void art_cpu_coating_rs_rp(const ArtCoating* c, double k, const double* a, const double* b, int64_t n, double* rs,
+                           double* rp) {
+  artc::cplx kz[ART_COATING_MAX_MATERIALS];
+  for (int64_t i = 0; i < n; ++i) {
+    artc::cplx s, p;
+    artc::coating_rs_rp(*c, artc::cos_incidence(a + 3 * i, b + 3 * i), k, kz, 1, s, p);
+    rs[2 * i] = s.re; rs[2 * i + 1] = s.im;
+    rp[2 * i] = p.re; rp[2 * i + 1] = p.im;
+  }
+}
+
+// k_polarisation's per-ray pass for n rays through K elements: dirs[(e * n + i) * 3] the direction of ray i before
+// element e (e = K: after the last), coating[e] an index into coats (-1: a mask); pol: P (re, im per axis) or NULL
+// (unpolarised).  Out: T[i]; E0, E1 [i * 6] the output field(s) (re x, im x, re y, ...; E1 only when unpolarised).
+void art_cpu_polarisation_rays(const ArtCoating* coats, const int32_t* coating, int32_t K, const double* dirs,
+                               int64_t n, const double* pol, double k, double* T, double* E0, double* E1) {
+  artc::cplx kz[ART_COATING_MAX_MATERIALS];
+  for (int64_t i = 0; i < n; ++i) {
+    const double* din = dirs + 3 * i;
+    double er0[3], ei0[3], er1[3] = {0.0, 0.0, 0.0}, ei1[3] = {0.0, 0.0, 0.0};
+    if (pol) {
+      const double pr = pol[0] * din[0] + pol[2] * din[1] + pol[4] * din[2];
+      const double pi = pol[1] * din[0] + pol[3] * din[1] + pol[5] * din[2];
+      for (int q = 0; q < 3; ++q) {
+        er0[q] = pol[2 * q] - pr * din[q];
+        ei0[q] = pol[2 * q + 1] - pi * din[q];
+      }
+      const double m = sqrt(er0[0] * er0[0] + er0[1] * er0[1] + er0[2] * er0[2] + ei0[0] * ei0[0] + ei0[1] * ei0[1] +
+                            ei0[2] * ei0[2]);
+      for (int q = 0; q < 3; ++q) { er0[q] /= m; ei0[q] /= m; }
+    } else {
+      artc::perp_unit(din[0], din[1], din[2], er0[0], er0[1], er0[2]);
+      er1[0] = din[1] * er0[2] - din[2] * er0[1];
+      er1[1] = din[2] * er0[0] - din[0] * er0[2];
+      er1[2] = din[0] * er0[1] - din[1] * er0[0];
+      for (int q = 0; q < 3; ++q) ei0[q] = 0.0;
+    }
+    for (int e = 0; e < K; ++e) {
+      const double* a = dirs + 3 * ((int64_t)e * n + i);
+      const double* b = dirs + 3 * ((int64_t)(e + 1) * n + i);
+      if (coating[e] < 0) continue;
+      artc::cplx rs, rp;
+      artc::coating_rs_rp(coats[coating[e]], artc::cos_incidence(a, b), k, kz, 1, rs, rp);
+      artc::Frame f;
+      artc::reflection_frame(a, b, f);
+      artc::prt_step(f, rs, rp, er0, ei0);
+      if (!pol) artc::prt_step(f, rs, rp, er1, ei1);
+    }
+    const double T0 = (er0[0] * er0[0] + er0[1] * er0[1] + er0[2] * er0[2]) + (ei0[0] * ei0[0] + ei0[1] * ei0[1] + ei0[2] * ei0[2]);
+    const double T1 = (er1[0] * er1[0] + er1[1] * er1[1] + er1[2] * er1[2]) + (ei1[0] * ei1[0] + ei1[1] * ei1[1] + ei1[2] * ei1[2]);
+    T[i] = pol ? T0 : 0.5 * (T0 + T1);
+    for (int q = 0; q < 3; ++q) {
+      E0[6 * i + 2 * q] = er0[q]; E0[6 * i + 2 * q + 1] = ei0[q];
+      if (!pol) { E1[6 * i + 2 * q] = er1[q]; E1[6 * i + 2 * q + 1] = ei1[q]; }
+    }
+  }
+}
+
+// the scalar helpers of art_coating.h, n values each (complex values as re, im pairs)
+void art_cpu_exp_cw(const double* x, int64_t n, double* out) {
+  for (int64_t i = 0; i < n; ++i) out[i] = artc::exp_cw(x[i]);
+}
+void art_cpu_sincos_cw(const double* x, int64_t n, double* sn, double* cs) {
+  for (int64_t i = 0; i < n; ++i) artc::sincos_cw(x[i], sn[i], cs[i]);
+}
+void art_cpu_csqrt_up(const double* z, int64_t n, double* out) {
+  for (int64_t i = 0; i < n; ++i) {
+    const artc::cplx w = artc::csqrt_up(artc::cmk(z[2 * i], z[2 * i + 1]));
+    out[2 * i] = w.re; out[2 * i + 1] = w.im;
+  }
+}
+void art_cpu_cdiv(const double* a, const double* b, int64_t n, double* out) {
+  for (int64_t i = 0; i < n; ++i) {
+    const artc::cplx w = artc::cdiv(artc::cmk(a[2 * i], a[2 * i + 1]), artc::cmk(b[2 * i], b[2 * i + 1]));
+    out[2 * i] = w.re; out[2 * i + 1] = w.im;
+  }
 }
 
 }  // extern "C"

@@ -7,17 +7,24 @@ def index_of(v):
     return complex(1 - v[0], v[1]) if isinstance(v, (tuple, list)) else complex(v)
 
 
-def parratt(media, thick, sigma, s2, k):
+def parratt(media, thick, sigma, s2, k, cos=None):
     """rs, rp of media [N_0 = vacuum, N_1 .. N_L, N_sub] (thick[j] of medium j, 1 <= j <= L; sigma[j] of interface
-    j, j + 1) at sin^2 t = s2 (array), wave number k."""
-    s2 = np.asarray(s2, dtype=float)
+    j, j + 1) at sin^2 t = s2 (array), wave number k.  With `cos` (array of cos t) s2 is not used: kz / k =
+    sqrt((N - 1)(N + 1) + cos^2 t) keeps every digit at grazing incidence, where 1 - cos^2 t would lose them."""
+    if cos is not None:
+        c = np.asarray(cos, dtype=float)
+        q2 = [(complex(N) - 1) * (complex(N) + 1) + (c * c).astype(complex) for N in media]
+    else:
+        s2 = np.asarray(s2, dtype=float)
+        q2 = [complex(N) ** 2 - s2.astype(complex) for N in media]
     kz = []
-    for N in media:
-        q = np.sqrt(complex(N) ** 2 - s2.astype(complex))
+    for v in q2:
+        q = np.sqrt(v)
         kz.append(k * np.where(q.imag < 0, -q, q))
+    shape = np.shape(q2[0])
     L = len(media) - 2
-    Rs = np.zeros(s2.shape, complex)
-    Rp = np.zeros(s2.shape, complex)
+    Rs = np.zeros(shape, complex)
+    Rp = np.zeros(shape, complex)
     for j in range(L, -1, -1):
         e0, e1 = complex(media[j]) ** 2, complex(media[j + 1]) ** 2
         rs = (kz[j] - kz[j + 1]) / (kz[j] + kz[j + 1])
@@ -31,14 +38,15 @@ def parratt(media, thick, sigma, s2, k):
     return Rs, Rp
 
 
-def coating_rs_rp(c, s2, k):
-    """rs, rp of a coating.Coating (its fields only) at sin^2 t = s2."""
+def coating_rs_rp(c, s2, k, cos=None):
+    """rs, rp of a coating.Coating (its fields only) at sin^2 t = s2, or at cos t = cos (then s2 is not used)."""
     if c.is_ideal:
-        return np.full(np.shape(s2), -1.0 + 0j), np.full(np.shape(s2), 1.0 + 0j)
+        shape = np.shape(s2 if cos is None else cos)
+        return np.full(shape, -1.0 + 0j), np.full(shape, 1.0 + 0j)
     media = [1.0] + [ly[0] for ly in c.layers] + [c.substrate]
     thick = [0.0] + [ly[1] for ly in c.layers] + [0.0]
     sigma = [ly[2] for ly in c.layers] + [c.roughness]
-    return parratt(media, thick, sigma, s2, k)
+    return parratt(media, thick, sigma, s2, k, cos)
 
 
 def perp_unit(d):
@@ -57,9 +65,7 @@ def propagate(dirs, coats, E, k):
         a, b = dirs[e], dirs[e + 1]
         if c is None:
             continue
-        cos = np.linalg.norm(b - a, axis=1) / 2
-        s2 = 1 - cos * cos
-        rs, rp = coating_rs_rp(c, s2, k)
+        rs, rp = coating_rs_rp(c, None, k, cos=np.linalg.norm(b - a, axis=1) / 2)
         s = np.cross(a, b)
         m = np.linalg.norm(s, axis=1)
         near = m < 1e-12
