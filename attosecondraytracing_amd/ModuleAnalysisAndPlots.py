@@ -126,6 +126,13 @@ def PulseAtFocus(RayListAnalysed, Detector, DeltaFT, Size=None, Pixels=64):
     return _plots.PulseAtFocus(RayListAnalysed, Detector, DeltaFT, Size, Pixels)
 
 
+def CoatedPulseAtFocus(OpticalChain, Coatings, Detector, DeltaFT, Polarisation, Size=None, Pixels=64, Centre=None):
+    """The pulse at focus behind the chain's coatings (OpticalChain.get_FocalPulse): sum_c |A_c|^2 through the peak in
+    X and Y, and its temporal profile against the one an ideal coating gives and the Fourier limit of DeltaFT (fs)."""
+    from . import _plots
+    return _plots.CoatedPulseAtFocus(OpticalChain, Coatings, Detector, DeltaFT, Polarisation, Size, Pixels, Centre)
+
+
 def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pixels=64):
     """Space-time Strehl ratio and on-peak duration of the pulse against the detector shift (all planes in one call)."""
     from . import _plots

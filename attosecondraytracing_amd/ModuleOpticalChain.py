@@ -158,6 +158,28 @@ class OpticalChain:
         from . import polarisation
         return polarisation.polarisation(self, Coatings, Polarisation, Detector, Wavelength, PerRay)
 
+    def get_FocalPulse(self, Coatings, Detector, DeltaFT, Polarisation, Size=None, Pixels=64, Centre=None, Shifts=None,
+                       Wavelength=None, RefPath=None, Spectrum=None, TimeWindow=None, Times=256, ScratchBytes=None):
+        """The space-time VECTOR field of a broadband pulse at focus behind the chain's coatings
+        (vector_pulse.VectorFocalPulse): Detector.get_FocalPulse with, per ray and frequency, the complex field that
+        get_Polarisation carries through the mirrors -- reflectance, reflection phase (group delay, chirp) and s / p
+        mixing, with coating.Material tables evaluated at every frequency.  Coatings and Polarisation (required, a
+        complex lab-frame 3-vector) as in get_Polarisation; every other argument as in Detector.get_FocalPulse;
+        ScratchBytes bounds the device scratch (the frequencies are then processed in blocks; the result does not
+        depend on it)."""
+        from . import vector_pulse
+        return vector_pulse.vector_focal_pulse(self, Coatings, Detector, DeltaFT, Polarisation, Size, Pixels, Centre,
+                                               Shifts, Wavelength, RefPath, Spectrum, TimeWindow, Times, ScratchBytes)
+
+    def get_VectorFocalField(self, Coatings, Detector, Polarisation, Size=None, Pixels=128, Centre=None, Shifts=None,
+                             Wavelength=None, RefPath=None):
+        """The vector focal field at one wavelength behind the chain's coatings (vector_pulse.VectorFocalField):
+        Detector.get_FocalField with get_Polarisation's complex field per ray as the amplitude, in the detector's
+        components (e1, e2, normal)."""
+        from . import vector_pulse
+        return vector_pulse.vector_focal_field(self, Coatings, Detector, Polarisation, Size, Pixels, Centre, Shifts,
+                                               Wavelength, RefPath)
+
     def _output_for(self, key, kwargs):
         """get_output_rays for a cache key the caller has computed already (trace_chain_list: once per chain)."""
         if key != self._last_key:

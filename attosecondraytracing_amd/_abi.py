@@ -219,6 +219,24 @@ class ArtPolarisationJob(C.Structure):
     ]
 
 
+ART_FOCAL_VECTOR_SCRATCH_DEFAULT = 1 << 29
+
+
+class ArtFocalVectorSpectrumDesc(C.Structure):
+    _fields_ = [
+        ("s", ArtFocalSpectrumDesc),
+        ("views", C.c_void_p),
+        ("coating", C.c_int32 * ART_POLARISATION_MAX_ELEMS),
+        ("n_elems", C.c_int32),
+        ("n_coatings", C.c_int32),
+        ("n", C.c_int64),
+        ("pol", C.c_double * 6),
+        ("w", C.c_void_p),
+        ("materials", C.c_void_p),
+        ("scratch_bound", C.c_int64),
+    ]
+
+
 # name -> (restype, argtypes); the loader checks every symbol exists (tests/test_abi.py does too)
 PROTOTYPES = {
     "art_abi_version": (C.c_int, []),
@@ -258,6 +276,10 @@ PROTOTYPES = {
     "art_polarisation_scratch_doubles": (C.c_int64, [C.POINTER(ArtPolarisationJob), C.c_int32]),
     "art_polarisation": (C.c_int, [C.c_void_p, C.POINTER(ArtPolarisationJob), C.c_int32, C.c_void_p,
                                    C.POINTER(ArtCoating), C.c_int32, C.c_void_p, C.c_void_p]),
+    "art_focal_vector_spectrum_scratch_doubles": (C.c_int64, [C.POINTER(ArtFocalVectorSpectrumDesc)]),
+    "art_focal_vector_spectrum": (C.c_int, [C.POINTER(ArtFocalVectorSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p,
+                                            C.POINTER(ArtCoating), C.POINTER(ArtCoatingMaterial), C.c_void_p,
+                                            C.c_void_p, C.c_void_p]),
     "art_reduce_scratch_doubles": (C.c_int64, []),
     "art_detector_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

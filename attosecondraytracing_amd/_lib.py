@@ -528,6 +528,40 @@ class HipBackend:
                                                self.stream_ptr()), "art_polarisation")
         return out
 
+    def focal_vector_tables(self, vdesc, views, coatings, materials):
+        """Uploads the tables of art_focal_vector_spectrum and points vdesc at them (`views`, `materials`, `n_coatings`).
+        views: the HOST ctypes array of the chain's K + 1 views; coatings: a list of ArtCoating; materials: float64
+        NumPy [nk, len(coatings), ART_COATING_MAX_MATERIALS, 2] (n, kappa).  Returns the call's other table arguments
+        (coatings_dev, coatings_host, materials_host); the caller keeps them alive until the call has been made."""
+        nk, nc = vdesc.s.nk, len(coatings)
+        mats = np.ascontiguousarray(materials, dtype=np.float64)
+        if mats.shape != (nk, nc, _abi.ART_COATING_MAX_MATERIALS, 2):
+            raise ValueError(f"materials must be [nk, coatings, {_abi.ART_COATING_MAX_MATERIALS}, 2]")
+        blob = bytes(views) + b"".join(bytes(k) for k in coatings) + mats.tobytes()
+        dev = self._upload_table((C.c_char * len(blob)).from_buffer_copy(blob), "focal vector spectrum")
+        vdesc.views = dev.data_ptr()
+        vdesc.n_coatings = nc
+        cdev = dev.data_ptr() + C.sizeof(views) if nc else None
+        vdesc.materials = dev.data_ptr() + C.sizeof(views) + nc * C.sizeof(_abi.ArtCoating) if nc else None
+        carr = (_abi.ArtCoating * max(nc, 1))(*coatings)
+        marr = (_abi.ArtCoatingMaterial * max(mats.size // 2, 1)).from_buffer_copy(mats.tobytes() or bytes(16))
+        return cdev, carr, marr
+
+    def focal_vector_spectrum(self, vdesc, views, coatings, materials):
+        """art_focal_vector_spectrum on the current stream (arguments as focal_vector_tables): a new device complex128
+        tensor [planes, nk, 3, ny, nx] (scratch reused per stream)."""
+        f = vdesc.s.f
+        field = torch.empty((f.planes, vdesc.s.nk, 3, f.ny, f.nx), dtype=torch.complex128, device=self.device)
+        cdev, carr, marr = self.focal_vector_tables(vdesc, views, coatings, materials)
+        ns = self.fn["art_focal_vector_spectrum_scratch_doubles"](C.byref(vdesc))
+        if ns < 0:
+            raise ArtError(f"art_focal_vector_spectrum_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self.scratch("focal vector", ns, torch.float64)
+        self.check(self.fn["art_focal_vector_spectrum"](C.byref(vdesc), C.byref(views[vdesc.n_elems]), cdev, carr, marr,
+                                                        scratch.data_ptr(), field.data_ptr(), self.stream_ptr()),
+                   "art_focal_vector_spectrum")
+        return field
+
     def analyse_bundles(self, jobs, n):
         """art_analyse_bundles for a list of ArtAnalysisJob (host structs): uploads the job table, enqueues the four
         launches and returns the DEVICE tensor out[len(jobs), 64] -- nothing is read back here."""

@@ -458,6 +458,50 @@ def PulseAtFocus(RayListAnalysed, Detector, DeltaFT, Size=None, Pixels=64):
     return fig
 
 
+def CoatedPulseAtFocus(OpticalChain, Coatings, Detector, DeltaFT, Polarisation, Size=None, Pixels=64, Centre=None):
+    """Three panels of the pulse at focus behind the chain's coatings (OpticalChain.get_FocalPulse): sum_c |A_c|^2 as
+    I(X, t) along the row of the space-time peak and I(Y, t) along its column (µm, fs), and the on-peak temporal
+    profile against the one Coating.ideal() on every mirror gives on the same pixel (both over the ideal maximum, so
+    the loss shows) and the Fourier-limited Gaussian of DeltaFT."""
+    from .coating import Coating
+    plt = _plt()
+    kw = dict(Size=Size, Pixels=Pixels, Centre=Centre)
+    p = OpticalChain.get_FocalPulse(Coatings, Detector, DeltaFT, Polarisation, **kw)
+    ideal = OpticalChain.get_FocalPulse(Coating.ideal(), Detector, DeltaFT, Polarisation, RefPath=p.ref_path,
+                                        TimeWindow=p.time_window, Times=len(p.t), **kw)
+    I = p.intensity[0]
+    n, l, j = np.unravel_index(int(np.argmax(I)), I.shape)
+    t = p.t
+    dt = 0.5 * (t[1] - t[0]) if len(t) > 1 else 0.5
+
+    def extent(a):
+        da = 0.5 * (a[1] - a[0]) if len(a) > 1 else 0.5
+        return ((a[0] - da) * 1e3, (a[-1] + da) * 1e3, t[0] - dt, t[-1] + dt)
+
+    plt.ion()
+    fig, (a1, a2, a3) = plt.subplots(1, 3, figsize=(15, 4.5))
+    for ax, img, axis, name in ((a1, I[:, l, :], p.x, "X"), (a2, I[:, :, j], p.y, "Y")):
+        im = ax.imshow(img, origin="lower", extent=extent(axis), aspect="auto", interpolation="nearest")
+        fig.colorbar(im, ax=ax).set_label("Intensity (arb.u.)")
+        ax.set_xlabel(f"{name} (µm)")
+        ax.set_ylabel("t (fs)")
+        ax.set_title(f"sum |A_c|^2 ({name}, t) through the peak")
+    ref = ideal.intensity[0][:, l, j]
+    top = max(ref.max(), np.finfo(float).tiny)
+    peak_t = ideal.t[int(np.argmax(ref))]
+    a3.plot(t, I[:, l, j] / top, label=f"coated, FWHM {p.duration[0]:.3g} fs")
+    a3.plot(t, ref / top, label=f"ideal coating, FWHM {ideal.duration[0]:.3g} fs")
+    a3.plot(t, np.exp(-4 * np.log(2) * (t - peak_t) ** 2 / DeltaFT ** 2), "k--", label=f"Fourier limit, {DeltaFT:.3g} fs")
+    a3.set_xlabel("t (fs)")
+    a3.set_ylabel("Intensity / ideal maximum")
+    a3.legend(loc="upper right")
+    a3.set_title("Pulse at {:.3f} mm, Strehl {:.3g} (ideal coating {:.3g})".format(Detector.get_distance(), p.strehl[0],
+                                                                                 ideal.strehl[0]))
+    fig._art_pulse, fig._art_ideal = p, ideal
+    plt.show()
+    return fig
+
+
 def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pixels=64):
     """Space-time Strehl ratio and on-peak duration (fs) of the pulse against the detector shift (mm,
     Detector.shiftByDistance's sign); all planes and frequencies are summed in one device call."""

@@ -115,15 +115,21 @@ ART_HD cplx kz2_of(const ArtCoatingMaterial& m, const double ct) {
 
 // kz / k of every material of a coating, into kz[m * stride]: the caller's per-lane table (the kernel keeps it in LDS,
 // one column per lane, so a wave-uniform material index is one read; no selects).  Vacuum (index -1) is formed where used.
+// The `_at` forms take the optical constants from `mats` (n_materials entries) in place of c.materials: a dispersive
+// coating is one ArtCoating (layers, thicknesses, roughnesses) and one material table per frequency.
+ART_HD void kz_table_at(const ArtCoating& c, const ArtCoatingMaterial* mats, const double ct, cplx* kz, const int stride) {
+  for (int m = 0; m < c.n_materials; ++m) kz[m * stride] = csqrt_up(kz2_of(mats[m], ct));
+}
 ART_HD void kz_table(const ArtCoating& c, const double ct, cplx* kz, const int stride) {
-  for (int m = 0; m < c.n_materials; ++m) kz[m * stride] = csqrt_up(kz2_of(c.materials[m], ct));
+  kz_table_at(c, c.materials, ct, kz, stride);
 }
 ART_HD cplx kz_of(const cplx* kz, const int stride, const int m, const double ct) {
   return m < 0 ? cmk(ct, 0.0) : kz[m * stride];     // (vacuum: kz / k = cos t >= 0)
 }
-ART_HD cplx eps_pick(const ArtCoating& c, const int m) {
-  return m < 0 ? cmk(1.0, 0.0) : eps_of(c.materials[m]);
+ART_HD cplx eps_pick_at(const ArtCoatingMaterial* mats, const int m) {
+  return m < 0 ? cmk(1.0, 0.0) : eps_of(mats[m]);
 }
+ART_HD cplx eps_pick(const ArtCoating& c, const int m) { return eps_pick_at(c.materials, m); }
 
 // the interface between material slots a (above) and b (below); qa, qb = kz / k; sigk = k sigma (dimensionless)
 ART_HD void interface_rs_rp(const cplx qa, const cplx qb, const cplx ea, const cplx eb, const double sigk, cplx& rs,
@@ -138,21 +144,23 @@ ART_HD void interface_rs_rp(const cplx qa, const cplx qb, const cplx ea, const c
   }
 }
 
-// rs, rp of coating c at cos t = ct, wave number k (1/mm).  Everything is done in units of k: kz / k, k t, k sigma.
-ART_HD void coating_rs_rp(const ArtCoating& c, const double ct, const double k, cplx* kz, const int stride, cplx& rs,
-                          cplx& rp) {
+// rs, rp of coating c with the optical constants `mats` at cos t = ct, wave number k (1/mm).  Everything is done in
+// units of k: kz / k, k t, k sigma.  ct (and the frame of prt_step) belong to the ray and the element, not to k: a
+// caller that runs many frequencies forms them once and calls this per frequency with that frequency's k and mats.
+ART_HD void coating_rs_rp_at(const ArtCoating& c, const ArtCoatingMaterial* mats, const double ct, const double k,
+                             cplx* kz, const int stride, cplx& rs, cplx& rp) {
   if (c.ideal) {
     rs = cmk(-1.0, 0.0);
     rp = cmk(1.0, 0.0);
     return;
   }
-  kz_table(c, ct, kz, stride);
+  kz_table_at(c, mats, ct, kz, stride);
   const int L = c.n_layers;
   int mb = c.substrate;
   int ma = L > 0 ? c.layers[L - 1].material : -1;
   cplx qb = kz_of(kz, stride, mb, ct);
   cplx qa = kz_of(kz, stride, ma, ct);
-  interface_rs_rp(qa, qb, eps_pick(c, ma), eps_pick(c, mb), k * c.roughness, rs, rp);
+  interface_rs_rp(qa, qb, eps_pick_at(mats, ma), eps_pick_at(mats, mb), k * c.roughness, rs, rp);
 #pragma unroll 1
   for (int l = L - 1; l >= 0; --l) {
     const ArtCoatingLayer& ly = c.layers[l];
@@ -161,13 +169,18 @@ ART_HD void coating_rs_rp(const ArtCoating& c, const double ct, const double k, 
     ma = l > 0 ? c.layers[l - 1].material : -1;
     qa = kz_of(kz, stride, ma, ct);
     cplx r_s, r_p;
-    interface_rs_rp(qa, qb, eps_pick(c, ma), eps_pick(c, mb), k * ly.roughness, r_s, r_p);
+    interface_rs_rp(qa, qb, eps_pick_at(mats, ma), eps_pick_at(mats, mb), k * ly.roughness, r_s, r_p);
     const double kt = 2.0 * k * ly.thickness;
     const cplx X = cexp(cmk(-qb.im * kt, qb.re * kt));
     const cplx Xs = cmul(rs, X), Xp = cmul(rp, X);
     rs = cdiv(cadd(r_s, Xs), cadd(cmk(1.0, 0.0), cmul(r_s, Xs)));
     rp = cdiv(cadd(r_p, Xp), cadd(cmk(1.0, 0.0), cmul(r_p, Xp)));
   }
+}
+// the same with the coating's own (constant) optical constants
+ART_HD void coating_rs_rp(const ArtCoating& c, const double ct, const double k, cplx* kz, const int stride, cplx& rs,
+                          cplx& rp) {
+  coating_rs_rp_at(c, c.materials, ct, k, kz, stride, rs, rp);
 }
 
 // normalize(d x a), a the lab axis of d's smallest |component| (the first of equals): a unit vector perpendicular to d
@@ -215,6 +228,21 @@ ART_HD void prt_step(const Frame& f, const cplx rs, const cplx rp, double* er, d
     er[q] = a.re * f.s[q] + b.re * f.po[q];
     ei[q] = a.im * f.s[q] + b.im * f.po[q];
   }
+}
+
+// The polarised input state of a ray: E0 = P - (P.d) d over its norm (P = pol: re x, im x, re y, im y, re z, im z; d the
+// source direction).  Returns |P - (P.d) d| (0: P is parallel to d and E0 is not finite).
+ART_HD double transverse_state(const double* P, const double* d, double* er, double* ei) {
+  const double pr = P[0] * d[0] + P[2] * d[1] + P[4] * d[2], pi = P[1] * d[0] + P[3] * d[1] + P[5] * d[2];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    er[q] = P[2 * q] - pr * d[q];
+    ei[q] = P[2 * q + 1] - pi * d[q];
+  }
+  const double m = sqrt(er[0] * er[0] + er[1] * er[1] + er[2] * er[2] + ei[0] * ei[0] + ei[1] * ei[1] + ei[2] * ei[2]);
+#pragma unroll
+  for (int q = 0; q < 3; ++q) { er[q] /= m; ei[q] /= m; }
+  return m;
 }
 
 }  // namespace artc

@@ -2255,6 +2255,169 @@ __global__ __launch_bounds__(kFoldBlock) void k_polarisation_fold(const ArtPolar
   if (threadIdx.x == 0) jb.out[q] = (cnt == 0.0 || (q == 10 && !jb.polarised)) ? 0.0 : v;
 }
 
+// ------------------------------------------------------------------------------------------- vector focal spectrum
+// art_focal_vector_spectrum (include/art_hip.h): art_focal_spectrum's sum with a complex amplitude per (ray, wavenumber,
+// component), the field of art_polarisation carried through coatings whose optical constants depend on the wavenumber.
+// k_vecspec_rays: grid (tiles of 256 slots, wavenumbers of the block), one ray per lane, k_polarisation's pass over the
+// history for a polarised input at k_j with the material table of (j, coating); it writes sqrt(w) (E . u_c) for
+// u = e1, e2, n of the detector as 6 rows of `amp` per wavenumber (re, im per component; 0 for a dead slot).  The frame
+// and cos t of an element do not depend on k, but a lane that kept them for all K elements, or the fields of several
+// wavenumbers, would not fit the 128 registers of four workgroups per CU: they are formed again per wavenumber, a few
+// hundred operations beside the element's Parratt steps (~150 each).  Views, coatings and materials are wave-uniform:
+// scalar loads.
+// k_vecspec_field is k_focal_spectrum_field with (plane, wavenumber, component) on the grid's y dimension and the row
+// phasor W = (a . u_c) exp(i ...); a kernel of its own for the reason given above k_focal_spectrum_prep, whose rows it
+// reads.  Partials are laid out [plane][slice][wavenumber of the block][component] so that k_focal_fold folds a plane's
+// slices straight into its place in the field.
+struct VecSpecArg {
+  const ArtBundleView* views;
+  const double* w;
+  double pol[6], u[9];          // P; e1, e2, n of the detector
+  double k0, dk;
+  int64_t n, stride;
+  int32_t n_elems, n_coatings, j0, nkb;
+  int32_t coating[ART_POLARISATION_MAX_ELEMS];
+};
+
+__global__ __launch_bounds__(kBlock, 4) void k_vecspec_rays(const VecSpecArg a, const ArtCoating* __restrict__ coats,
+                                                         const ArtCoatingMaterial* __restrict__ mats,
+                                                         double* __restrict__ amp) {
+  __shared__ artc::cplx s_kz[ART_COATING_MAX_MATERIALS * kBlock];   // kz / k per material, one column per lane
+  __shared__ double s_dir[6 * kBlock];                                     // d_in, d_out, one column per lane
+  const int jj = blockIdx.y, j = a.j0 + jj;
+  const double k = focal_kj(a.k0, j, a.dk);
+  const int64_t n = a.n;
+  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned nb8 = (unsigned)(n * 8), nb1 = (unsigned)n;   // n <= 2^28 (checked by the host)
+  const int K = a.n_elems;
+  const ArtBundleView* views = a.views;
+  const bool live = __builtin_amdgcn_raw_buffer_load_b8(rsrc_of(pol_alive(views, K), nb1), (int)i, 0, ART_LD_AUX) != 0;
+  const unsigned o8 = live ? i * 8u : kDropOffset;
+  const double w = a.w ? ld_f64(rsrc_of(const_cast<double*>(a.w), nb8), o8) : 1.0;
+  double din[3], er[3], ei[3];
+  pol_dirs(views, 0, nb8, o8, din);
+  artc::transverse_state(a.pol, din, er, ei);
+  for (int e = 0; e < K; ++e) {
+    double dout[3];
+    pol_dirs(views, e + 1, nb8, o8, dout);
+    const int c = a.coating[e];
+    if (c >= 0) {                                         // (a mask leaves E unchanged)
+      // the two directions wait in LDS while the coefficients are formed (the Parratt loop needs every register)
+      double* sd = s_dir + threadIdx.x;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) { sd[q * kBlock] = din[q]; sd[(3 + q) * kBlock] = dout[q]; }
+      artc::cplx rs, rp;
+      artc::coating_rs_rp_at(coats[c], mats + ((int64_t)j * a.n_coatings + c) * ART_COATING_MAX_MATERIALS,
+                             artc::cos_incidence(din, dout), k, s_kz + threadIdx.x, kBlock, rs, rp);
+      asm volatile("" ::: "memory");                      // (read them back: do not keep them in registers)
+#pragma unroll
+      for (int q = 0; q < 3; ++q) { din[q] = sd[q * kBlock]; dout[q] = sd[(3 + q) * kBlock]; }
+      artc::Frame f;                                      // (formed after the coefficients: fewer registers live)
+      artc::reflection_frame(din, dout, f);
+      artc::prt_step(f, rs, rp, er, ei);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) din[q] = dout[q];
+  }
+  if ((int64_t)i >= n) return;
+  const double sw = live ? sqrt(w) : 0.0;                 // (k_focal_spectrum_prep's amplitude)
+  double* row = amp + (int64_t)jj * 6 * a.stride + i;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double* u = a.u + 3 * c;
+    const double re = er[0] * u[0] + er[1] * u[1] + er[2] * u[2], im = ei[0] * u[0] + ei[1] * u[1] + ei[2] * u[2];
+    row[(2 * c) * a.stride] = live ? sw * re : 0.0;       // a dead slot's values are unspecified: selected away
+    row[(2 * c + 1) * a.stride] = live ? sw * im : 0.0;
+  }
+}
+
+// blockIdx.y = ((q * nkb + jj) * 3 + c) (plane q, wavenumber j0 + jj of the block, component c); amps: the rows of
+// k_vecspec_rays; out (double2): plane q at q * plane_stride, slice at slice * slice_stride, then [jj][c][ny][nx]
+__global__ __launch_bounds__(kBlock) void k_vecspec_field(const FocalArg a, const double dk, const int j0, const int nkb,
+                                                          const double* __restrict__ rows,
+                                                          const double* __restrict__ amps, const int64_t plane_stride,
+                                                          const int64_t slice_stride, double* __restrict__ out) {
+  __shared__ double2 sU[kFocalChunk][kFocalTile];     // exp(i X_j k d.e1)
+  __shared__ double2 sW[kFocalChunk][kFocalTile];     // (a . u_c) exp(i (base + s_q k d.n + Y_l k d.e2))
+  const int qjc = blockIdx.y, qj = qjc / 3, comp = qjc - 3 * qj, q = qj / nkb, jj = qj - q * nkb, slice = blockIdx.z;
+  const double kj = focal_kj(a.k, j0 + jj, dk);
+  const int tx0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * kFocalTile, ty0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * kFocalTile;
+  const int t = threadIdx.x, lx = t % kFocalLanes, ly = t / kFocalLanes;
+  const int64_t st = a.stride, r0 = (int64_t)slice * a.per_slice;
+  const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
+  const double sh = a.shift[q];
+  const double* am = amps + ((int64_t)jj * 6 + 2 * comp) * st;
+  // staging role of this lane: rows (W) or columns (U), ray sr of the chunk, segment sg of the tile
+  const bool colw = t < kBlock / 2;
+  const int sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg), sg = t % (kFocalTile / kFocalSeg);
+  double acc_re[kFocalMicro][kFocalMicro], acc_im[kFocalMicro][kFocalMicro];
+#pragma unroll
+  for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+    for (int u = 0; u < kFocalMicro; ++u) acc_re[v][u] = acc_im[v][u] = 0.0;
+
+  for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
+    const int64_t r = c0 + sr;
+    const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
+    double ph, a_re, a_im, s_re, s_im;
+    int p0;
+    if (colw) {
+      p0 = tx0 + sg * kFocalSeg;
+      const double ka = focal_mul(kj, in ? rows[2 * st + r] : 0.0);
+      ph = ka * (a.x0 + (double)p0 * a.dx);
+      a_re = 1.0; a_im = 0.0;
+      sincos(focal_mul(ka, a.dx), &s_im, &s_re);
+    } else {
+      p0 = ty0 + sg * kFocalSeg;
+      const double base = focal_mul(kj, in ? rows[st + r] : 0.0), kb = focal_mul(kj, in ? rows[3 * st + r] : 0.0),
+                   kc = focal_mul(kj, in ? rows[4 * st + r] : 0.0);
+      ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
+      a_re = in ? am[r] : 0.0; a_im = in ? am[st + r] : 0.0;
+      sincos(focal_mul(kb, a.dy), &s_im, &s_re);
+    }
+    double sn, cs;
+    sincos(ph, &sn, &cs);
+    double z_re = a_re * cs - a_im * sn, z_im = a_re * sn + a_im * cs;
+    double2* dst = colw ? &sU[sr][sg * kFocalSeg] : &sW[sr][sg * kFocalSeg];
+#pragma unroll
+    for (int m = 0; m < kFocalSeg; ++m) {
+      dst[m] = make_double2(z_re, z_im);
+      const double n_re = fma(z_re, s_re, -(z_im * s_im));
+      z_im = fma(z_re, s_im, z_im * s_re);
+      z_re = n_re;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int rr = 0; rr < kFocalChunk; ++rr) {
+      double2 uu[kFocalMicro], vv[kFocalMicro];
+#pragma unroll
+      for (int i = 0; i < kFocalMicro; ++i) {
+        uu[i] = sU[rr][lx + kFocalLanes * i];
+        vv[i] = sW[rr][ly + kFocalLanes * i];
+      }
+#pragma unroll
+      for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+        for (int u = 0; u < kFocalMicro; ++u) {
+          acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
+          acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
+          acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
+          acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
+        }
+    }
+    __syncthreads();
+  }
+  double2* o = reinterpret_cast<double2*>(out) + (int64_t)q * plane_stride + (int64_t)slice * slice_stride +
+               (int64_t)(jj * 3 + comp) * a.ny * a.nx;
+#pragma unroll
+  for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+    for (int u = 0; u < kFocalMicro; ++u) {
+      const int l = ty0 + ly + kFocalLanes * v, j = tx0 + lx + kFocalLanes * u;
+      if (l < a.ny && j < a.nx) o[(int64_t)l * a.nx + j] = make_double2(acc_re[v][u], acc_im[v][u]);
+    }
+}
+
 template <bool HAS_W>
 __global__ __launch_bounds__(kBlock) void k_moments_partial(const uint8_t* alive, const double* X, const double* Y,
                                                             const double* opl, const double* w, const int64_t n,
@@ -3753,6 +3916,122 @@ int art_polarisation(const ArtPolarisationJob* jobs_dev, const ArtPolarisationJo
   hipLaunchKernelGGL(k_polarisation_fold, dim3(ART_POLARISATION_DOUBLES, n_jobs), dim3(kFoldBlock), 0, s, jobs_dev, per_job,
                      (const double*)scratch);
   return launched("art_polarisation launch");
+}
+
+// the wavenumber blocks of art_focal_vector_spectrum: slices S of the rays (never from the block: the same bytes for any),
+// wavenumbers per block nkb, doubles of scratch
+struct VecSpecPlan {
+  int S, nkb;
+  int64_t stride, total;
+};
+static VecSpecPlan vecspec_plan(const ArtFocalVectorSpectrumDesc* d) {
+  const ArtFocalDesc& f = d->s.f;
+  VecSpecPlan p;
+  // (the grid rows of ONE wavenumber: a block may hold no more, and a count taken from all nk leaves a launch of a
+  // block with about as many workgroups as the machine has places for, so that a few stragglers run a round alone)
+  p.S = focal_slices(f.nx, f.ny, f.planes * 3, d->n);
+  p.stride = focal_stride(d->n);
+  p.nkb = 1;
+  p.total = 0;
+  if (d->n == 0) return p;
+  const int64_t rows = (int64_t)kFocalSpecRows * p.stride;
+  const int64_t per_k = 6 * p.stride + (p.S > 1 ? (int64_t)p.S * f.planes * 3 * f.ny * f.nx * 2 : 0);
+  const int64_t bound = d->scratch_bound ? d->scratch_bound : ART_FOCAL_VECTOR_SCRATCH_DEFAULT;
+  const int64_t fit = (bound - rows) / per_k;
+  p.nkb = fit < 1 ? 1 : (fit > d->s.nk ? d->s.nk : (int)fit);
+  p.total = rows + p.nkb * per_k;
+  return p;
+}
+
+// the checks of the descriptor that need neither the coatings nor the buffers
+static int vecspec_check(const ArtFocalVectorSpectrumDesc* d) {
+  if (!d) return fail(ART_ERR_BAD_ARG, "focal vector spectrum descriptor is NULL");
+  if (const int e = focal_desc_check(&d->s.f)) return e;
+  if (const int e = focal_spectrum_check(&d->s)) return e;
+  if ((int64_t)d->s.f.planes * d->s.nk * 3 > 65535)
+    return fail(ART_ERR_BAD_ARG, "focal vector spectrum: planes * nk * 3 must be <= 65535");
+  if (d->n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (d->n > kMaxRaysPerLaunchHw) return fail(ART_ERR_UNSUPPORTED, "more than 2^28 rays in one focal vector spectrum call");
+  if (d->n_elems < 1 || d->n_elems > ART_POLARISATION_MAX_ELEMS)
+    return fail(ART_ERR_BAD_ARG, "a focal vector spectrum needs 1..ART_POLARISATION_MAX_ELEMS elements");
+  if (d->n_coatings < 0 || d->n_coatings > 65535) return fail(ART_ERR_BAD_ARG, "n_coatings must be in 0..65535");
+  if (d->scratch_bound < 0) return fail(ART_ERR_BAD_ARG, "focal vector spectrum: scratch_bound must be >= 0");
+  for (int e = 0; e < d->n_elems; ++e)
+    if (d->coating[e] < -1 || d->coating[e] >= d->n_coatings) return fail(ART_ERR_BAD_ARG, "coating index out of range");
+  for (int q = 0; q < 6; ++q)
+    if (!isfinite(d->pol[q])) return fail(ART_ERR_BAD_ARG, "focal vector spectrum: the input state is not finite");
+  return ART_OK;
+}
+
+int64_t art_focal_vector_spectrum_scratch_doubles(const ArtFocalVectorSpectrumDesc* d) {
+  if (const int e = vecspec_check(d)) return e;
+  return vecspec_plan(d).total;
+}
+
+int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBundleView* b, const ArtCoating* coatings_dev,
+                              const ArtCoating* coatings_host, const ArtCoatingMaterial* materials_host, double* scratch,
+                              double* field, void* stream) {
+  if (const int e = vecspec_check(d)) return e;
+  const ArtFocalDesc* f = &d->s.f;
+  const int nk = d->s.nk, nc = d->n_coatings;
+  if (nc > 0 && (!coatings_dev || !coatings_host || !materials_host || !d->materials))
+    return fail(ART_ERR_BAD_ARG, "coating or material table is NULL");
+  for (int c = 0; c < nc; ++c) {
+    if (const int cr = coating_check(coatings_host[c])) return cr;
+    if (coatings_host[c].ideal) continue;
+    for (int j = 0; j < nk; ++j)
+      for (int m = 0; m < coatings_host[c].n_materials; ++m) {
+        const ArtCoatingMaterial& mt = materials_host[((int64_t)j * nc + c) * ART_COATING_MAX_MATERIALS + m];
+        if (!(isfinite(mt.n) && isfinite(mt.kappa) && mt.kappa >= 0.0))
+          return fail(ART_ERR_BAD_ARG, "a material of the per-wavenumber table must have finite n and finite kappa >= 0");
+      }
+  }
+  if (d->n > 0 && !d->views) return fail(ART_ERR_BAD_ARG, "focal vector spectrum: views is NULL");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = d->n, pix = (int64_t)f->ny * f->nx;
+  bool done;
+  if (const int e = focal_call_check(b, n, scratch, field, (int64_t)f->planes * nk * 3 * pix, s, &done); e || done) return e;
+  const VecSpecPlan p = vecspec_plan(d);
+  const int S = p.S;
+  const FocalArg a = focal_arg(f, n, S);
+  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
+  VecSpecArg va;
+  memset(&va, 0, sizeof(va));
+  va.views = d->views; va.w = d->w;
+  for (int q = 0; q < 6; ++q) va.pol[q] = d->pol[q];
+  for (int c = 0; c < 3; ++c) { va.u[c] = a.e1[c]; va.u[3 + c] = a.e2[c]; va.u[6 + c] = a.nrm[c]; }
+  va.k0 = f->k; va.dk = d->s.dk;
+  va.n = n; va.stride = a.stride;
+  va.n_elems = d->n_elems; va.n_coatings = nc;
+  for (int e = 0; e < d->n_elems; ++e) va.coating[e] = d->coating[e];
+  per_launch(n, [&](const int64_t off, const int64_t m) {       // (one launch: n <= 2^28)
+    hipLaunchKernelGGL(k_focal_spectrum_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off),
+                       d->w ? d->w + off : nullptr, m, scratch + off);
+    return ART_OK;
+  });
+  double* amps = scratch + (int64_t)kFocalSpecRows * a.stride;
+  double* part = amps + (int64_t)p.nkb * 6 * a.stride;
+  for (int j0 = 0; j0 < nk; j0 += p.nkb) {
+    const int m = nk - j0 < p.nkb ? nk - j0 : p.nkb;
+    va.j0 = j0; va.nkb = m;
+    hipLaunchKernelGGL(k_vecspec_rays, dim3((unsigned)pol_tiles(n), m), dim3(kBlock), 0, s, va, coatings_dev, d->materials,
+                       amps);
+    double* dst = field + (int64_t)j0 * 3 * pix * 2;          // plane 0's place of this block in the field
+    if (S == 1) {
+      hipLaunchKernelGGL(k_vecspec_field, dim3(tiles, f->planes * m * 3, 1), dim3(kBlock), 0, s, a, d->s.dk, j0, m,
+                         (const double*)scratch, (const double*)amps, (int64_t)nk * 3 * pix, (int64_t)0, dst);
+      continue;
+    }
+    const int64_t block = (int64_t)m * 3 * pix;               // a plane's pixels of this block
+    hipLaunchKernelGGL(k_vecspec_field, dim3(tiles, f->planes * m * 3, S), dim3(kBlock), 0, s, a, d->s.dk, j0, m,
+                       (const double*)scratch, (const double*)amps, (int64_t)S * block, block, part);
+    const int64_t want = (block + kBlock - 1) / kBlock;
+    for (int q = 0; q < f->planes; ++q)
+      hipLaunchKernelGGL(k_focal_fold, dim3((int)(want > kMaxBlocks ? kMaxBlocks : want)), dim3(kBlock), 0, s,
+                         (const double2*)part + (int64_t)q * S * block, S, block,
+                         reinterpret_cast<double2*>(dst) + (int64_t)q * nk * 3 * pix);
+  }
+  return launched("art_focal_vector_spectrum launch");
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }

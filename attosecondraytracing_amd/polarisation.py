@@ -8,8 +8,10 @@ Ray.intensity (histograms, focal fields and pulses, wavefronts, getETransmission
 takes the coatings into account.
 
 The chain's history comes from get_output_rays(); a lazy history (history="lazy") is materialised by its own mechanism,
-which costs one re-trace of the chain.  Out of scope: optical constants that vary across a pulse's spectrum, the
-reflection phase in the focal field (a vector focal field), transmissive optics, and fusing this pass into the trace."""
+which costs one re-trace of the chain.  Tabulated materials (coating.Material) are evaluated at the one wavelength of
+the call; a pulse behind dispersive coatings, and the reflection phase in the focal field, are vector_pulse.py
+(OpticalChain.get_FocalPulse, get_VectorFocalField).  Out of scope: transmissive optics, and fusing this pass into the
+trace."""
 import ctypes as C
 import math
 
@@ -80,6 +82,16 @@ def _state(P):
     return v
 
 
+def history(chain):
+    """[source bundle, the bundle after each element]: the K + 1 views of a chain's polarisation pass."""
+    out = chain.get_output_rays()
+    bundles = [chain.source_rays] + [out[k] for k in range(len(chain.optical_elements))]   # (a lazy history materialises here)
+    n = bundles[-1].n_slots
+    if any(b.n_slots != n for b in bundles):
+        raise ValueError("the bundles of the chain's history do not have the same slots")
+    return bundles
+
+
 def polarisations(requests):
     """requests: [(chain, Coatings, kwargs)], kwargs those of OpticalChain.get_Polarisation.  One Polarisation per
     request, in order; all chains of one backend go to the device in ONE call of art_polarisation (blocks of
@@ -101,12 +113,7 @@ def polarisations(requests):
         det = kw.get("Detector")
         if det is not None:
             det._iscomplete()
-        src = chain.source_rays
-        out = chain.get_output_rays()
-        bundles = [src] + [out[k] for k in range(len(els))]        # (a lazy history materialises here)
-        n = bundles[-1].n_slots
-        if any(b.n_slots != n for b in bundles):
-            raise ValueError("the bundles of the chain's history do not have the same slots")
+        bundles = history(chain)
         wl = kw.get("Wavelength")
         wl = bundles[-1].wavelength if wl is None else wl
         if wl is None or not math.isfinite(float(wl)) or float(wl) <= 0:
@@ -150,10 +157,11 @@ def _job(item, coat_list, coat_pos):
         if c is None:
             j.coating[e] = -1
         else:
-            if id(c) not in coat_pos:
-                coat_pos[id(c)] = len(coat_list)
-                coat_list.append(c)
-            j.coating[e] = coat_pos[id(c)]
+            key = (id(c), wl) if c.dispersive else id(c)   # (tabulated materials are evaluated at the job's wavelength)
+            if key not in coat_pos:
+                coat_pos[key] = len(coat_list)
+                coat_list.append(c.at(wl) if c.dispersive else c)
+            j.coating[e] = coat_pos[key]
     j.n_elems = K
     j.n = n
     if P is not None:

@@ -1,8 +1,9 @@
 """Space-time focal fields of broadband pulses, summed on the device (art_hip.h, art_focal_spectrum):
 Detector.get_FocalPulse.
 
-All optics are mirrors, achromatic, so one traced bundle serves every frequency of the pulse: only the phase k (optical
-path) changes with k.  The focal field of focal.py (see its docstring for the model and its limits) is summed at J
+All optics are mirrors, so one traced bundle serves every frequency of the pulse; here they are also taken as achromatic
+(only the phase k (optical path) changes with k) -- coatings whose reflection depends on the frequency, and the vector
+field they act on, are OpticalChain.get_FocalPulse (vector_pulse.py).  The focal field of focal.py (see its docstring for the model and its limits) is summed at J
 wavenumbers k_j = omega_j / c in one device call, and a Fourier sum over them gives the envelope in time:
 
     A(x, y, t) = sum_j g_j E_j(x, y) exp(-i (omega_j - omega_0) t) / sum_j |g_j|,     g_j = s(omega_j) omega_j / omega_0
@@ -125,27 +126,24 @@ def _positive(v, name):
     return v
 
 
-def focal_pulse(det, RayList, DeltaFT, Size=None, Pixels=64, Centre=None, Shifts=None, Wavelength=None, RefPath=None,
-                Spectrum=None, TimeWindow=None, Times=256):
-    """Detector.get_FocalPulse (see the module's docstring).  Size, Pixels, Centre, Shifts, Wavelength and RefPath as
-    in get_FocalField.  DeltaFT: the Fourier-limited duration (intensity FWHM, fs) that sets the frequency grid and the
-    default spectrum; Spectrum: a callable omega (rad/fs, array) -> complex amplitude that replaces the default
-    Gaussian (a chirp is a quadratic phase); TimeWindow: T (fs), default 16 DeltaFT + 4 (max opl - min opl) / c over
-    the alive rays; Times: samples of [-T/2, T/2).  All wavenumbers and planes are summed in one device call."""
-    import torch
+def check_pulse_args(DeltaFT, TimeWindow, Times, Spectrum):
+    """(DeltaFT, TimeWindow or None, Nt) validated as get_FocalPulse's arguments."""
     DeltaFT = _positive(DeltaFT, "DeltaFT")
     if TimeWindow is not None:
         TimeWindow = _positive(TimeWindow, "TimeWindow")
     if not (np.isscalar(Times) and float(Times) == int(Times) and int(Times) >= 1):
         raise ValueError("Times must be a positive integer")
-    Nt = int(Times)
     if Spectrum is not None and not callable(Spectrum):
         raise ValueError("Spectrum must be a callable omega -> complex amplitude")
-    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
-    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+    return DeltaFT, TimeWindow, int(Times)
+
+
+def spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, stats):
+    """The frequency grid and weights of a pulse: (T, omega0, m, dw, omega, g, gsum), T defaulting to 16 DeltaFT +
+    4 (max opl - min opl) / c over the alive rays of the lite read-out `stats`."""
     T = TimeWindow
     if T is None:
-        spread = s[13] - s[12] if s[0] > 0 else 0.0
+        spread = stats[13] - stats[12] if stats[0] > 0 else 0.0
         T = 16 * DeltaFT + 4 * spread / C_MM_PER_FS
     omega0, m = spectral_grid(wavelength, DeltaFT, T)
     dw = 2 * math.pi / T
@@ -160,6 +158,27 @@ def focal_pulse(det, RayList, DeltaFT, Size=None, Pixels=64, Centre=None, Shifts
     gsum = np.abs(g).sum()
     if not gsum > 0:
         raise ValueError("Spectrum is zero on the whole frequency grid")
+    return T, omega0, m, dw, omega, g, gsum
+
+
+def time_axis(T, Nt, m, dw, gsum):
+    """(t [Nt], M [Nt, J]): the samples of [-T/2, T/2) and the matrix of the Fourier sum over the offsets m."""
+    t = -0.5 * T + np.arange(Nt) * (T / Nt)
+    return t, np.exp(-1j * (m * dw)[None, :] * t[:, None]) / gsum
+
+
+def focal_pulse(det, RayList, DeltaFT, Size=None, Pixels=64, Centre=None, Shifts=None, Wavelength=None, RefPath=None,
+                Spectrum=None, TimeWindow=None, Times=256):
+    """Detector.get_FocalPulse (see the module's docstring).  Size, Pixels, Centre, Shifts, Wavelength and RefPath as
+    in get_FocalField.  DeltaFT: the Fourier-limited duration (intensity FWHM, fs) that sets the frequency grid and the
+    default spectrum; Spectrum: a callable omega (rad/fs, array) -> complex amplitude that replaces the default
+    Gaussian (a chirp is a quadratic phase); TimeWindow: T (fs), default 16 DeltaFT + 4 (max opl - min opl) / c over
+    the alive rays; Times: samples of [-T/2, T/2).  All wavenumbers and planes are summed in one device call."""
+    import torch
+    DeltaFT, TimeWindow, Nt = check_pulse_args(DeltaFT, TimeWindow, Times, Spectrum)
+    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+    T, omega0, m, dw, omega, g, gsum = spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, s)
     sd = _abi.ArtFocalSpectrumDesc()
     sd.f = fd
     sd.f.k = omega[0] / C_MM_PER_FS
@@ -168,8 +187,7 @@ def focal_pulse(det, RayList, DeltaFT, Size=None, Pixels=64, Centre=None, Shifts
     field = B.backend.focal_spectrum(sd, B.view(), B.intensity, B.n_slots)
     P, J, ny, nx = field.shape
     spectrum = field * torch.as_tensor(g, device=field.device)[None, :, None, None]
-    t = -0.5 * T + np.arange(Nt) * (T / Nt)
-    M = np.exp(-1j * (m * dw)[None, :] * t[:, None]) / gsum                    # [Nt, J]
+    t, M = time_axis(T, Nt, m, dw, gsum)                                      # M [Nt, J]
     envelope = torch.matmul(torch.as_tensor(M, device=field.device), spectrum.reshape(P, J, ny * nx))
     return FocalPulse(spectrum, envelope.reshape(P, Nt, ny, nx), omega, omega0, g, t, T, x, y, shifts, DeltaFT,
                       wavelength, ref, focal.amplitude_sum(B))

@@ -487,6 +487,50 @@ int art_polarisation(const ArtPolarisationJob* jobs_dev, const ArtPolarisationJo
                      const ArtCoating* coatings_dev, const ArtCoating* coatings_host, int32_t n_coatings, double* scratch,
                      void* stream);
 
+/* Vector focal fields of a pulse behind dispersive coatings (added under ABI 14: ArtFocalVectorSpectrumDesc,
+ * art_focal_vector_spectrum, art_focal_vector_spectrum_scratch_doubles): art_focal_spectrum's sum with the complex
+ * vector field of art_polarisation, evaluated per ray AND per wavenumber, as each ray's amplitude.  With
+ * k_j = s.f.k + j * s.dk (art_focal_spectrum's k_j), u_0, u_1 = rows 0, 1 of s.f.det.rot and u_2 = s.f.det.normal:
+ *     a_r(k_j)        = sqrt(w_r) E_r(k_j)          E_r: art_polarisation's E_K of a polarised input `pol` (same initial
+ *                                                    field, frames, cos t; a mask, coating index -1, leaves E unchanged),
+ *                                                    every coating's rs, rp formed at k_j with the optical constants
+ *                                                    materials[j][c][.] in place of coatings[c].materials
+ *     field[q][j][c]  = sum_r (a_r(k_j) . u_c) exp(i k_j Phi_r)      (bilinear dot product; c = 0, 1, 2)
+ * exp(i k_j Phi_r) is art_focal_spectrum's phase factor of ray r (same separation and operation order), w_r = w[r] (1
+ * when w is NULL) for the rays alive in views[n_elems], 0 for every other slot.  b is views[n_elems] as a HOST struct.
+ * field (DEVICE, complex128, [planes][nk][3][ny][nx]) is written, not added to; n = 0 writes zeros.  Fixed summation
+ * order (no float atomics): the same bytes on every call with the same arguments.
+ * The wavenumbers are processed in blocks of nkb; a block needs 6 doubles per slot and wavenumber (the a_r . u_c) besides
+ * its partial sums.  scratch_bound (doubles; 0: ART_FOCAL_VECTOR_SCRATCH_DEFAULT) chooses the largest nkb whose scratch
+ * stays within it (at least 1, whatever the bound); every (plane, wavenumber, component) is summed on its own, and the
+ * slicing of the rays does not depend on nkb: the same bytes for every scratch_bound.
+ * scratch: DEVICE, art_focal_vector_spectrum_scratch_doubles(d) doubles.  coatings_dev / materials: DEVICE copies of the
+ * HOST arrays coatings_host / materials_host (read for validation), materials as
+ * ArtCoatingMaterial[nk][n_coatings][ART_COATING_MAX_MATERIALS]; entries beyond a coating's n_materials are not read.
+ * Limits: all of art_focal_spectrum's with planes * nk * 3 <= 65535 in place of planes * nk <= 65535 (the component
+ * rides on the grid beside plane and wavenumber); of art_polarisation's: 0 <= n <= 2^28 (ART_ERR_UNSUPPORTED beyond),
+ * 1 <= n_elems <= ART_POLARISATION_MAX_ELEMS, coating indices in [-1, n_coatings), 0 <= n_coatings <= 65535, finite
+ * pol, every coating valid, and every materials[j][c][m], m < n_materials of a non-ideal coating c, finite with
+ * kappa >= 0; scratch_bound >= 0; views, field and scratch non-NULL when n > 0: ART_ERR_BAD_ARG otherwise, with nothing
+ * launched and field untouched. */
+#define ART_FOCAL_VECTOR_SCRATCH_DEFAULT ((int64_t)1 << 29)   /* doubles: 4 GiB */
+typedef struct ArtFocalVectorSpectrumDesc {
+  ArtFocalSpectrumDesc s;      /* grid, planes, detector, L_ref, k_0, dk, nk                                         */
+  const ArtBundleView* views;  /* DEVICE array of n_elems + 1 views: the source, then the bundle after each element   */
+  int32_t coating[ART_POLARISATION_MAX_ELEMS];     /* per element: index into the coatings, -1 for a mask           */
+  int32_t n_elems;             /* K                                                                                  */
+  int32_t n_coatings;
+  int64_t n;                   /* slots of every view                                                                */
+  double pol[6];               /* P: re x, im x, re y, im y, re z, im z                                              */
+  const double* w;             /* DEVICE weights of the final bundle (views[K]) or NULL                              */
+  const ArtCoatingMaterial* materials;   /* DEVICE, [nk][n_coatings][ART_COATING_MAX_MATERIALS]                      */
+  int64_t scratch_bound;       /* doubles; 0 = ART_FOCAL_VECTOR_SCRATCH_DEFAULT                                      */
+} ArtFocalVectorSpectrumDesc;
+int64_t art_focal_vector_spectrum_scratch_doubles(const ArtFocalVectorSpectrumDesc* d);
+int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBundleView* b, const ArtCoating* coatings_dev,
+                              const ArtCoating* coatings_host, const ArtCoatingMaterial* materials_host, double* scratch,
+                              double* field, void* stream);
+
 /* Masked reductions over alive rays, deterministic (fixed two-level tree, no float atomics).
  * out16 (DEVICE, 16 doubles):
  *   [0] count  [1] sum opl  [2] min X [3] max X [4] min Y [5] max Y  [6] sum X [7] sum Y
