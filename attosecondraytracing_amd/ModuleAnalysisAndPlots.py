@@ -113,6 +113,13 @@ def FocalSpot(RayListAnalysed, Detector, Size=None, Pixels=128, Log=False):
     return _plots.FocalSpot(RayListAnalysed, Detector, Size, Pixels, Log)
 
 
+def SourceImage(RayListAnalysed, Detector, RaysPerSource=None, Groups=None, Size=None, Pixels=128, Log=False):
+    """The partially coherent image of an extended source (Detector.get_FocalImage) beside the fully coherent
+    |get_FocalField|^2 of the same bundle on the same grid."""
+    from . import _plots
+    return _plots.SourceImage(RayListAnalysed, Detector, RaysPerSource, Groups, Size, Pixels, Log)
+
+
 def ThroughFocus(RayListAnalysed, Detector, Shifts, Size=None, Pixels=64):
     """Strehl ratio and peak position of the coherent focal field against the detector shift (all planes in one call)."""
     from . import _plots

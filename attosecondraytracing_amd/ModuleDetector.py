@@ -239,6 +239,16 @@ class Detector:
         from . import focal
         return focal.focal_field(self, RayList, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
 
+    def get_FocalImage(self, RayList, RaysPerSource=None, Groups=None, Size=None, Pixels=128, Centre=None, Shifts=None,
+                       Wavelength=None, RefPath=None):
+        """Partially coherent focal image (image.FocalImage) of an extended source: the alive rays are summed on the
+        device as in get_FocalField inside each group of mutually coherent rays, and the groups' intensities are added.
+        Exactly one of RaysPerSource (the group of a slot is its ray number // RaysPerSource: ExtendedSource's numbering,
+        the value is the bundle's rays_per_source) and Groups (one integer id per slot, non-decreasing: groups are
+        contiguous slot ranges).  Every other argument as in get_FocalField."""
+        from . import image
+        return image.focal_image(self, RayList, RaysPerSource, Groups, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+
     def get_FocalPulse(self, RayList, DeltaFT, Size=None, Pixels=64, Centre=None, Shifts=None, Wavelength=None,
                        RefPath=None, Spectrum=None, TimeWindow=None, Times=256):
         """Space-time focal field of a pulse (pulse.FocalPulse): the focal fields of get_FocalField (same Size, Pixels,

@@ -180,6 +180,16 @@ class OpticalChain:
         return vector_pulse.vector_focal_field(self, Coatings, Detector, Polarisation, Size, Pixels, Centre, Shifts,
                                                Wavelength, RefPath)
 
+    def get_FocalImage(self, Detector, RaysPerSource=None, **kw):
+        """The partially coherent focal image (image.FocalImage) of the chain's final bundle on Detector:
+        Detector.get_FocalImage with RaysPerSource defaulting to the source's rays_per_source (set by ExtendedSource);
+        every other argument as in Detector.get_FocalImage."""
+        if RaysPerSource is None and kw.get("Groups") is None:
+            RaysPerSource = getattr(self.source_rays, "rays_per_source", None)
+            if RaysPerSource is None:
+                raise ValueError("the source has no rays_per_source (it is no ExtendedSource): pass RaysPerSource=")
+        return Detector.get_FocalImage(self.get_output_rays()[-1], RaysPerSource=RaysPerSource, **kw)
+
     def _output_for(self, key, kwargs):
         """get_output_rays for a cache key the caller has computed already (trace_chain_list: once per chain)."""
         if key != self._last_key:

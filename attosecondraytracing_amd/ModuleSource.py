@@ -55,6 +55,7 @@ def ExtendedSource(S, Axis, Diameter: float, Divergence: float, NbRays: int, Wav
                             b.view())
     b.tag_content(("extended source", float(Diameter), float(Divergence), int(n_src), int(per),
                    np.asarray(S, dtype=float).tobytes(), np.asarray(Axis, dtype=float).tobytes(), Wavelength))
+    b.rays_per_source = per       # the mutually incoherent groups of Detector.get_FocalImage
     return b
 
 

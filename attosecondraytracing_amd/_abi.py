@@ -237,6 +237,18 @@ class ArtFocalVectorSpectrumDesc(C.Structure):
     ]
 
 
+ART_FOCAL_MAX_GROUPS = 1 << 20
+
+
+class ArtFocalImageDesc(C.Structure):
+    _fields_ = [
+        ("f", ArtFocalDesc),
+        ("groups", C.c_int32),
+        ("reserved", C.c_int32),
+        ("seg", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); the loader checks every symbol exists (tests/test_abi.py does too)
 PROTOTYPES = {
     "art_abi_version": (C.c_int, []),
@@ -280,6 +292,9 @@ PROTOTYPES = {
     "art_focal_vector_spectrum": (C.c_int, [C.POINTER(ArtFocalVectorSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p,
                                             C.POINTER(ArtCoating), C.POINTER(ArtCoatingMaterial), C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    "art_focal_image_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "art_focal_image": (C.c_int, [C.POINTER(ArtFocalImageDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_reduce_scratch_doubles": (C.c_int64, []),
     "art_detector_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -336,6 +336,23 @@ class HipBackend:
                                                  self.stream_ptr()), "art_focal_spectrum")
         return field
 
+    def focal_image(self, fdesc, seg, groups, view, w, n):
+        """art_focal_image on the current stream: a new device float64 tensor [planes, ny, nx].  seg: device int64
+        tensor of groups + 1 slot offsets (never read back); scratch reused per stream."""
+        d = _abi.ArtFocalImageDesc()
+        d.f = fdesc
+        d.groups = int(groups)
+        d.seg = seg.data_ptr()
+        image = torch.empty((fdesc.planes, fdesc.ny, fdesc.nx), dtype=torch.float64, device=self.device)
+        ns = self.fn["art_focal_image_scratch_doubles"](fdesc.nx, fdesc.ny, fdesc.planes, d.groups, n)
+        if ns < 0:
+            raise ArtError(f"art_focal_image_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self.scratch("focal", ns, torch.float64)
+        self.check(self.fn["art_focal_image"](C.byref(d), C.byref(view), None if (w is None or n == 0) else w.data_ptr(),
+                                              n, scratch.data_ptr(), image.data_ptr(), self.stream_ptr()),
+                   "art_focal_image")
+        return image
+
     def _red_scratch(self):
         return self.scratch("red", self.fn["art_reduce_scratch_doubles"](), torch.float64)
 

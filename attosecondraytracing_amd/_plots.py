@@ -398,6 +398,41 @@ def FocalSpot(RayListAnalysed, Detector, Size=None, Pixels=128, Log=False):
     return fig
 
 
+def SourceImage(RayListAnalysed, Detector, RaysPerSource=None, Groups=None, Size=None, Pixels=128, Log=False):
+    """Two images in µm, detector coordinates, on one grid: the partially coherent image of an extended source
+    (Detector.get_FocalImage, its Strehl ratio and rms widths in the title) and the fully coherent |get_FocalField|^2
+    of the same bundle, each over its own maximum."""
+    plt = _plt()
+    B = _as_bundle(RayListAnalysed)
+    g = Detector.get_FocalImage(B, RaysPerSource=RaysPerSource, Groups=Groups, Size=Size, Pixels=Pixels)
+    centre = (0.5 * (g.x[0] + g.x[-1]), 0.5 * (g.y[0] + g.y[-1]))
+    size = (max(g.x[-1] - g.x[0], np.finfo(float).tiny), max(g.y[-1] - g.y[0], np.finfo(float).tiny))
+    f = Detector.get_FocalField(B, Size=size, Pixels=(len(g.x), len(g.y)), Centre=centre, RefPath=g.ref_path)
+    dx = 0.5 * (g.x[1] - g.x[0]) if len(g.x) > 1 else 0.5
+    dy = 0.5 * (g.y[1] - g.y[0]) if len(g.y) > 1 else 0.5
+    extent = ((g.x[0] - dx) * 1e3, (g.x[-1] + dx) * 1e3, (g.y[0] - dy) * 1e3, (g.y[-1] + dy) * 1e3)
+
+    def shown(img):
+        img = img / max(img.max(), np.finfo(float).tiny)
+        return np.log10(np.maximum(img, 1e-12)) if Log else img
+
+    plt.ion()
+    fig, (a1, a2) = plt.subplots(1, 2, sharex=True, sharey=True)
+    for ax, img, name in ((a1, g.intensity[0].cpu().numpy(), "Partially coherent, {} groups".format(g.groups)),
+                          (a2, f.intensity[0], "Coherent")):
+        im = ax.imshow(shown(img), origin="lower", extent=extent, aspect="equal", interpolation="nearest")
+        fig.colorbar(im, ax=ax, shrink=0.6).set_label("log10 intensity / peak" if Log else "Intensity / peak")
+        ax.set_title(name)
+        ax.set_xlabel("X (µm)")
+    a1.set_ylabel("Y (µm)")
+    fig.suptitle("Source image, {:.3f} mm, Strehl {:.3f}, rms {:.3f} x {:.3f} µm".format(
+        Detector.get_distance(), g.strehl[0], g.rms[0, 0] * 1e3, g.rms[0, 1] * 1e3))
+    fig._art_image = g
+    fig._art_focal = f
+    plt.show()
+    return fig
+
+
 def ThroughFocus(RayListAnalysed, Detector, Shifts, Size=None, Pixels=64):
     """Strehl ratio and peak position (µm, detector coordinates) of the coherent focal field against the detector shift
     (mm, Detector.shiftByDistance's sign); all planes are summed in one device call."""

@@ -203,6 +203,11 @@ class RayBundle:
             b.path_head = np.array([r.path for r in rays], dtype=np.float64)
         return b
 
+    def _share_grouping(self, other):
+        """Bundles over the same slots keep ExtendedSource's rays_per_source (image.py: the incoherent groups)."""
+        if hasattr(self, "rays_per_source"):
+            other.rays_per_source = self.rays_per_source
+
     # ------------------------------------------------------------------ raw access
     @property
     def n_slots(self):
@@ -365,6 +370,7 @@ class RayBundle:
         out = RayBundle(self.data, alive, self.number, self.intensity, self.wavelength, self._parent, self.backend)
         self._share_parent(out)
         out.path_head = self.path_head
+        self._share_grouping(out)
         return out
 
     def transformed(self, M, T, rotate_points=True):
@@ -374,6 +380,7 @@ class RayBundle:
         out._parent = self._parent
         self._share_parent(out)
         out.path_head = self.path_head
+        self._share_grouping(out)
         self.backend.transform_bundle(M, T, rotate_points, self.view(), out.view(), self.n_slots)
         return out
 
@@ -384,6 +391,7 @@ class RayBundle:
         out = RayBundle(data, alive, self.number, self.intensity, self.wavelength, self._parent, self.backend)
         self._share_parent(out)
         out.path_head = self.path_head
+        self._share_grouping(out)
         out.tag_content(self.content_key())        # a copy is bit-identical to its original
         return out
 
@@ -394,6 +402,7 @@ class RayBundle:
         out = RayBundle(self.data, self.alive, self.number, self.intensity, self.wavelength, self._parent, self.backend)
         self._share_parent(out)
         out.path_head = self.path_head
+        self._share_grouping(out)
         out.tag_content(self.content_key())
         hit = getattr(self, "_sum_w", None)
         if hit is not None and hit[0] == self.version:

@@ -1685,6 +1685,154 @@ __global__ __launch_bounds__(kBlock) void k_focal_fold(const double2* __restrict
   }
 }
 
+// ------------------------------------------------------------------------------------------- focal image
+// art_focal_image: the partially coherent image of an extended source, I_q = sum_g |sum_{r in g} ...|^2 over groups g
+// of slots [seg[g], seg[g+1]) (seg on the device, never read by the host).  k_focal_prep's rows, then k_focal_image:
+// k_focal_field's loop (a copy: shared helpers change k_focal_field's registers) run group by group -- a chunk never
+// straddles two groups, the tail of a group's last chunk has amplitude 0 -- and at the end of a group every lane adds
+// re^2 + im^2 of its 16 complex sums to 16 real ones and clears the complex ones.  Grid: (tile, plane x slice), a slice
+// a contiguous range of `per` groups; partials [plane][slice][ny][nx] go through k_focal_image_fold in slice order.
+// With so few groups that slices of them cannot fill the machine (split > 1) a workgroup instead takes one of `split`
+// chunk-aligned pieces of ONE group and writes its complex sum [plane][group][piece][ny][nx]; k_focal_image_fold_split
+// adds a group's pieces in order, squares, and adds the groups in order.  Offsets are clamped to [0, n] and
+// seg[g+1] <= seg[g] is an empty group: safe for any contents of seg.  No float atomics: the same bytes on every call.
+__global__ __launch_bounds__(kBlock) void k_focal_image(const FocalArg a, const double* __restrict__ rows,
+                                                        const int64_t* __restrict__ seg, const int groups, const int per,
+                                                        const int slices, const int split, double* __restrict__ out) {
+  __shared__ double2 sU[kFocalChunk][kFocalTile];     // exp(i X_j k d.e1)
+  __shared__ double2 sW[kFocalChunk][kFocalTile];     // amp exp(i (base + s_q k d.n + Y_l k d.e2))
+  const int job = blockIdx.y;                         // split == 1: (plane, slice); else (plane, group, piece)
+  const int q = split > 1 ? job / (groups * split) : job / slices;
+  const int g0 = split > 1 ? (job / split) % groups : (job % slices) * per;
+  const int g1 = split > 1 ? g0 + 1 : (g0 + per < groups ? g0 + per : groups);
+  const int piece = job % split;
+  const int tx0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * kFocalTile, ty0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * kFocalTile;
+  const int t = threadIdx.x, lx = t % kFocalLanes, ly = t / kFocalLanes;
+  const int64_t st = a.stride;
+  const double sh = a.shift[q];
+  // staging role of this lane: rows (W) or columns (U), ray sr of the chunk, segment sg of the tile
+  const bool colw = t < kBlock / 2;
+  const int sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg), sg = t % (kFocalTile / kFocalSeg);
+  double acc_re[kFocalMicro][kFocalMicro], acc_im[kFocalMicro][kFocalMicro], acc_in[kFocalMicro][kFocalMicro];
+#pragma unroll
+  for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+    for (int u = 0; u < kFocalMicro; ++u) acc_re[v][u] = acc_im[v][u] = acc_in[v][u] = 0.0;
+
+  for (int g = g0; g < g1; ++g) {
+    int64_t r0 = seg[g], r1 = seg[g + 1];
+    r0 = r0 < 0 ? 0 : (r0 > a.n ? a.n : r0);
+    r1 = r1 < 0 ? 0 : (r1 > a.n ? a.n : r1);
+    if (split > 1 && r1 > r0) {                       // this piece of the group, a whole number of chunks
+      const int64_t chunks = (r1 - r0 + kFocalChunk - 1) / kFocalChunk;
+      const int64_t len = (chunks + split - 1) / split * kFocalChunk;
+      r0 += piece * len;
+      if (r0 + len < r1) r1 = r0 + len;
+    }
+    for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
+      const int64_t r = c0 + sr;
+      const bool in = r < r1;                     // beyond the group: a zero row phasor, nothing is added
+      double ph, amp, s_re, s_im;
+      int p0;
+      if (colw) {
+        p0 = tx0 + sg * kFocalSeg;
+        const double ka = in ? rows[2 * st + r] : 0.0;
+        ph = ka * (a.x0 + (double)p0 * a.dx);
+        amp = 1.0;
+        s_re = in ? rows[5 * st + r] : 1.0; s_im = in ? rows[6 * st + r] : 0.0;
+      } else {
+        p0 = ty0 + sg * kFocalSeg;
+        const double base = in ? rows[st + r] : 0.0, kb = in ? rows[3 * st + r] : 0.0, kc = in ? rows[4 * st + r] : 0.0;
+        ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
+        amp = in ? rows[r] : 0.0;
+        s_re = in ? rows[7 * st + r] : 1.0; s_im = in ? rows[8 * st + r] : 0.0;
+      }
+      double sn, cs;
+      sincos(ph, &sn, &cs);
+      double z_re = amp * cs, z_im = amp * sn;
+      double2* dst = colw ? &sU[sr][sg * kFocalSeg] : &sW[sr][sg * kFocalSeg];
+#pragma unroll
+      for (int m = 0; m < kFocalSeg; ++m) {
+        dst[m] = make_double2(z_re, z_im);
+        const double n_re = z_re * s_re - z_im * s_im;
+        z_im = z_re * s_im + z_im * s_re;
+        z_re = n_re;
+      }
+      __syncthreads();
+#pragma unroll 2
+      for (int rr = 0; rr < kFocalChunk; ++rr) {
+        double2 uu[kFocalMicro], vv[kFocalMicro];
+#pragma unroll
+        for (int i = 0; i < kFocalMicro; ++i) {
+          uu[i] = sU[rr][lx + kFocalLanes * i];
+          vv[i] = sW[rr][ly + kFocalLanes * i];
+        }
+#pragma unroll
+        for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+          for (int u = 0; u < kFocalMicro; ++u) {
+            acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
+            acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
+            acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
+            acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
+          }
+      }
+      __syncthreads();
+    }
+    if (split > 1) break;                         // the piece's complex sum is the result
+#pragma unroll
+    for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+      for (int u = 0; u < kFocalMicro; ++u) {
+        acc_in[v][u] = fma(acc_re[v][u], acc_re[v][u], fma(acc_im[v][u], acc_im[v][u], acc_in[v][u]));
+        acc_re[v][u] = acc_im[v][u] = 0.0;
+      }
+  }
+  const int64_t o = (int64_t)job * a.ny * a.nx;
+#pragma unroll
+  for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+    for (int u = 0; u < kFocalMicro; ++u) {
+      const int l = ty0 + ly + kFocalLanes * v, j = tx0 + lx + kFocalLanes * u;
+      if (l < a.ny && j < a.nx) {
+        if (split > 1) reinterpret_cast<double2*>(out)[o + (int64_t)l * a.nx + j] = make_double2(acc_re[v][u], acc_im[v][u]);
+        else out[o + (int64_t)l * a.nx + j] = acc_in[v][u];
+      }
+    }
+}
+
+// image[q][p] = sum over the slices in slice order of partial[q][slice][p]
+__global__ __launch_bounds__(kBlock) void k_focal_image_fold(const double* __restrict__ part, const int slices,
+                                                             const int64_t pixels, const int64_t total,
+                                                             double* __restrict__ image) {
+  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < total; p += (int64_t)gridDim.x * kBlock) {
+    const int64_t q = p / pixels, px = p - q * pixels;
+    double v = 0.0;
+    for (int s = 0; s < slices; ++s) v += part[(q * slices + s) * pixels + px];
+    image[p] = v;
+  }
+}
+
+// image[q][p] = sum over the groups in order of |sum over the pieces in order of partial[q][group][piece][p]|^2
+__global__ __launch_bounds__(kBlock) void k_focal_image_fold_split(const double2* __restrict__ part, const int groups,
+                                                                   const int split, const int64_t pixels,
+                                                                   const int64_t total, double* __restrict__ image) {
+  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < total; p += (int64_t)gridDim.x * kBlock) {
+    const int64_t q = p / pixels, px = p - q * pixels;
+    double v = 0.0;
+    for (int g = 0; g < groups; ++g) {
+      double re = 0.0, im = 0.0;
+      for (int s = 0; s < split; ++s) {
+        const double2 z = part[((q * groups + g) * split + s) * pixels + px];
+        re += z.x;
+        im += z.y;
+      }
+      v = fma(re, re, fma(im, im, v));
+    }
+    image[p] = v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------- focal spectrum
 // art_focal_spectrum: the focal field at nk wavenumbers k_j = k_0 + j dk from one bundle (mirrors are achromatic, so
 // only the phase k (optical path) changes with k).  k_focal_spectrum_prep writes the k-independent rows of each slot
@@ -3729,6 +3877,77 @@ int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double*
                        (const double2*)part, S, pixels, reinterpret_cast<double2*>(field));
   }
   return launched("art_focal_field launch");
+}
+
+// the launch shape of art_focal_image, from the sizes alone (seg stays on the device): S slices of `per` groups, or,
+// when all the groups' workgroups fill less than half of kFocalWantBlocks, `split` pieces of every group (S = 1 then)
+struct FocalImagePlan { int S, per, split; };
+static FocalImagePlan focal_image_plan(int nx, int ny, int planes, int groups, int64_t n) {
+  FocalImagePlan p;
+  int s = focal_slices(nx, ny, planes, n);
+  if (s > groups) s = groups;
+  p.per = (groups + s - 1) / s;
+  p.S = (groups + p.per - 1) / p.per;            // no empty slice
+  const int64_t wgs = (int64_t)((nx + kFocalTile - 1) / kFocalTile) * ((ny + kFocalTile - 1) / kFocalTile) * planes * groups;
+  int64_t k = kFocalWantBlocks / wgs;
+  const int64_t by_rays = (n / groups + 4 * kFocalChunk - 1) / (4 * kFocalChunk);   // 4 chunks of a mean group per piece
+  if (k > by_rays) k = by_rays;
+  if (k > kFocalMaxSlices) k = kFocalMaxSlices;
+  p.split = k < 2 ? 1 : (int)k;
+  if (p.split > 1) { p.S = 1; p.per = groups; }
+  return p;
+}
+
+int64_t art_focal_image_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int32_t groups, int64_t n) {
+  if (nx < 1 || ny < 1 || nx > ART_FOCAL_MAX_PIXELS || ny > ART_FOCAL_MAX_PIXELS || planes < 1 ||
+      planes > ART_FOCAL_MAX_PLANES || groups < 1 || groups > ART_FOCAL_MAX_GROUPS || n < 0)
+    return fail(ART_ERR_BAD_ARG, "focal image scratch: nx, ny in [1, 2048], planes in [1, 64], groups in [1, 2^20], n >= 0");
+  const FocalImagePlan p = focal_image_plan(nx, ny, planes, groups, n);
+  const int64_t pixels = (int64_t)planes * ny * nx;
+  const int64_t part = p.split > 1 ? (int64_t)groups * p.split * pixels * 2 : (p.S > 1 ? (int64_t)p.S * pixels : 0);
+  return (int64_t)kFocalRows * focal_stride(n) + part;
+}
+
+int art_focal_image(const ArtFocalImageDesc* d, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
+                    double* image, void* stream) {
+  if (!d) return fail(ART_ERR_BAD_ARG, "focal image descriptor is NULL");
+  const ArtFocalDesc* f = &d->f;
+  if (const int e = focal_desc_check(f)) return e;
+  if (d->groups < 1 || d->groups > ART_FOCAL_MAX_GROUPS) return fail(ART_ERR_BAD_ARG, "focal image: groups must be in [1, 2^20]");
+  if (!d->seg) return fail(ART_ERR_BAD_ARG, "focal image: seg must not be NULL");
+  if (!image) return fail(ART_ERR_BAD_ARG, "focal image: image must not be NULL");
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (n > 0 && !scratch) return fail(ART_ERR_BAD_ARG, "focal image: scratch must not be NULL");
+  if (n > 0 && !view_ok(b)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t pixels = (int64_t)f->ny * f->nx, total = pixels * f->planes;
+  if (n == 0) {
+    const hipError_t e = hipMemsetAsync(image, 0, (size_t)total * sizeof(double), s);
+    return e == hipSuccess ? ART_OK : fail_hip(e, "hipMemsetAsync");
+  }
+  const FocalImagePlan p = focal_image_plan(f->nx, f->ny, f->planes, d->groups, n);
+  const FocalArg a = focal_arg(f, n, 1);
+  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
+  per_launch(n, [&](const int64_t off, const int64_t m) {
+    hipLaunchKernelGGL(k_focal_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off), w ? w + off : nullptr,
+                       m, scratch + off);
+    return ART_OK;
+  });
+  const bool direct = p.S == 1 && p.split == 1;
+  double* part = direct ? image : scratch + (int64_t)kFocalRows * a.stride;
+  const int jobs = p.split > 1 ? f->planes * d->groups * p.split : f->planes * p.S;   // <= 2048 or <= 64 * 64
+  hipLaunchKernelGGL(k_focal_image, dim3(tiles, jobs), dim3(kBlock), 0, s, a, (const double*)scratch, d->seg,
+                     (int)d->groups, p.per, p.S, p.split, part);
+  if (!direct) {
+    const int64_t want = (total + kBlock - 1) / kBlock;
+    const dim3 grid((int)(want > kMaxBlocks ? kMaxBlocks : want));
+    if (p.split > 1)
+      hipLaunchKernelGGL(k_focal_image_fold_split, grid, dim3(kBlock), 0, s, (const double2*)part, (int)d->groups, p.split,
+                         pixels, total, image);
+    else
+      hipLaunchKernelGGL(k_focal_image_fold, grid, dim3(kBlock), 0, s, (const double*)part, p.S, pixels, total, image);
+  }
+  return launched("art_focal_image launch");
 }
 
 // the checks an ArtFocalSpectrumDesc adds to focal_desc_check

@@ -10,7 +10,8 @@ At a ray's own hit point the phase is k (opl_r - RefPath), opl_r the value behin
 
 Limits of the model: each ray stands for an equal share of the beam's solid angle, scaled by w (true to O(NA^2) for the
 Vogel-spiral sources at the numerical apertures of the shipped configurations, not for arbitrary ray sets); all rays
-are summed as mutually coherent, which is wrong for ExtendedSource bundles (partial coherence is not modelled)."""
+are summed as mutually coherent, which is wrong for ExtendedSource bundles (partial coherence: image.py,
+Detector.get_FocalImage)."""
 import math
 
 import numpy as np

@@ -531,6 +531,30 @@ int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBund
                               const ArtCoating* coatings_host, const ArtCoatingMaterial* materials_host, double* scratch,
                               double* field, void* stream);
 
+/* Partially coherent focal image of an extended source (added under ABI 14: ArtFocalImageDesc, art_focal_image,
+ * art_focal_image_scratch_doubles): the rays of one bundle in mutually incoherent groups of contiguous slots, summed
+ * coherently inside a group and as intensities across groups,
+ *     image[q][l,j] = sum_g | sum_{r in group g} sqrt(w_r) exp(i k [(path_r - L_ref) + d_r . (x_qjl - p_r)]) |^2
+ * with art_focal_field's per-ray terms, formed in the same operation order; group g = slots [seg[g], seg[g+1]).  seg
+ * lives on the DEVICE and the host never reads it: every offset is clamped to [0, n], seg[g+1] <= seg[g] is an empty
+ * group (it contributes 0), and slots outside every group contribute nothing -- no contents of seg make the call read
+ * outside the bundle.  Dead slots contribute nothing.
+ * image (DEVICE, fp64, [planes][ny][nx]) is written, not added to; n = 0 writes zeros.  Fixed summation order (no float
+ * atomics): the same bytes on every call with the same arguments.
+ * scratch: DEVICE, art_focal_image_scratch_doubles(nx, ny, planes, groups, n) doubles (-1 on arguments out of range).
+ * Limits: all of art_focal_field's on f, 1 <= groups <= ART_FOCAL_MAX_GROUPS, seg and image non-NULL, scratch non-NULL
+ * when n > 0: ART_ERR_BAD_ARG otherwise, with nothing launched and image untouched. */
+#define ART_FOCAL_MAX_GROUPS (1 << 20)
+typedef struct ArtFocalImageDesc {
+  ArtFocalDesc f;         /* grid, planes, detector, k, L_ref: exactly art_focal_field's                           */
+  int32_t groups;         /* 1 .. ART_FOCAL_MAX_GROUPS                                                             */
+  int32_t reserved;
+  const int64_t* seg;     /* DEVICE, groups + 1 slot offsets: group g = slots [seg[g], seg[g+1])                    */
+} ArtFocalImageDesc;
+int64_t art_focal_image_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int32_t groups, int64_t n);
+int art_focal_image(const ArtFocalImageDesc* d, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
+                    double* image, void* stream);
+
 /* Masked reductions over alive rays, deterministic (fixed two-level tree, no float atomics).
  * out16 (DEVICE, 16 doubles):
  *   [0] count  [1] sum opl  [2] min X [3] max X [4] min Y [5] max Y  [6] sum X [7] sum Y
