@@ -100,6 +100,28 @@ def DelayProfile(RayListAnalysed, Detector, Bins=200):
     return _plots.DelayProfile(RayListAnalysed, Detector, Bins)
 
 
+def SpectrometerImage(OpticalChain, Detector, Wavelengths, Bins=200, Range=None, Show=True):
+    """What a spectrometer's camera sees: the spot images of `Wavelengths` (mm) behind a chain with one grating
+    (OpticalChain.get_SpectralRays: one fan-out launch), summed on the device into one X-Y histogram on Detector.
+    Returns (figure or None with Show=False, histogram.Histogram)."""
+    from . import histogram
+    h = histogram.spectrometer_histogram(Detector, OpticalChain.get_SpectralRays(Wavelengths), Bins, Range)
+    if not Show:
+        return None, h
+    from . import _plots
+    plt = _plots._plt()
+    fig, ax = plt.subplots()
+    img = h.intensity if h.intensity is not None else h.counts
+    im = ax.imshow(np.asarray(img).T, origin="lower", aspect="auto", interpolation="nearest",
+                   extent=[h.edges[0][0], h.edges[0][-1], h.edges[1][0], h.edges[1][-1]])
+    fig.colorbar(im).set_label("Intensity (arb.u.)" if h.intensity is not None else "Rays per bin")
+    ax.set_title("Spectrometer image, {} wavelengths".format(len(np.atleast_1d(Wavelengths))))
+    ax.set_xlabel("X (mm)")
+    ax.set_ylabel("Y (mm)")
+    fig._art_hist = h
+    return fig, h
+
+
 def MirrorFootprint(OpticalChain, ReflectionNumber: int, Bins=200):
     """Image of the footprint of all rays on one optical element, binned on the device, over its support outline."""
     from . import _plots

@@ -257,6 +257,9 @@ class Detector:
         t = RefPath / c.  Spectrum: a callable omega (rad/fs) -> complex amplitude replacing the transform-limited
         Gaussian (e.g. a chirp).  Gives I(x, y, t), the space-time Strehl ratio, the duration and the pulse front."""
         from . import pulse
+        if getattr(RayList, "grooves", None) is not None:
+            raise NotImplementedError("get_FocalPulse: these rays crossed a grating, so one bundle no longer serves all "
+                                      "frequencies; trace one bundle per wavelength with OpticalChain.get_SpectralRays")
         return pulse.focal_pulse(self, RayList, DeltaFT, Size, Pixels, Centre, Shifts, Wavelength, RefPath, Spectrum,
                                  TimeWindow, Times)
 

@@ -398,6 +398,66 @@ class DeformedMirror(_Mirror):
         return hash((hash(self.Mirror),) + tuple(hash(d) for d in self.DeformationList))
 
 
+class Grating(_Mirror):
+    """A classical ruled diffraction grating on any of the six mirror surfaces (no counterpart in the reference, whose
+    optics are achromatic).  The grooves are the intersections of the surface with equally spaced parallel planes,
+    `LinesPerMm` of them per millimetre along q0 = (cos GrooveAngle, sin GrooveAngle, 0) of the optic's own frame:
+    GrooveAngle (degrees) is measured from the optic's x axis, the element's `majoraxis`, which `OEPlacement` puts into
+    the plane of incidence -- 0 is the classical in-plane mount, 90 the conical (off-plane) mount.  `Order` is the
+    diffraction order m; LinesPerMm = 0 or Order = 0 is the bare mirror.  Traced by art_trace_grating
+    (include/art_hip.h); the wavelength is the traced bundle's."""
+
+    def __init__(self, Mirror, LinesPerMm, Order=1, GrooveAngle=0.0):
+        if isinstance(Mirror, (DeformedMirror, Grating)) or hasattr(Mirror, "DeformationList"):
+            raise ValueError("Grating: mirrors with defects (DeformedMirror) or gratings are not supported as substrates")
+        tname = getattr(Mirror, "type", None)
+        if not (isinstance(tname, str) and "Mirror" in tname) or getattr(Mirror, "_abi_kind", None) is None:
+            raise ValueError("Grating: the substrate must be one of the mirror classes (a Mask cannot carry a grating)")
+        N = float(LinesPerMm)
+        if not (math.isfinite(N) and N >= 0):
+            raise ValueError("Grating: LinesPerMm must be finite and >= 0")
+        if int(Order) != Order:
+            raise ValueError("Grating: Order must be an integer")
+        if not math.isfinite(float(GrooveAngle)):
+            raise ValueError("Grating: GrooveAngle must be finite")
+        self.Mirror = Mirror
+        self.lines_per_mm = N
+        self.order = int(Order)
+        self.groove_angle = float(GrooveAngle)
+        self.type = Mirror.type              # passes the '"Mirror" in type' checks, convex substrates included
+        self.support = Mirror.support
+
+    @property
+    def _abi_kind(self):
+        return self.Mirror._abi_kind
+
+    def _abi_params(self):
+        return self.Mirror._abi_params()
+
+    def _groove_vector(self):
+        """q0 in the optic's xy plane (exact for the two mounts: cos 90 deg is not 6e-17 here)."""
+        a = self.groove_angle % 360.0
+        exact = {0.0: (1.0, 0.0), 90.0: (0.0, 1.0), 180.0: (-1.0, 0.0), 270.0: (0.0, -1.0)}
+        if a in exact:
+            return exact[a]
+        return (math.cos(math.radians(a)), math.sin(math.radians(a)))
+
+    def get_normal(self, Point):
+        return self.Mirror.get_normal(Point)
+
+    def get_centre(self):
+        return self.Mirror.get_centre()
+
+    def _sag(self, x, y):
+        return self.Mirror._sag(x, y)
+
+    def get_grid3D(self, NbPoint, **kwargs):
+        return self.Mirror.get_grid3D(NbPoint, **kwargs)
+
+    def __hash__(self):
+        return hash((hash(self.Mirror), "grating", self.lines_per_mm, self.order, self.groove_angle))
+
+
 def ReflectionMirrorRayList(Mirror, ListRay, IgnoreDefects=False):
     """Reflect a bundle given in the mirror's own frame (ART/ModuleMirror.py:912-939): one identity-pose
     element on the device."""

@@ -168,6 +168,7 @@ class OpticalChain:
         ScratchBytes bounds the device scratch (the frequencies are then processed in blocks; the result does not
         depend on it)."""
         from . import vector_pulse
+        self._refuse_gratings("get_FocalPulse")
         return vector_pulse.vector_focal_pulse(self, Coatings, Detector, DeltaFT, Polarisation, Size, Pixels, Centre,
                                                Shifts, Wavelength, RefPath, Spectrum, TimeWindow, Times, ScratchBytes)
 
@@ -177,8 +178,30 @@ class OpticalChain:
         Detector.get_FocalField with get_Polarisation's complex field per ray as the amplitude, in the detector's
         components (e1, e2, normal)."""
         from . import vector_pulse
+        self._refuse_gratings("get_VectorFocalField")
         return vector_pulse.vector_focal_field(self, Coatings, Detector, Polarisation, Size, Pixels, Centre, Shifts,
                                                Wavelength, RefPath)
+
+    def _grating_indices(self):
+        return [k for k, oe in enumerate(self.optical_elements) if hasattr(oe.type, "lines_per_mm")]
+
+    def _refuse_gratings(self, what):
+        if self._grating_indices():
+            raise NotImplementedError(f"{what}: the chain contains a grating, so one bundle no longer serves all "
+                                      "frequencies; trace one bundle per wavelength with get_SpectralRays")
+
+    def get_SpectralRays(self, Wavelengths, Detector=None):
+        """The chain's final bundle at each of `Wavelengths` (mm), for a chain with ONE grating: the elements in front of
+        the grating are traced once, the grating fans the bundle out into one bundle per wavelength in ONE launch
+        (art_trace_grating), and the elements behind it are traced for all wavelengths in one many-chain launch.
+        Returns one bundle per wavelength, each with its `wavelength` and `grooves`.  Detector: a placed detector whose
+        read-out is fused behind the trace of every bundle."""
+        idx = self._grating_indices()
+        if len(idx) > 1:
+            raise NotImplementedError("get_SpectralRays: more than one grating in the chain")
+        if not idx:
+            raise ValueError("get_SpectralRays: the chain contains no grating")
+        return mp.RayTracingSpectral(self.source_rays, self.optical_elements, idx[0], Wavelengths, Detector)
 
     def get_FocalImage(self, Detector, RaysPerSource=None, **kw):
         """The partially coherent focal image (image.FocalImage) of the chain's final bundle on Detector:

@@ -80,6 +80,11 @@ def _build_descriptor(oe, IgnoreDefects, backend):
     d.flags = 0
     d.zern = None
     d.grid = None
+    d.grating = None
+    if hasattr(optic, "lines_per_mm"):
+        # ModuleMirror.Grating: traced by art_trace_grating only, one element per launch (like the recurrence layout)
+        d.flags |= _abi.ART_FLAG_GRATING
+        d.grating = optic
     if hasattr(optic, "DeformationList") and len(optic.DeformationList) > 0:
         be = backend or _lib.get_backend()
         keep = []
@@ -127,6 +132,23 @@ def _as_bundle(rays, backend=None):
 
 
 _CHAIN_MAX = 8          # elements per fused launch (kChainMax in csrc/art_scene.h)
+# elements the fused launches, the scene table and the guide kernel refuse: traced element by element, a launch each
+_STEPWISE_FLAGS = _abi.ART_FLAG_ZERN_RECURRENCE | _abi.ART_FLAG_GRATING
+
+
+def _trace_one(be, desc, vin, vout, n, wavelength, grooves):
+    """One element, one launch: art_trace_element, or art_trace_grating for a ModuleMirror.Grating at the bundle's
+    wavelength.  `grooves`: the groove counts the rays arrive with (device tensor [n] or None); returns those they leave
+    with -- the same object unless the element is a grating."""
+    if not desc.flags & _abi.ART_FLAG_GRATING:
+        be.trace_element(desc, vin, vout, n)
+        return grooves
+    if wavelength is None:
+        raise ValueError("tracing a Grating needs the wavelength of the ray bundle (RayBundle.wavelength is None)")
+    G = desc.grating
+    out = be.zeros(n)
+    be.trace_grating(desc, G._groove_vector(), G.lines_per_mm, G.order, [wavelength], vin, [vout], n, grooves, out)
+    return out
 
 
 # ------------------------------------------------------------------------------------------- the hot path
@@ -180,8 +202,10 @@ def RayTracingCalculation(source_rays, optical_elements, IgnoreDefects=True, mod
         descs.append(d)
         keep.append(k)
     mode = mode or DEFAULT_TRACE_MODE
-    if any(d.flags & _abi.ART_FLAG_ZERN_RECURRENCE for d in descs):
-        mode = "element"      # Zernike orders above 16 run the recurrences per ray: a kernel of its own, one element per launch
+    if any(d.flags & _STEPWISE_FLAGS for d in descs):
+        # Zernike orders above 16 run the recurrences per ray, a grating fans out in wavelength: kernels of their own, one
+        # element per launch
+        mode = "element"
     bad = next((k for k, d in enumerate(descs) if d.nonfinite), None)
     if bad is not None:
         # The reference meets a mirror with NaN/inf parameters in np.roots (ART/ModuleGeometry.py:84, :99), which
@@ -230,19 +254,51 @@ def RayTracingCalculation(source_rays, optical_elements, IgnoreDefects=True, mod
         if not history and m > 1:
             # ping-pong through one scratch bundle, in place
             cur = RayBundle.allocate(n, like=src, backend=be)
-            be.trace_element(descs[0], src.view(), cur.view(), n)
+            g = _trace_one(be, descs[0], src.view(), cur.view(), n, src.wavelength, src.grooves)
             for k in range(1, m - 1):
-                be.trace_element(descs[k], cur.view(), cur.view(), n)
-            be.trace_element(descs[m - 1], cur.view(), outs[-1].view(), n)
+                g = _trace_one(be, descs[k], cur.view(), cur.view(), n, src.wavelength, g)
+            outs[-1].grooves = _trace_one(be, descs[m - 1], cur.view(), outs[-1].view(), n, src.wavelength, g)
         else:
-            vin = src.view()
+            vin, g = src.view(), src.grooves
             for k in range(m):
                 vout = outs[k].view()
-                be.trace_element(descs[k], vin, vout, n)
+                g = outs[k].grooves = _trace_one(be, descs[k], vin, vout, n, src.wavelength, g)
                 vin = vout
     else:
         raise ValueError("mode must be 'chain' or 'element'")
     return outs
+
+
+def RayTracingSpectral(source_rays, optical_elements, grating_index, Wavelengths, detector=None, IgnoreDefects=True):
+    """The final bundle of a chain with ONE grating (element `grating_index`) at each of `Wavelengths` (mm): the
+    elements in front of the grating are traced once, ONE art_trace_grating launch reads that bundle once and writes one
+    diffracted bundle per wavelength, and the elements behind the grating are traced for all of them by the many-chain
+    launch (one source per chain).  Returns one bundle per wavelength with its `wavelength` and `grooves`."""
+    wls = [float(w) for w in np.atleast_1d(np.asarray(Wavelengths, dtype=float))]
+    if not 1 <= len(wls) <= _abi.ART_GRATING_MAX_WAVELENGTHS:
+        raise ValueError(f"Wavelengths: 1 to {_abi.ART_GRATING_MAX_WAVELENGTHS} values")
+    if not all(np.isfinite(w) and w > 0 for w in wls):
+        raise ValueError("Wavelengths must be finite and positive (mm)")
+    src = _as_bundle(source_rays)
+    be, n, k = src.backend, src.n_slots, int(grating_index)
+    head = RayTracingCalculation(src, optical_elements[:k], IgnoreDefects, history=False)[-1] if k > 0 else src
+    desc, _ = element_descriptor(optical_elements[k], IgnoreDefects, be)
+    G = desc.grating
+    if G is None:
+        raise ValueError("RayTracingSpectral: the element at grating_index is no Grating")
+    outs = [RayBundle.allocate(n, like=head, backend=be) for _ in wls]
+    grooves = be.zeros(len(wls) * n).view(len(wls), n)
+    keep = be.trace_grating(desc, G._groove_vector(), G.lines_per_mm, G.order, wls, head.view(), [b.view() for b in outs], n,
+                            head.grooves, grooves)
+    for j, b in enumerate(outs):
+        b.parent, b._keepalive = head, keep
+        b.wavelength, b.grooves = wls[j], grooves[j]
+    tail = list(optical_elements[k + 1:])
+    if not tail:
+        return outs
+    res = RayTracingCalculationMany(outs, [tail] * len(wls), IgnoreDefects, history=False,
+                                    detectors=None if detector is None else [detector] * len(wls))
+    return [r[-1] for r in res]
 
 
 class _ParentResolver:
@@ -389,7 +445,7 @@ def _RayTracingCalculationMany(source_rays_list, optical_elements_list, IgnoreDe
             keep.append(k)
     uniform = (m > 0 and n > 0 and all(len(els) == m for els in optical_elements_list)
                and all(s.n_slots == n and s.backend is be for s in sources) and not any(d.nonfinite for d in descs)
-               and not any(d.flags & _abi.ART_FLAG_ZERN_RECURRENCE for d in descs))
+               and not any(d.flags & _STEPWISE_FLAGS for d in descs))
     if detectors is not None and len(detectors) != c:
         raise ValueError("need one detector per chain")
     # Common prefix: a loop list varies ONE entry of one list (OEPlacement), so its chains start from equal sources and
@@ -525,6 +581,28 @@ def _placeChains(SourceProperties, OpticsList, variants, Description):
     return chains
 
 
+def _explain_lost_guide(one, element):
+    """The guide ray did not come back from a grating: if it does hit the substrate, its order is evanescent there --
+    raise ValueError with the numbers of the grating equation (otherwise return: the ray missed, as on a mirror)."""
+    G = element.type
+    bare = moe.OpticalElement(G.Mirror, element.position, element.normal, element.majoraxis)
+    hit = RayTracingCalculation(one, [bare])[-1]
+    if len(hit) == 0:
+        return
+    u = one.data[3:6, 0].cpu().numpy()
+    v = hit.data[3:6, 0].cpu().numpy()
+    nrm = (u - v) / np.linalg.norm(u - v)                       # the mirror's v = u - 2 (u.n) n
+    fwd, _ = mgeo.frame_maps(element.normal, element.majoraxis)
+    qx, qy = G._groove_vector()
+    mlN = G.order * one.wavelength * G.lines_per_mm
+    g = fwd.T @ (mlN * np.array([qx, qy, 0.0]))
+    vt = (u - u.dot(nrm) * nrm) + (g - g.dot(nrm) * nrm)
+    raise ValueError(f"Grating: the order m = {G.order} is evanescent for the guide ray at wavelength {one.wavelength:g} mm "
+                     f"with {G.lines_per_mm:g} lines/mm: m*lambda*N = {mlN:.6g}, incidence "
+                     f"{np.degrees(np.arccos(abs(u.dot(nrm)))):.6g} deg (sin = {np.sqrt(max(0.0, 1 - u.dot(nrm) ** 2)):.6g}), "
+                     f"|v_t|^2 = {vt.dot(vt):.6g} > 1, so sqrt(1 - |v_t|^2) does not exist")
+
+
 def _placeChainsOn(be, Source, OpticsList, variants, Description, c):
     from . import ModuleOpticalChain as moc
     plane_angles = [[np.deg2rad(a % 360) for a in v[2]] for v in variants]
@@ -546,7 +624,7 @@ def _placeChainsOn(be, Source, OpticsList, variants, Description, c):
             # a mirror with NaN / inf parameters: the reference's np.roots raises for the first ray that reaches it
             # (see RayTracingCalculation), and the guide ray always does
             raise np.linalg.LinAlgError("Array must not contain infs or NaNs")
-        slow = [j for j, d in enumerate(descs) if d.flags & _abi.ART_FLAG_ZERN_RECURRENCE]
+        slow = [j for j, d in enumerate(descs) if d.flags & _STEPWISE_FLAGS]
         if not slow:
             be.trace_guides(descs, guides, guide_alive)
             return
@@ -554,9 +632,11 @@ def _placeChainsOn(be, Source, OpticsList, variants, Description, c):
         for j in range(c):
             if not al[j]:
                 continue
-            one = RayBundle.from_arrays(host[j, 0:3], host[j, 3:6], path0=host[j, 6], backend=be)
+            one = RayBundle.from_arrays(host[j, 0:3], host[j, 3:6], wavelength=Source.wavelength, path0=host[j, 6], backend=be)
             out = RayTracingCalculation(one, [through[j]])[-1]
             if len(out) == 0:
+                if descs[j].flags & _abi.ART_FLAG_GRATING:
+                    _explain_lost_guide(one, through[j])
                 al[j] = 0
             else:
                 host[j] = out.data[:, 0].cpu().numpy()

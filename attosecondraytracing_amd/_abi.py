@@ -16,6 +16,7 @@ ART_SUP_ROUND, ART_SUP_ROUNDHOLE, ART_SUP_RECT, ART_SUP_RECTHOLE, ART_SUP_RECTRE
 
 ART_FLAG_PERTURBED_NORMAL = 1
 ART_FLAG_ZERN_RECURRENCE = 2
+ART_FLAG_GRATING = 4
 ART_ZERN_RECURRENCE_MAX_ORDER = 64
 
 ART_ZERN_MAX_ORDER = 16
@@ -58,6 +59,22 @@ class ArtBundleView(C.Structure):
         ("path", C.c_void_p),
         ("incidence", C.c_void_p),
         ("alive", C.c_void_p),
+    ]
+
+
+ART_GRATING_MAX_WAVELENGTHS = 1024
+
+
+class ArtGratingDesc(C.Structure):
+    _fields_ = [
+        ("q", C.c_double * 2),
+        ("lines_per_mm", C.c_double),
+        ("order", C.c_int32),
+        ("nw", C.c_int32),
+        ("wavelengths", C.c_void_p),
+        ("outs", C.c_void_p),
+        ("grooves_in", C.c_void_p),
+        ("grooves_out", C.c_void_p),
     ]
 
 
@@ -256,6 +273,8 @@ PROTOTYPES = {
     "art_device_count": (C.c_int, []),
     "art_trace_element": (C.c_int, [C.POINTER(ArtElementDesc), C.POINTER(ArtBundleView), C.POINTER(ArtBundleView),
                                     C.c_int64, C.c_void_p]),
+    "art_trace_grating": (C.c_int, [C.POINTER(ArtElementDesc), C.POINTER(ArtGratingDesc), c_double_p,
+                                    C.POINTER(ArtBundleView), C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
     "art_trace_chain": (C.c_int, [C.POINTER(ArtElementDesc), C.c_int32, C.POINTER(ArtBundleView),
                                   C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
     "art_scene_bytes": (C.c_int64, [C.c_int32, C.c_int32]),

@@ -125,6 +125,27 @@ class HipBackend:
         self.check(self._timed(lambda: self.fn["art_trace_element"](C.byref(desc), C.byref(view_in),
                                                                     C.byref(view_out), n, sp)), "art_trace_element")
 
+    def trace_grating(self, desc, q, lines_per_mm, order, wavelengths, view_in, views_out, n, grooves_in=None,
+                      grooves_out=None):
+        """art_trace_grating: `desc` (an ArtElementDesc with ART_FLAG_GRATING) diffracts the bundle `view_in` into one
+        bundle per wavelength (mm) in ONE launch.  grooves_in: device tensor [n] or None; grooves_out: device tensor
+        [len(wavelengths), n] (contiguous) or None."""
+        nw = len(wavelengths)
+        wl_host = (C.c_double * nw)(*[float(w) for w in wavelengths])
+        varr = (_abi.ArtBundleView * nw)(*views_out)
+        wl_dev = self.from_numpy(np.array([float(w) for w in wavelengths], dtype=np.float64))
+        v_dev = self.from_numpy(np.frombuffer(bytes(varr), dtype=np.uint8).copy())
+        g = _abi.ArtGratingDesc()
+        g.q[0], g.q[1] = float(q[0]), float(q[1])
+        g.lines_per_mm, g.order, g.nw = float(lines_per_mm), int(order), nw
+        g.wavelengths, g.outs = wl_dev.data_ptr(), v_dev.data_ptr()
+        g.grooves_in = None if grooves_in is None else grooves_in.data_ptr()
+        g.grooves_out = None if grooves_out is None else grooves_out.data_ptr()
+        sp = self.stream_ptr()
+        self.check(self._timed(lambda: self.fn["art_trace_grating"](C.byref(desc), C.byref(g), wl_host, varr,
+                                                                    C.byref(view_in), n, sp)), "art_trace_grating")
+        return wl_dev, v_dev          # (read by the launch: the caller keeps them alive with the outputs)
+
     def trace_chain(self, descs, view_in, views_out, n, readout=None):
         """art_trace_chain, or art_trace_chain_readout when `readout` (from new_chain_readout) is given."""
         m = len(descs)

@@ -23,12 +23,15 @@ _SERIAL = itertools.count(1)   # identity of a bundle for change detection (id()
 
 
 class RayBundle:
-    def __init__(self, data, alive, number=None, intensity=None, wavelength=None, parent=None, backend=None):
+    def __init__(self, data, alive, number=None, intensity=None, wavelength=None, parent=None, backend=None, grooves=None):
         self.data = data              # torch float64 [8, n]
         self.alive = alive            # torch uint8 [n]
         self.number = number          # torch int64 [n] or None (= slot index)
         self.intensity = intensity    # torch float64 [n] or None
         self.wavelength = wavelength  # float or None (uniform, as every reference source produces)
+        # torch float64 [n] or None: sum of m * G(P) over the gratings the rays met (ModuleMirror.Grating); None for every
+        # bundle that met no grating.  The phase of a ray in a coherent analysis is k * path + 2 pi * grooves.
+        self.grooves = grooves
         self._parent = parent         # bundle this one was traced from (for Ray.path tuples); see `parent`
         self._parent_resolver = None  # lazy history (ModuleProcessing.LazyHistory): called once, sets the real parent
         self._backend = backend or _lib.get_backend()
@@ -95,6 +98,7 @@ class RayBundle:
             self.data, self.alive = data, alive
             self.number = None if self.number is None else self.number.to(be.device)
             self.intensity = None if self.intensity is None else self.intensity.to(be.device)
+            self.grooves = None if self.grooves is None else self.grooves.to(be.device)
             self._backend = be
         return self._backend
 
@@ -103,7 +107,7 @@ class RayBundle:
         host = lambda t: None if t is None else t.detach().cpu().numpy()
         return {"data": host(self.data), "alive": host(self.alive), "number": host(self.number),
                 "intensity": host(self.intensity), "wavelength": self.wavelength, "parent": self.parent,
-                "version": self.version, "path_head": self.path_head}
+                "version": self.version, "path_head": self.path_head, "grooves": host(self.grooves)}
 
     def __setstate__(self, st):
         t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a))
@@ -112,6 +116,7 @@ class RayBundle:
         self._parent_resolver = None
         self.wavelength, self.parent, self.version = st["wavelength"], st["parent"], st["version"]
         self.path_head = st.get("path_head")
+        self.grooves = t(st.get("grooves"))
         self._backend = None
         self._index = None
         self._count = None
@@ -148,7 +153,7 @@ class RayBundle:
         be = backend or (like.backend if like is not None else _lib.get_backend())
         data, alive = cls._rows(n, be.device)
         if like is not None:
-            return cls(data, alive, like.number, like.intensity, like.wavelength, like, be)
+            return cls(data, alive, like.number, like.intensity, like.wavelength, like, be, like.grooves)
         return cls(data, alive, backend=be)
 
     @classmethod
@@ -157,14 +162,16 @@ class RayBundle:
         history of one chain."""
         be = backend or like.backend
         data, alive = cls._rows(n, be.device, count)
-        return [cls(data[k], alive[k], like.number, like.intensity, like.wavelength, like, be) for k in range(count)]
+        return [cls(data[k], alive[k], like.number, like.intensity, like.wavelength, like, be, like.grooves)
+                for k in range(count)]
 
     @classmethod
     def allocate_grid(cls, n, chains, count, likes, backend=None):
         """[chains][count] bundles out of two allocations: the histories of a list of chains traced in one launch."""
         be = backend or likes[0].backend
         data, alive = cls._rows(n, be.device, (chains, count))
-        return [[cls(data[c, k], alive[c, k], likes[c].number, likes[c].intensity, likes[c].wavelength, likes[c], be)
+        return [[cls(data[c, k], alive[c, k], likes[c].number, likes[c].intensity, likes[c].wavelength, likes[c], be,
+                     likes[c].grooves)
                  for k in range(count)] for c in range(chains)]
 
     @classmethod
@@ -223,6 +230,33 @@ class RayBundle:
         v.alive = self.alive.data_ptr()
         return v
 
+    def phase_path_view(self, wavelength=None):
+        """(ArtBundleView, keepalive) for the COHERENT analyses (focal fields, images, wavefronts) at `wavelength` (default
+        the bundle's): the view of this bundle, with `path` pointing at path + wavelength * grooves when the rays crossed
+        a grating -- k times that is the phase k * path + 2 pi * grooves.  The kernels are the same; delays, histograms
+        and read-outs keep the geometric path (view())."""
+        v = self.view()
+        if self.grooves is None:
+            return v, None
+        wavelength = self.wavelength if wavelength is None else wavelength
+        if wavelength is None:
+            raise ValueError("a bundle that crossed a grating needs a wavelength for a coherent analysis")
+        eff = torch.add(self.data[ROW_PATH], self.grooves, alpha=float(wavelength)).contiguous()
+        v.path = eff.data_ptr()
+        return v, eff
+
+    def phase_ref_offset(self, wavelength=None):
+        """wavelength * (mean groove count of the alive rays): what the default reference path of a coherent analysis (the
+        mean geometric optical path) is shifted by for a bundle that crossed a grating; 0.0 otherwise."""
+        if self.grooves is None:
+            return 0.0
+        wavelength = self.wavelength if wavelength is None else wavelength
+        alive = self.alive != 0
+        cnt = int(alive.sum())
+        if cnt == 0 or wavelength is None:
+            return 0.0
+        return float(wavelength) * float(torch.where(alive, self.grooves, 0.0).sum()) / cnt
+
     def slots(self, lo, hi):
         """A bundle OBJECT over slots [lo, hi) of this one's arrays (no copy: the rows are unit-stride streams, a range of
         slots is a range of every row).  For tiled launches: the tiles of one trace write disjoint ranges of the same
@@ -230,7 +264,7 @@ class RayBundle:
         lo, hi = int(lo), int(hi)
         cut = lambda t: None if t is None else t[lo:hi]
         out = RayBundle(self.data[:, lo:hi], self.alive[lo:hi], cut(self.number), cut(self.intensity), self.wavelength, None,
-                        self._backend)
+                        self._backend, cut(self.grooves))
         if self.number is None and lo != 0:
             out.number = torch.arange(lo, hi, dtype=torch.int64, device=self.alive.device)     # slot i of the range is ray lo + i
         return out
@@ -367,7 +401,7 @@ class RayBundle:
         pos = torch.as_tensor(np.asarray(positions, dtype=np.int64), device=self.backend.device)
         alive = torch.zeros_like(self.alive)
         alive[idx.index_select(0, pos)] = 1
-        out = RayBundle(self.data, alive, self.number, self.intensity, self.wavelength, self._parent, self.backend)
+        out = RayBundle(self.data, alive, self.number, self.intensity, self.wavelength, self._parent, self.backend, self.grooves)
         self._share_parent(out)
         out.path_head = self.path_head
         self._share_grouping(out)
@@ -388,7 +422,7 @@ class RayBundle:
         data, alive = self._rows(self.n_slots, self.data.device)
         data.copy_(self.data)
         alive.copy_(self.alive)
-        out = RayBundle(data, alive, self.number, self.intensity, self.wavelength, self._parent, self.backend)
+        out = RayBundle(data, alive, self.number, self.intensity, self.wavelength, self._parent, self.backend, self.grooves)
         self._share_parent(out)
         out.path_head = self.path_head
         self._share_grouping(out)
@@ -399,7 +433,8 @@ class RayBundle:
         """A new bundle OBJECT over the same device arrays (attributes such as `intensity` can be replaced per object;
         the arrays themselves are shared and must be treated as immutable -- `copy()` gives private storage).  What the
         chains of an OEPlacement loop list hold of their common source."""
-        out = RayBundle(self.data, self.alive, self.number, self.intensity, self.wavelength, self._parent, self.backend)
+        out = RayBundle(self.data, self.alive, self.number, self.intensity, self.wavelength, self._parent, self.backend,
+                        self.grooves)
         self._share_parent(out)
         out.path_head = self.path_head
         self._share_grouping(out)

@@ -905,6 +905,93 @@ ART_HD bool trace_ray_dyn(const ArtElementDesc& e, const double* zern, Ray& r) {
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Diffraction grating ruled on an undeformed mirror (ART_FLAG_GRATING, art_trace_grating; the reference has no
+// wavelength-dependent optic).  The grooves are the intersections of the surface with equally spaced parallel planes
+// (a classical ruled grating): the groove number at a surface point P is
+//     G(P) = N q0.(P - c),     q0 = (cos a, sin a, 0) in the optic frame, N lines per mm, c = e.centre.
+// A ray that crosses the grating in order m collects the phase 2 pi m G(P) besides k * path: the phase of a ray in any
+// coherent analysis is  k * path + 2 pi * grooves,  grooves = sum over the gratings met of m G(P).
+// Direction of the diffracted ray, by Fermat's principle: for an incident plane wave u and an outgoing one v the phase
+// collected through the surface point x is
+//     phi(x) = k u.x + 2 pi m G(x) - k v.x ,
+// and the order exists where phi is stationary for x moving IN the surface: for every tangent tau at P
+//     k u.tau + 2 pi m N q0.tau - k v.tau = 0    <=>    v.tau = u.tau + m lambda N q0.tau ,
+// i.e. with g = m lambda N q0 and the unit normal n
+//     g_t = g - (g.n) n,   v_t = (u - (u.n) n) + g_t,   s = 1 - |v_t|^2,   v = v_t - sign(u.n) sqrt(s) n
+// (the ray leaves on the side it came from); s <= 0: the order is evanescent and the ray is lost.  g = 0 gives the
+// mirror's v = u - 2 (u.n) n.  The groove term enters with a PLUS sign next to u.tau: a wrong sign tilts the diffracted
+// wavefront by twice the dispersion angle (tests/test_gpu_grating.py, the flat-wavefront test).
+// s is formed without the cancellation of 1 - |v_t|^2 at grazing incidence: |u - (u.n) n|^2 = 1 - (u.n)^2 for unit u, n,
+// hence s = (u.n)^2 - (2 u_t.g_t + |g_t|^2), which is (u.n)^2 exactly for g = 0.
+//
+// Everything up to and including the normal does not depend on the wavelength: grating_hit() forms it once per ray,
+// grating_diffract() once per ray and wavelength.
+struct GratingHit {
+  double Px, Py, Pz;        // hit point, optic frame
+  double nx, ny, nz;        // unit normal there
+  double utx, uty, utz;     // u - (u.n) n
+  double dn;                // u.n
+  double t;                 // ray parameter of the hit = geometric path of this leg (|u| = 1)
+  double inc;               // incidence angle, as for a mirror
+  double G;                 // groove number N q0.(P - c)
+};
+
+template <int KIND>
+ART_HD bool grating_hit(const ArtElementDesc& e, const Ray& r, double qx, double qy, double N, GratingHit& h) {
+  double Ax, Ay, Az, ux, uy, uz;
+  mat3_apply_off(e.fwd, e.ART_D_IN_OFF, r.ox, r.oy, r.oz, Ax, Ay, Az);
+  mat3_apply(e.fwd, r.dx, r.dy, r.dz, ux, uy, uz);
+  double t;
+  if (!intersect_k<KIND>(e, Ax, Ay, Az, ux, uy, uz, t)) return false;
+  h.Px = fma(t, ux, Ax); h.Py = fma(t, uy, Ay); h.Pz = fma(t, uz, Az);
+  base_normal_k<KIND>(e, h.Px, h.Py, h.Pz, h.nx, h.ny, h.nz);
+  const double dn = dot3(ux, uy, uz, h.nx, h.ny, h.nz);
+  h.utx = fma(-dn, h.nx, ux); h.uty = fma(-dn, h.ny, uy); h.utz = fma(-dn, h.nz, uz);
+  h.dn = dn;
+  h.t = t;
+  h.inc = kahan_angle_unit(-ux, -uy, -uz, h.nx, h.ny, h.nz, -dn);
+  h.G = N * fma(qx, h.Px - e.centre[0], qy * (h.Py - e.centre[1]));
+  return true;
+}
+
+// (gx, gy) = m lambda N q0.  `out` receives the diffracted ray in the lab frame (path = path_in + t); returns false,
+// with `out` holding nothing of value, for an evanescent order.  Branch-free: the wavelength loop stays wave-uniform.
+ART_HD bool grating_diffract(const ArtElementDesc& e, const GratingHit& h, double gx, double gy, double path_in, Ray& out) {
+  const double gn = fma(gx, h.nx, gy * h.ny);
+  const double gtx = fma(-gn, h.nx, gx), gty = fma(-gn, h.ny, gy), gtz = -gn * h.nz;
+  const double vtx = h.utx + gtx, vty = h.uty + gty, vtz = h.utz + gtz;
+  const double s = fma(h.dn, h.dn, -fma(2.0, dot3(h.utx, h.uty, h.utz, gtx, gty, gtz), dot3(gtx, gty, gtz, gtx, gty, gtz)));
+  const bool ok = s > 0.0;
+  double sq, rs;
+  sqrt_rsqrt(ok ? s : 1.0, sq, rs);
+  const double k = copysign(sq, h.dn);
+  const double vx = fma(-k, h.nx, vtx), vy = fma(-k, h.ny, vty), vz = fma(-k, h.nz, vtz);
+  double dx, dy, dz;
+  mat3t_apply_off(e.fwd, e.ART_D_OUT_OFF, h.Px, h.Py, h.Pz, out.ox, out.oy, out.oz);
+  mat3t_apply(e.fwd, vx, vy, vz, dx, dy, dz);
+  const double s2 = dot3(dx, dy, dz, dx, dy, dz);      // renormalised as in trace_ray
+  const double kk = fma(-0.5, s2, 1.5);
+  out.dx = dx * kk; out.dy = dy * kk; out.dz = dz * kk;
+  out.path = path_in + h.t;
+  out.inc = h.inc;
+  return ok;
+}
+
+// One ray, one wavelength (mm), any mirror kind: what art_trace_grating computes per ray and wavelength.  `e` is a
+// PREPARED descriptor.  A lost ray (miss or evanescent order) leaves r and grooves untouched.
+ART_HD bool grating_ray(const ArtElementDesc& e, double qx, double qy, double N, int order, double wavelength, Ray& r,
+                        double& grooves) {
+  GratingHit h;
+  if (!grating_hit<ART_KIND_DYN>(e, r, qx, qy, N, h)) return false;
+  const double sc = (double)order * wavelength * N;
+  Ray o;
+  if (!grating_diffract(e, h, sc * qx, sc * qy, r.path, o)) return false;
+  r = o;
+  grooves += (double)order * h.G;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Detector read-out for one ray (ART/ModuleDetector.py:191-234, :272-275; ModuleGeometry.py:48-57)
 ART_HD void detector_ray(const ArtDetectorDesc& d, const Ray& r, double& Ix, double& Iy, double& Iz, double& X,
                          double& Y, double& opl) {

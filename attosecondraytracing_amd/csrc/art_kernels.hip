@@ -677,6 +677,44 @@ __global__ __launch_bounds__(kBlock) void k_trace_element_zrec(const ElemArg ea,
   store_slot(bo, i, r, ok);
 }
 
+// Grating (ART_FLAG_GRATING, art_device.h grating_hit / grating_diffract): one ray per thread, any mirror kind (run-time
+// switch, wave-uniform).  The input slot is read ONCE; frame change, intersection, support test and normal are formed
+// once; then the thread loops over the nw wavelengths with the hit in registers and stores one diffracted ray each.
+// The wavelengths and the output views are the same for every lane: read through the constant address space, i.e.
+// scalar loads into SGPRs (one copy per wave).  Stores of lost rays and of slots >= n are dropped by the range check.
+__global__ __launch_bounds__(kBlock) void k_trace_grating(const ElemArg ea, const ArtGratingDesc g, const ArtBundleView in,
+                                                          const int64_t n) {
+  const ArtElementDesc& e = ea.e[blockIdx.y];
+  const BundleRsrc bi = make_rsrc(in, n);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const unsigned o8 = (unsigned)i * 8u, nb8 = (unsigned)(n * 8);
+  art::Ray r;
+  r.inc = 0.0;
+  uint8_t a;
+  load_slot(bi, i, r, a);
+  const double g_in = ld_f64(rsrc_of(g.grooves_in, g.grooves_in ? nb8 : 0u), o8);     // NULL: every load reads 0
+  art::GratingHit h = {};
+  bool hit = a != 0;
+  if (hit) hit = art::grating_hit<ART_KIND_DYN>(e, r, g.q[0], g.q[1], g.lines_per_mm, h);
+  const double g_out = g_in + (double)g.order * h.G;
+  const art::zuni_t wl = ART_ZUNI(g.wavelengths);
+  typedef const uint64_t __attribute__((address_space(4)))* uview_t;
+  const uview_t vp = (uview_t)(const void*)g.outs;
+  static_assert(sizeof(ArtBundleView) == 9 * sizeof(uint64_t), "ArtBundleView is nine pointers");
+  for (int j = 0; j < g.nw; ++j) {
+    const double sc = (double)g.order * wl[j] * g.lines_per_mm;
+    ArtBundleView v;
+    v.ox = (double*)vp[9 * j + 0]; v.oy = (double*)vp[9 * j + 1]; v.oz = (double*)vp[9 * j + 2];
+    v.dx = (double*)vp[9 * j + 3]; v.dy = (double*)vp[9 * j + 4]; v.dz = (double*)vp[9 * j + 5];
+    v.path = (double*)vp[9 * j + 6]; v.incidence = (double*)vp[9 * j + 7]; v.alive = (uint8_t*)vp[9 * j + 8];
+    art::Ray o;
+    const bool ok = art::grating_diffract(e, h, sc * g.q[0], sc * g.q[1], r.path, o) && hit;
+    store_slot(make_rsrc(v, n), i, o, ok);
+    double* go = g.grooves_out ? g.grooves_out + (int64_t)j * n : nullptr;
+    st_f64(rsrc_of(go, go ? nb8 : 0u), ok ? o8 : kDropOffset, g_out);
+  }
+}
+
 using art::ChainArgs;
 using art::kChainMax;
 
@@ -3234,6 +3272,8 @@ int check_elem(const ArtElementDesc* e) {
   return ART_OK;
 }
 
+const char* const kGratingRefusal = "an element is a grating: trace it with art_trace_grating";
+
 template <int KIND>
 void launch_element(const ArtElementDesc& e, const ArtBundleView& in, const ArtBundleView& out, int64_t n,
                     hipStream_t s) {
@@ -3451,6 +3491,7 @@ int art_trace_element(const ArtElementDesc* e, const ArtBundleView* in, const Ar
                       void* stream) {
   int rc = check_elem(e);
   if (rc) return rc;
+  if (e->flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   if (n == 0) return ART_OK;  // an empty bundle has no arrays to point to
   if (!view_ok(in) || !view_ok(out)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
@@ -3479,6 +3520,35 @@ int art_trace_element(const ArtElementDesc* e, const ArtBundleView* in, const Ar
   return launched("art_trace_element launch");
 }
 
+int art_trace_grating(const ArtElementDesc* e, const ArtGratingDesc* g, const double* wavelengths_host,
+                      const ArtBundleView* outs_host, const ArtBundleView* in, int64_t n, void* stream) {
+  int rc = check_elem(e);
+  if (rc) return rc;
+  if (e->kind == ART_MASK) return fail(ART_ERR_BAD_ARG, "art_trace_grating: a mask cannot be a grating");
+  if (e->n_defects > 0 || e->n_grid > 0) return fail(ART_ERR_BAD_ARG, "art_trace_grating: mirrors with defects are not supported as substrates");
+  if (!g || !wavelengths_host || !outs_host) return fail(ART_ERR_BAD_ARG, "art_trace_grating: NULL argument");
+  if (!(fabs(g->q[0] * g->q[0] + g->q[1] * g->q[1] - 1.0) <= 1e-12)) return fail(ART_ERR_BAD_ARG, "art_trace_grating: q must be a unit vector");
+  if (!(isfinite(g->lines_per_mm) && g->lines_per_mm >= 0.0)) return fail(ART_ERR_BAD_ARG, "art_trace_grating: lines_per_mm must be finite and >= 0");
+  if (g->nw < 1 || g->nw > ART_GRATING_MAX_WAVELENGTHS) return fail(ART_ERR_BAD_ARG, "art_trace_grating: nw must be in 1..ART_GRATING_MAX_WAVELENGTHS");
+  for (int j = 0; j < g->nw; ++j)
+    if (!(isfinite(wavelengths_host[j]) && wavelengths_host[j] > 0.0)) return fail(ART_ERR_BAD_ARG, "art_trace_grating: every wavelength must be finite and > 0");
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (n > kMaxRaysPerLaunchHw) return fail(ART_ERR_UNSUPPORTED, "art_trace_grating: more rays than one launch covers");
+  if (n == 0) return ART_OK;  // an empty bundle has no arrays to point to
+  if (!g->wavelengths || !g->outs) return fail(ART_ERR_BAD_ARG, "art_trace_grating: device arrays of wavelengths / views missing");
+  if (!view_ok(in)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
+  for (int j = 0; j < g->nw; ++j) {
+    if (!view_ok(&outs_host[j])) return fail(ART_ERR_BAD_ARG, "an output view has a NULL array");
+    if (g->nw > 1 && (outs_host[j].ox == in->ox || outs_host[j].alive == in->alive))
+      return fail(ART_ERR_BAD_ARG, "art_trace_grating: an output may alias the input only when nw == 1");
+  }
+  ElemArg ea;
+  ea.e[0] = *e;
+  art::prepare_element(ea.e[0]);
+  hipLaunchKernelGGL(k_trace_grating, dim3(grid_stream(n)), dim3(kBlock), 0, (hipStream_t)stream, ea, *g, *in, n);
+  return launched("art_trace_grating launch");
+}
+
 static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const ArtBundleView* in,
                             const ArtBundleView* outs, const ArtChainReadout* ro, int64_t n, void* stream) {
   if (!elems || !outs || n_elems <= 0) return fail(ART_ERR_BAD_ARG, "empty chain");
@@ -3488,6 +3558,7 @@ static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const 
     if (rc) return rc;
     if (elems[k].flags & ART_FLAG_ZERN_RECURRENCE)
       return fail(ART_ERR_UNSUPPORTED, "an element carries Zernike tables in the recurrence layout: trace it with art_trace_element");
+    if (elems[k].flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
   }
   hipStream_t s = (hipStream_t)stream;
   if (ro) {
@@ -4472,6 +4543,7 @@ int art_trace_guides(const ArtElementDesc* elems, int32_t count, double* rays, u
     if (rc) return rc;
     if (elems[k].flags & ART_FLAG_ZERN_RECURRENCE)
       return fail(ART_ERR_UNSUPPORTED, "an element carries Zernike tables in the recurrence layout: trace it with art_trace_element");
+    if (elems[k].flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
     ga.e[k] = elems[k];
     art::prepare_element(ga.e[k]);
     defects = defects || ga.e[k].n_defects > 0 || ga.e[k].n_grid > 0;

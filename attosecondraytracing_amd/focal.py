@@ -113,7 +113,8 @@ def focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath):
     bbox = (0.5 * (s[2] + s[3]), 0.5 * (s[4] + s[5])) if alive else None
     pix, sizes, centre, shifts = resolve_grid(Size, Pixels, Centre, Shifts, wavelength,
                                               lambda: mp.ReturnNumericalAperture(B, 1) if alive else 0.0, bbox)
-    ref = (s[1] / s[0] if alive else 0.0) if RefPath is None else float(RefPath)
+    # (behind a grating the phase path is path + wavelength * grooves: bundle.RayBundle.phase_path_view)
+    ref = ((s[1] / s[0] if alive else 0.0) + B.phase_ref_offset(wavelength)) if RefPath is None else float(RefPath)
     x0, dx, x = pixel_axis(centre[0], sizes[0], pix[0])
     y0, dy, y = pixel_axis(centre[1], sizes[1], pix[1])
     fd = _abi.ArtFocalDesc()
@@ -136,5 +137,6 @@ def focal_field(det, RayList, Size=None, Pixels=128, Centre=None, Shifts=None, W
     All planes are summed in one device call."""
     B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
     fd, x, y, shifts, wavelength, ref, _ = focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
-    field = B.backend.focal_field(fd, B.view(), B.intensity, B.n_slots)
+    view, _keep = B.phase_path_view(wavelength)
+    field = B.backend.focal_field(fd, view, B.intensity, B.n_slots)
     return FocalField(field, x, y, shifts, wavelength, ref, amplitude_sum(B))

@@ -251,7 +251,7 @@ class SceneProgram:
             return False
         descs = [self._mp.element_descriptor(oe, self.IgnoreDefects, self.be)[0] for els in element_lists for oe in els]
         return (self._structure(element_lists, descs) == self._signature and not any(d.nonfinite for d in descs)
-                and any(d.flags & self._abi.ART_FLAG_ZERN_RECURRENCE for d in descs) == self._stepwise)
+                and any(d.flags & self._mp._STEPWISE_FLAGS for d in descs) == self._stepwise)
 
     def update(self, element_lists):
         """New poses / parameters for the same optics: re-pack the table and copy it over the device image."""
@@ -270,12 +270,13 @@ class SceneProgram:
         # A Zernike defect above order 16 runs the reference's recurrences per ray in a kernel of its own (art_trace_element
         # only: per-lane row storage): a program that contains one is STEPWISE -- one launch per element into the same
         # preallocated bundles, descriptors as kernel arguments (so: eager launches, no captured graph, no fused read-out)
-        stepwise = any(d.flags & self._abi.ART_FLAG_ZERN_RECURRENCE for d in descs)
+        # -- and so is one that contains a grating (art_trace_grating only)
+        stepwise = any(d.flags & self._mp._STEPWISE_FLAGS for d in descs)
         if stepwise and (not self._history or self.readouts is not None):
-            raise ValueError("a SceneProgram with a Zernike defect above order 16 is traced element by element: it needs "
+            raise ValueError("a SceneProgram with a Zernike defect above order 16 or a grating is traced element by element: it needs "
                              "history=True and cannot carry fused read-outs (detectors=None; Detector.readout works)")
         if self._stepwise is not None and stepwise != self._stepwise:
-            raise ValueError("SceneProgram.update: the optics changed (a Zernike order crossed 16); build a new program")
+            raise ValueError("SceneProgram.update: the optics changed (a Zernike order crossed 16, or a grating); build a new program")
         self._stepwise = stepwise
         if stepwise:
             self._descs, self._keep = descs, keep
@@ -306,10 +307,12 @@ class SceneProgram:
     def _launch(self):
         if self._stepwise:
             for ci in range(self.c):
-                vin = self._views_in[ci]
+                vin, src = self._views_in[ci], self.sources[ci]
+                g = src.grooves
                 for k in range(self.m):
                     vout = self._views_out[ci * self.m + k]
-                    self.be.trace_element(self._descs[ci * self.m + k], vin, vout, self.n)
+                    g = self._mp._trace_one(self.be, self._descs[ci * self.m + k], vin, vout, self.n, src.wavelength, g)
+                    self.outputs[ci][k].grooves = g
                     vin = vout
         else:
             self.be.trace_scene(self.dev, self.host, self.n, segments=-(-self.m // 8))

@@ -109,6 +109,42 @@ def detector_histogram(det, RayList, Axes=("X", "Y"), Bins=100, Range=None):
     return bin_bundle(B, desc, [_DETECTOR_AXES[a] for a in Axes], per_axis_bins(Bins, len(Axes)), ranges)
 
 
+def spectrometer_histogram(det, bundles, Bins=200, Range=None):
+    """ModuleAnalysisAndPlots.SpectrometerImage: the X-Y spot histograms of several bundles (one per wavelength,
+    OpticalChain.get_SpectralRays) on one detector, SUMMED on the device -- art_histogram with accumulate = 1 into the
+    first bundle's bins, one fixed-point shift for all of them, so the sum is exact.  Range defaults to the joint
+    bounding box of the alive rays."""
+    import torch
+    Bs = [as_bundle(b) for b in bundles]
+    if not Bs:
+        raise ValueError("no bundle to bin")
+    stats = [det.readout(B, store=False, lite=True)["stats"] for B in Bs]
+    live = [s for s in stats if s[0] > 0]
+    lims = [(min(s[2 + 2 * k] for s in live), max(s[3 + 2 * k] for s in live)) for k in range(2)] if live else [(0.0, 1.0)] * 2
+    ranges = per_axis_ranges(Range, 2, lambda k: lims[k])
+    bins = per_axis_bins(Bins, 2)
+    desc = _abi.ArtHistogramDesc()
+    desc.source = _abi.ART_HIST_DETECTOR
+    desc.map = det._desc()
+    desc.ndim = 2
+    for k, (nb, (lo, hi)) in enumerate(zip(bins, ranges)):
+        desc.axis[k], desc.bins[k], desc.lo[k], desc.hi[k] = k, nb, lo, hi
+    weighted = all(B.intensity is not None for B in Bs)
+    shift = 0
+    if weighted:
+        wmax = max((float(torch.amax(torch.abs(B.intensity))) if B.intensity.numel() else 0.0) for B in Bs)
+        if not math.isfinite(wmax):
+            raise ValueError("the rays' intensities must be finite to be binned")
+        shift = shift_for(sum(B.n_slots for B in Bs), wmax)
+    out = None
+    for B in Bs:
+        counts, wsums, totals, _ = B.backend.histogram(desc, B.view(), B.intensity if weighted else None, B.n_slots,
+                                                       out=out, shift=shift)
+        out = (counts, wsums, totals)
+    return Histogram(counts.cpu().numpy().reshape(bins), None if wsums is None else wsums.cpu().numpy().reshape(bins),
+                     totals.cpu().numpy(), [np.linspace(lo, hi, nb + 1) for nb, (lo, hi) in zip(bins, ranges)], shift)
+
+
 def footprint(oe, RayList, Bins=100, Range=None):
     """OpticalChain.get_Footprint: the hit points on optical element `oe` in its support frame, fwd (P - position)
     (MirrorProjection's coordinates), binned over +-_CircumRect()/2 by default."""

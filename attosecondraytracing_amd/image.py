@@ -116,6 +116,7 @@ def focal_image(det, RayList, RaysPerSource=None, Groups=None, Size=None, Pixels
     fd, x, y, shifts, wavelength, ref, _ = focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
     if groups == 0:                 # no slot: one empty group for the device
         seg = torch.zeros(2, dtype=torch.int64, device=B.alive.device)
-    intensity = B.backend.focal_image(fd, seg, max(groups, 1), B.view(), B.intensity, B.n_slots)
+    view, _keep = B.phase_path_view(wavelength)          # (behind a grating: path + wavelength * grooves)
+    intensity = B.backend.focal_image(fd, seg, max(groups, 1), view, B.intensity, B.n_slots)
     power, ideal = group_sums(B, seg)
     return FocalImage(intensity, x, y, shifts, wavelength, ref, groups, power, ideal)

@@ -228,7 +228,7 @@ def wavefronts(requests):
         host = iter(torch.stack([torch.as_tensor(s)[:2] for s in dev]).cpu().numpy() if dev else ())
         for it, s in pending:
             st = s if isinstance(s, np.ndarray) else next(host)
-            it[2]["ref_path"] = float(st[1] / st[0]) if st[0] > 0 else 0.0
+            it[2]["ref_path"] = (float(st[1] / st[0]) + it[0].phase_ref_offset(it[2]["wavelength"])) if st[0] > 0 else 0.0
     groups = {}
     for pos, it in enumerate(items):
         groups.setdefault(id(it[0].backend), []).append(pos)
@@ -251,7 +251,7 @@ def _job(item):
     be, n = B.backend, B.n_slots
     j = _abi.ArtWavefrontJob()
     j.det = det._desc()
-    j.b = B.view()
+    j.b, j._keep = B.phase_path_view(p["wavelength"])       # (behind a grating: path + wavelength * grooves)
     j.w = None if B.intensity is None else B.intensity.data_ptr()
     j.n = n
     j.ref[:] = [p["centre"][0], p["centre"][1], p["shift"]]

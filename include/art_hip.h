@@ -58,6 +58,7 @@ enum ArtSupportKind {
 /* element flags */
 #define ART_FLAG_PERTURBED_NORMAL 1u /* IgnoreDefects=False: reflect off the defect-perturbed normal (ModuleMirror.py:933-936) */
 #define ART_FLAG_ZERN_RECURRENCE 2u  /* the element's Zernike tables are in the RECURRENCE layout (any order, below)      */
+#define ART_FLAG_GRATING 4u          /* this element is a grating: only art_trace_grating traces it                        */
 
 /* Zernike defect table (ART/ModuleDefects.py:149-174), a DEVICE array of doubles per element.  The polynomials
  * of ART/recursive_zernike_generator.py have integer monomial coefficients; the host expands
@@ -155,6 +156,38 @@ int art_device_count(void);
  * miss get out->alive = 0 and their other outputs are left untouched.                                  */
 int art_trace_element(const ArtElementDesc* e, const ArtBundleView* in, const ArtBundleView* out,
                       int64_t n, void* stream);
+
+/* Diffraction grating ruled on any undeformed mirror (added under ABI 14: ART_FLAG_GRATING, ArtGratingDesc,
+ * art_trace_grating).  The grooves are the intersections of the surface with equally spaced parallel planes: groove
+ * number G(P) = N q0.(P - centre) at the hit point P (optic frame), q0 = (q[0], q[1], 0).  Per ray and wavelength, with
+ * the unit normal n at P, the incident unit direction u and g = m lambda N q0 (lambda in mm, N in lines per mm):
+ *     g_t = g - (g.n) n,  v_t = (u - (u.n) n) + g_t,  s = 1 - |v_t|^2,  v = v_t - sign(u.n) sqrt(s) n
+ * s <= 0: the order is evanescent and the ray is lost.  path += the geometric length of the leg, incidence as for a
+ * mirror, grooves_out[j][r] = grooves_in[r] + m G(P): the phase of a ray in a coherent analysis is
+ * k path + 2 pi grooves (derivation: csrc/art_device.h).  g = 0 (N = 0 or m = 0) is the mirror.
+ * ONE launch, one thread per ray: intersection, support test and normal are formed once, then the thread loops over the
+ * nw wavelengths and stores one diffracted ray per wavelength into outs[j]: the input is read once, not nw times.
+ * Slots dead on input, rays that miss and evanescent orders get alive = 0 in the affected outputs, whose other arrays
+ * (and grooves_out) are left untouched there.  outs[j] may alias `in` only when nw == 1.
+ * wavelengths_host / outs_host: HOST copies of the DEVICE arrays g->wavelengths / g->outs, read for validation only.
+ * Limits: e valid by art_trace_element's rules, without defects, not a mask; | |q|^2 - 1 | <= 1e-12; N finite, >= 0;
+ * 1 <= nw <= ART_GRATING_MAX_WAVELENGTHS; every wavelength finite and > 0; views complete when n > 0:
+ * ART_ERR_BAD_ARG otherwise; 0 <= n <= 2^28 (ART_ERR_UNSUPPORTED beyond); nothing is launched on failure.
+ * art_trace_element, art_trace_chain(_readout), art_scene_pack and art_trace_guides return ART_ERR_UNSUPPORTED for an
+ * element with ART_FLAG_GRATING set.                                                                                  */
+#define ART_GRATING_MAX_WAVELENGTHS 1024
+typedef struct ArtGratingDesc {
+  double q[2];                  /* q0: unit vector in the optic's xy plane, the direction of dispersion   */
+  double lines_per_mm;          /* N >= 0, finite                                                         */
+  int32_t order;                /* m                                                                      */
+  int32_t nw;                   /* 1 .. ART_GRATING_MAX_WAVELENGTHS                                       */
+  const double* wavelengths;    /* DEVICE, nw doubles (mm)                                                */
+  const ArtBundleView* outs;    /* DEVICE, nw views: the diffracted bundle per wavelength                 */
+  double* grooves_in;           /* DEVICE, n doubles, or NULL (= 0): the groove count each ray arrives with */
+  double* grooves_out;          /* DEVICE, [nw][n] doubles, or NULL                                       */
+} ArtGratingDesc;
+int art_trace_grating(const ArtElementDesc* e, const ArtGratingDesc* g, const double* wavelengths_host,
+                      const ArtBundleView* outs_host, const ArtBundleView* in, int64_t n, void* stream);
 
 /* Whole chain in ONE launch: the ray stays in registers from element to element.  outs[k] receives the
  * bundle after element k for every k with outs[k].alive != NULL (pass zeroed views to skip history);

@@ -1,0 +1,285 @@
+"""CPU: diffraction gratings -- the oracle against the long-double truth, the header's per-ray function (compiled with
+g++) against the truth, the host shell (Grating, RayBundle.grooves, refusals), the ABI mirror, and the device code's
+resource usage (no scratch memory)."""
+import ctypes as C
+import os
+import pickle
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import grating_common as gc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SCENES = gc.scenes()
+
+
+# ------------------------------------------------------------------------------------------ oracle, truth, header
+@pytest.mark.parametrize("name", sorted(SCENES))
+def test_fp64_oracle_agrees_with_long_double_truth(name):
+    assert gc.HAVE_LD, "numpy.longdouble has no extended precision on this platform"
+    oe, (P, V, path, alive), wl = SCENES[name]
+    E = gc.element_spec(oe)
+    ref = gc.diffract(E, P, V, path, alive, wl, T=gc.LD)
+    res = gc.diffract(E, P, V, path, alive, wl, T=np.float64)
+    clear = np.abs(np.asarray(ref["s"], dtype=float)) > 1e-9            # (the evanescent scene has none closer, see below)
+    assert (res["alive"] == ref["alive"])[clear].all()
+    assert ref["hit"].sum() > 0
+    gc.assert_parity(res, ref, ref["alive"] & res["alive"], name)
+
+
+def test_evanescent_scene_straddles_the_cut_off_with_a_margin():
+    oe, (P, V, path, alive), wl = SCENES["evanescent"]
+    ref = gc.diffract(gc.element_spec(oe), P, V, path, alive, wl, T=gc.LD)
+    s = np.asarray(ref["s"], dtype=float)[ref["hit"]]
+    assert (np.abs(s) >= 1e-9).all() and (s > 0).any() and (s < 0).any()
+
+
+HARNESS = r'''
+#include <cstdio>
+#include <vector>
+#include "art_device.h"
+// in: 36 doubles (kind, support kind, fwd[9], pos[3], centre[3], sp[6], mp[4], qx, qy, N, m, wavelength, n, 3 unused), then
+// n rows of 9 doubles (point, vector, path, alive, grooves).  out: n rows of 10 (ray[8], grooves, alive).
+int main(int argc, char** argv) {
+  FILE* f = fopen(argv[1], "rb");
+  double h[36];
+  if (!f || fread(h, 8, 36, f) != 36) return 2;
+  ArtElementDesc e = {};
+  e.kind = (int)h[0]; e.support_kind = (int)h[1];
+  for (int i = 0; i < 9; ++i) e.fwd[i] = h[2 + i];
+  for (int i = 0; i < 3; ++i) { e.pos[i] = h[11 + i]; e.centre[i] = h[14 + i]; }
+  for (int i = 0; i < 6; ++i) e.sp[i] = h[17 + i];
+  for (int i = 0; i < 4; ++i) e.mp[i] = h[23 + i];
+  art::prepare_element(e);
+  const long n = (long)h[32];
+  std::vector<double> in(9 * n), out(10 * n);
+  if (fread(in.data(), 8, 9 * n, f) != (size_t)(9 * n)) return 3;
+  for (long i = 0; i < n; ++i) {
+    const double* r = &in[9 * i];
+    art::Ray ray = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], 0.0};
+    double g = r[8];
+    const bool ok = r[7] != 0.0 && art::grating_ray(e, h[27], h[28], h[29], (int)h[30], h[31], ray, g);
+    const double o[10] = {ray.ox, ray.oy, ray.oz, ray.dx, ray.dy, ray.dz, ray.path, ray.inc, g, ok ? 1.0 : 0.0};
+    for (int k = 0; k < 10; ++k) out[10 * i + k] = o[k];
+  }
+  FILE* w = fopen(argv[2], "wb");
+  fwrite(out.data(), 8, 10 * n, w);
+  fclose(w);
+  return 0;
+}
+'''
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    td = tmp_path_factory.mktemp("grating_harness")
+    src, exe = td / "h.cpp", td / "h"
+    src.write_text(HARNESS)
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-DART_HOST_TWIN", "-ffp-contract=off",
+                           "-I", os.path.join(ROOT, "attosecondraytracing_amd", "csrc"), "-o", str(exe), str(src)])
+    return td, str(exe)
+
+
+@pytest.mark.parametrize("name", sorted(SCENES))
+def test_header_function_agrees_with_long_double_truth(harness, name):
+    td, exe = harness
+    oe, (P, V, path, alive), wl = SCENES[name]
+    E = gc.element_spec(oe)
+    n = len(P)
+    sp = list(E["support"][1:]) + [0.0] * 6
+    head = ([{"plane": 0, "sphere": 1, "torus": 3}[E["kind"]], 0 if E["support"][0] == "round" else 2] + list(E["fwd"].reshape(9))
+            + list(E["pos"]) + list(E["centre"]) + sp[:6] + (E["mp"] + [0.0] * 4)[:4]
+            + [E["q"][0], E["q"][1], E["N"], E["m"], wl, n, 0, 0, 0])
+    g_in = np.linspace(-3.0, 3.0, n)
+    rows = np.column_stack([P, V, path, alive.astype(float), g_in])
+    fin, fout = str(td / (name + ".in")), str(td / (name + ".out"))
+    with open(fin, "wb") as f:
+        f.write(np.asarray(head, dtype=np.float64).tobytes())
+        f.write(np.ascontiguousarray(rows, dtype=np.float64).tobytes())
+    subprocess.check_call([exe, fin, fout])
+    out = np.fromfile(fout, dtype=np.float64).reshape(n, 10)
+    ref = gc.diffract(E, P, V, path, alive, wl, grooves=g_in, T=gc.LD)
+    clear = np.abs(np.asarray(ref["s"], dtype=float)) > 1e-9
+    got_alive = out[:, 9] != 0
+    assert (got_alive == ref["alive"])[clear].all()
+    res = {"point": out[:, 0:3], "vector": out[:, 3:6], "path": out[:, 6], "inc": out[:, 7], "grooves": out[:, 8]}
+    gc.assert_parity(res, ref, ref["alive"] & got_alive, name)
+    lost = ~got_alive                                   # a lost ray keeps its state and its groove count
+    assert (out[lost, 0:3] == P[lost]).all() and (out[lost, 8] == g_in[lost]).all()
+
+
+# ------------------------------------------------------------------------------------------------------- host shell
+def _mirrors():
+    import ART.ModuleMirror as mm
+    import ART.ModuleSupport as ms
+    S = ms.SupportRound(10.0)
+    return mm, ms, [mm.MirrorPlane(S), mm.MirrorSpherical(100.0, S), mm.MirrorSpherical(-100.0, S),
+                    mm.MirrorParabolic(50.0, 30.0, S), mm.MirrorToroidal(300.0, 20.0, S),
+                    mm.MirrorEllipsoidal(S, SemiMajorAxis=200.0, SemiMinorAxis=100.0, OffAxisAngle=30.0),
+                    mm.MirrorCylindrical(100.0, S)]
+
+
+def test_grating_wraps_every_mirror_and_delegates():
+    mm, ms, mirrors = _mirrors()
+    for M in mirrors:
+        G = mm.Grating(M, 1200.0, Order=-1, GrooveAngle=90.0)
+        assert "Mirror" in G.type and G.type == M.type
+        assert G.support is M.support and G._abi_kind == M._abi_kind
+        assert np.array_equal(G.get_centre(), M.get_centre())
+        assert list(G._abi_params()) == list(M._abi_params())
+        assert G._groove_vector() == (0.0, 1.0)
+        assert len(G.get_grid3D(200)) == len(M.get_grid3D(200))
+        assert hash(G) != hash(mm.Grating(M, 1200.0, Order=1, GrooveAngle=90.0))
+    q = mm.Grating(mirrors[0], 100.0, GrooveAngle=30.0)._groove_vector()
+    assert abs(q[0] ** 2 + q[1] ** 2 - 1) < 1e-15 and abs(q[1] - 0.5) < 1e-15
+
+
+def test_grating_validation_and_refused_substrates():
+    mm, ms, mirrors = _mirrors()
+    import ART.ModuleMask as mk
+    import ART.ModuleDefects as md
+    with pytest.raises(ValueError):
+        mm.Grating(mk.Mask(ms.SupportRound(5.0)), 1200.0)
+    D = mm.DeformedMirror(mirrors[0], [md.Zernike(mirrors[0].support, {(2, 0): 1e-5})])
+    with pytest.raises(ValueError):
+        mm.Grating(D, 1200.0)
+    for bad in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError):
+            mm.Grating(mirrors[0], bad)
+    with pytest.raises(ValueError):
+        mm.Grating(mirrors[0], 1200.0, Order=0.5)
+    with pytest.raises(ValueError):
+        mm.Grating(mirrors[0], 1200.0, GrooveAngle=float("nan"))
+
+
+def test_descriptor_carries_the_grating_flag():
+    from attosecondraytracing_amd import ModuleProcessing as mp, _abi
+    oe = gc.place(gc.plane_grating(1200.0, -1, 0.0), 500.0, 80.0)
+    d, _ = mp._build_descriptor(oe, True, None)
+    assert d.flags & _abi.ART_FLAG_GRATING and d.grating is oe.type
+    bare = gc.place(oe.type.Mirror, 500.0, 80.0)
+    d0, _ = mp._build_descriptor(bare, True, None)
+    assert not d0.flags & _abi.ART_FLAG_GRATING
+    assert bytes(d)[16:] == bytes(d0)[16:]             # everything but the flags word is the substrate's
+
+
+def _host_bundle(n=10, grooves=True):
+    import torch
+    from attosecondraytracing_amd.bundle import RayBundle
+    b = RayBundle.__new__(RayBundle)
+    RayBundle.__init__(b, torch.arange(8 * n, dtype=torch.float64).reshape(8, n).clone(), torch.ones(n, dtype=torch.uint8),
+                       wavelength=30e-6, backend=object(), grooves=torch.arange(n, dtype=torch.float64) * 0.25 if grooves else None)
+    return b
+
+
+def test_bundle_grooves_survive_slicing_pickling_and_copies():
+    import torch
+    b = _host_bundle()
+    s = b.slots(2, 7)
+    assert torch.equal(s.grooves, b.grooves[2:7])
+    r = pickle.loads(pickle.dumps(b))
+    assert torch.equal(r.grooves, b.grooves) and r.wavelength == b.wavelength
+    assert b.alias().grooves is b.grooves
+    plain = _host_bundle(grooves=False)
+    assert plain.grooves is None and plain.slots(0, 4).grooves is None
+    assert pickle.loads(pickle.dumps(plain)).grooves is None
+    assert plain.phase_ref_offset() == 0.0
+    assert abs(b.phase_ref_offset() - 30e-6 * float(b.grooves.mean())) < 1e-18
+
+
+def test_pulse_analyses_refuse_bundles_behind_a_grating():
+    import ART.ModuleDetector as mdet
+    import ART.ModuleOpticalChain as moc
+    b = _host_bundle()
+    det = mdet.Detector(np.zeros(3))
+    with pytest.raises(NotImplementedError, match="get_SpectralRays"):
+        det.get_FocalPulse(b, 5.0)
+    oe = gc.place(gc.plane_grating(1200.0, -1, 0.0), 500.0, 80.0)
+    chain = moc.OpticalChain.__new__(moc.OpticalChain)
+    chain._optical_elements = [oe, oe]
+    with pytest.raises(NotImplementedError, match="get_SpectralRays"):
+        chain.get_FocalPulse(None, det, 5.0, np.array([0, 1, 0]))
+    with pytest.raises(NotImplementedError, match="get_SpectralRays"):
+        chain.get_VectorFocalField(None, det, np.array([0, 1, 0]))
+    with pytest.raises(NotImplementedError, match="more than one grating"):
+        chain.get_SpectralRays([30e-6])
+    chain._optical_elements = [gc.place(oe.type.Mirror, 500.0, 80.0)]
+    with pytest.raises(ValueError):
+        chain.get_SpectralRays([30e-6])
+
+
+def test_tracing_a_grating_needs_a_wavelength():
+    from attosecondraytracing_amd import ModuleProcessing as mp, _abi
+    d = _abi.ArtElementDesc()
+    d.flags = _abi.ART_FLAG_GRATING
+    with pytest.raises(ValueError, match="wavelength"):
+        mp._trace_one(None, d, None, None, 0, None, None)
+
+
+# -------------------------------------------------------------------------------------------------------------- ABI
+def test_grating_desc_matches_the_header_and_the_library_exports_the_entry(tmp_path):
+    from attosecondraytracing_amd import _abi
+    import torch  # noqa: F401  (before the library: one HIP runtime per process)
+    import __graft_entry__ as g
+    src = r'''
+#include <stdio.h>
+#include <stddef.h>
+#include "art_hip.h"
+int main(void) {
+  printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %u %d\n", sizeof(ArtGratingDesc), offsetof(ArtGratingDesc, q),
+         offsetof(ArtGratingDesc, lines_per_mm), offsetof(ArtGratingDesc, order), offsetof(ArtGratingDesc, nw),
+         offsetof(ArtGratingDesc, wavelengths), offsetof(ArtGratingDesc, outs), offsetof(ArtGratingDesc, grooves_in),
+         offsetof(ArtGratingDesc, grooves_out), ART_FLAG_GRATING, ART_GRATING_MAX_WAVELENGTHS);
+  return 0;
+}'''
+    c, exe = tmp_path / "t.c", tmp_path / "t"
+    c.write_text(src)
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(c)])
+    vals = [int(v) for v in subprocess.check_output([str(exe)]).split()]
+    D = _abi.ArtGratingDesc
+    assert vals == [C.sizeof(D), D.q.offset, D.lines_per_mm.offset, D.order.offset, D.nw.offset, D.wavelengths.offset,
+                    D.outs.offset, D.grooves_in.offset, D.grooves_out.offset, _abi.ART_FLAG_GRATING,
+                    _abi.ART_GRATING_MAX_WAVELENGTHS]
+    if g._stale(g.HIP_LIB, g.HIP_DEPS):
+        g.build()
+    lib = C.CDLL(g.HIP_LIB)
+    assert hasattr(lib, "art_trace_grating") and "art_trace_grating" in _abi.PROTOTYPES
+
+
+def test_scene_pack_refuses_a_grating_on_the_host():
+    """art_scene_pack is pure host code: the refusal can be checked without a device."""
+    from attosecondraytracing_amd import _abi
+    import torch  # noqa: F401
+    import __graft_entry__ as g
+    if g._stale(g.HIP_LIB, g.HIP_DEPS):
+        g.build()
+    fn = _abi.bind(C.CDLL(g.HIP_LIB))
+    e = (_abi.ArtElementDesc * 1)()
+    e[0].kind, e[0].flags = _abi.ART_PLANE, _abi.ART_FLAG_GRATING
+    v = _abi.ArtBundleView(*([8] * 9))
+    ins, outs = (_abi.ArtBundleView * 1)(v), (_abi.ArtBundleView * 1)(v)
+    image = C.create_string_buffer(int(fn["art_scene_bytes"](1, 1)))
+    assert fn["art_scene_pack"](e, 1, 1, ins, outs, None, C.cast(image, C.c_void_p)) == _abi.ART_ERR_UNSUPPORTED
+    e[0].flags = 0
+    assert fn["art_scene_pack"](e, 1, 1, ins, outs, None, C.cast(image, C.c_void_p)) >= 0
+
+
+# ---------------------------------------------------------------------------------------------------- device code
+def test_grating_kernel_compiles_for_gfx950_without_scratch(tmp_path):
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc not available")
+    src = os.path.join(ROOT, "attosecondraytracing_amd", "csrc", "art_kernels.hip")
+    p = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-c",
+                        "-Rpass-analysis=kernel-resource-usage", "-o", str(tmp_path / "dev.o"), src],
+                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert p.returncode == 0, p.stdout[-4000:]
+    blocks = re.split(r"remark: Function Name: ", p.stdout)
+    mine = [b for b in blocks if "k_trace_grating" in b.split("[", 1)[0]]
+    assert len(mine) == 1, "the kernel's resource remarks were not found"
+    m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", mine[0])
+    assert m and int(m.group(1)) == 0, mine[0]
+    assert re.search(r"VGPRs Spill: 0", mine[0]) and re.search(r"SGPRs Spill: 0", mine[0])
