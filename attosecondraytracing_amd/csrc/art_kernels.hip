@@ -1597,10 +1597,11 @@ struct FocalArg {
 };
 
 inline int64_t focal_stride(int64_t n) { return (n + 63) / 64 * 64; }
+inline int focal_tiles(int nx, int ny) { return ((nx + kFocalTile - 1) / kFocalTile) * ((ny + kFocalTile - 1) / kFocalTile); }
 
 // slices of the rays: enough workgroups to fill the machine, at least 4 chunks of rays per slice
 inline int focal_slices(int nx, int ny, int planes, int64_t n) {
-  const int64_t wgs = (int64_t)((nx + kFocalTile - 1) / kFocalTile) * ((ny + kFocalTile - 1) / kFocalTile) * planes;
+  const int64_t wgs = (int64_t)focal_tiles(nx, ny) * planes;
   int64_t s = (kFocalWantBlocks + wgs - 1) / wgs;
   const int64_t by_rays = (n + 4 * kFocalChunk - 1) / (4 * kFocalChunk);
   if (s > by_rays) s = by_rays;
@@ -1630,83 +1631,150 @@ __global__ __launch_bounds__(kBlock) void k_focal_prep(const FocalArg a, const A
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_focal_field(const FocalArg a, const double* __restrict__ rows,
-                                                        double* __restrict__ out) {
-  __shared__ double2 sU[kFocalChunk][kFocalTile];     // exp(i X_j k d.e1)
-  __shared__ double2 sW[kFocalChunk][kFocalTile];     // amp exp(i (base + s_q k d.n + Y_l k d.e2))
-  const int q = blockIdx.y, slice = blockIdx.z;
-  const int tx0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * kFocalTile, ty0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * kFocalTile;
-  const int t = threadIdx.x, lx = t % kFocalLanes, ly = t / kFocalLanes;
-  const int64_t st = a.stride, r0 = (int64_t)slice * a.per_slice;
-  const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
-  const double sh = a.shift[q];
-  // staging role of this lane: rows (W) or columns (U), ray sr of the chunk, segment sg of the tile
-  const bool colw = t < kBlock / 2;
-  const int sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg), sg = t % (kFocalTile / kFocalSeg);
-  double acc_re[kFocalMicro][kFocalMicro], acc_im[kFocalMicro][kFocalMicro];
-#pragma unroll
-  for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-    for (int u = 0; u < kFocalMicro; ++u) acc_re[v][u] = acc_im[v][u] = 0.0;
+// ---- the pieces that k_focal_field, k_focal_image, k_focal_spectrum_field and k_vecspec_field are made of.  The
+// rotation and the sums are explicit FMAs, so the four kernels round alike: from the same phase terms, the same bytes.
 
-  for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
-    const int64_t r = c0 + sr;
-    const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
-    double ph, amp, s_re, s_im;
-    int p0;
-    if (colw) {
-      p0 = tx0 + sg * kFocalSeg;
-      const double ka = in ? rows[2 * st + r] : 0.0;
-      ph = ka * (a.x0 + (double)p0 * a.dx);
-      amp = 1.0;
-      s_re = in ? rows[5 * st + r] : 1.0; s_im = in ? rows[6 * st + r] : 0.0;
-    } else {
-      p0 = ty0 + sg * kFocalSeg;
-      const double base = in ? rows[st + r] : 0.0, kb = in ? rows[3 * st + r] : 0.0, kc = in ? rows[4 * st + r] : 0.0;
-      ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
-      amp = in ? rows[r] : 0.0;
-      s_re = in ? rows[7 * st + r] : 1.0; s_im = in ? rows[8 * st + r] : 0.0;
-    }
-    double sn, cs;
-    sincos(ph, &sn, &cs);
-    double z_re = amp * cs, z_im = amp * sn;
-    double2* dst = colw ? &sU[sr][sg * kFocalSeg] : &sW[sr][sg * kFocalSeg];
-#pragma unroll
-    for (int m = 0; m < kFocalSeg; ++m) {
-      dst[m] = make_double2(z_re, z_im);
-      const double n_re = z_re * s_re - z_im * s_im;
-      z_im = z_re * s_im + z_im * s_re;
-      z_re = n_re;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int rr = 0; rr < kFocalChunk; ++rr) {
-      double2 uu[kFocalMicro], vv[kFocalMicro];
-#pragma unroll
-      for (int i = 0; i < kFocalMicro; ++i) {
-        uu[i] = sU[rr][lx + kFocalLanes * i];
-        vv[i] = sW[rr][ly + kFocalLanes * i];
-      }
-#pragma unroll
-      for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-        for (int u = 0; u < kFocalMicro; ++u) {
-          acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
-          acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
-          acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
-          acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
-        }
-    }
-    __syncthreads();
+using FocalStage = double2[kFocalChunk][kFocalTile];      // one chunk's phasors in LDS
+using FocalAcc = double[kFocalMicro][kFocalMicro];        // a lane's 4 x 4 block of sums
+
+// a lane's two roles in its workgroup (blockIdx.x is the tile)
+struct FocalLane {
+  int tx0, ty0;      // first pixel of the tile
+  int lx, ly;        // accumulating: columns tx0 + lx + 16 u and rows ty0 + ly + 16 v
+  bool colw;         // staging: columns (U) or rows (W),
+  int sr, sg;        //          ray sr of the chunk, segment sg of the tile
+};
+
+__device__ __forceinline__ FocalLane focal_lane(const int tiles_x) {
+  const int t = threadIdx.x;
+  FocalLane L;
+  L.tx0 = (int)(blockIdx.x % (unsigned)tiles_x) * kFocalTile;
+  L.ty0 = (int)(blockIdx.x / (unsigned)tiles_x) * kFocalTile;
+  L.lx = t % kFocalLanes;
+  L.ly = t / kFocalLanes;
+  L.colw = t < kBlock / 2;
+  L.sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg);
+  L.sg = t % (kFocalTile / kFocalSeg);
+  return L;
+}
+
+// a product that is never contracted into an FMA: k_j * row rounds as k * (...) does in k_focal_prep
+__device__ __forceinline__ double focal_mul(const double a, const double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// For slot r of the rows (in: it belongs to the workgroup's rays; else neutral values), the staging lane's phase at the
+// first pixel of its segment (plane shift sh) and its one-pixel step phasor, read from k_focal_prep's rows ...
+__device__ __forceinline__ void focal_phase_terms(const FocalArg& a, const double* __restrict__ rows, const FocalLane& L,
+                                                  const int64_t r, const bool in, const double sh, double& ph,
+                                                  double& s_re, double& s_im) {
+  const int64_t st = a.stride;
+  if (L.colw) {
+    const int p0 = L.tx0 + L.sg * kFocalSeg;
+    const double ka = in ? rows[2 * st + r] : 0.0;
+    ph = ka * (a.x0 + (double)p0 * a.dx);
+    s_re = in ? rows[5 * st + r] : 1.0; s_im = in ? rows[6 * st + r] : 0.0;
+  } else {
+    const int p0 = L.ty0 + L.sg * kFocalSeg;
+    const double base = in ? rows[st + r] : 0.0, kb = in ? rows[3 * st + r] : 0.0, kc = in ? rows[4 * st + r] : 0.0;
+    ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
+    s_re = in ? rows[7 * st + r] : 1.0; s_im = in ? rows[8 * st + r] : 0.0;
   }
-  double2* o = reinterpret_cast<double2*>(out) + ((int64_t)slice * a.planes + q) * a.ny * a.nx;
+}
+
+// ... or formed at the wavenumber kj from k_focal_spectrum_prep's rows, with the operations and their order of
+// k_focal_prep (one more sincos per lane and chunk): the same values as the rows of k_focal_prep at k = kj
+__device__ __forceinline__ void focal_phase_terms_at(const double kj, const FocalArg& a, const double* __restrict__ rows,
+                                                     const FocalLane& L, const int64_t r, const bool in, const double sh,
+                                                     double& ph, double& s_re, double& s_im) {
+  const int64_t st = a.stride;
+  if (L.colw) {
+    const int p0 = L.tx0 + L.sg * kFocalSeg;
+    const double ka = focal_mul(kj, in ? rows[2 * st + r] : 0.0);
+    ph = ka * (a.x0 + (double)p0 * a.dx);
+    sincos(focal_mul(ka, a.dx), &s_im, &s_re);
+  } else {
+    const int p0 = L.ty0 + L.sg * kFocalSeg;
+    const double base = focal_mul(kj, in ? rows[st + r] : 0.0), kb = focal_mul(kj, in ? rows[3 * st + r] : 0.0),
+                 kc = focal_mul(kj, in ? rows[4 * st + r] : 0.0);
+    ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
+    sincos(focal_mul(kb, a.dy), &s_im, &s_re);
+  }
+}
+
+// the staging lane's kFocalSeg phasors of its ray: z at the segment's first pixel, then rotated by s pixel by pixel
+__device__ __forceinline__ void focal_rotate_store(FocalStage& sU, FocalStage& sW, const FocalLane& L, double z_re,
+                                                   double z_im, const double s_re, const double s_im) {
+  double2* dst = L.colw ? &sU[L.sr][L.sg * kFocalSeg] : &sW[L.sr][L.sg * kFocalSeg];
+#pragma unroll
+  for (int m = 0; m < kFocalSeg; ++m) {
+    dst[m] = make_double2(z_re, z_im);
+    const double n_re = fma(z_re, s_re, -(z_im * s_im));
+    z_im = fma(z_re, s_im, z_im * s_re);
+    z_re = n_re;
+  }
+}
+
+// acc += W U^T over the chunk's rays, for the lane's 4 x 4 pixels (between the kernel's two barriers)
+__device__ __forceinline__ void focal_accumulate(const FocalStage& sU, const FocalStage& sW, const FocalLane& L,
+                                                 FocalAcc& acc_re, FocalAcc& acc_im) {
+#pragma unroll 2
+  for (int rr = 0; rr < kFocalChunk; ++rr) {
+    double2 uu[kFocalMicro], vv[kFocalMicro];
+#pragma unroll
+    for (int i = 0; i < kFocalMicro; ++i) {
+      uu[i] = sU[rr][L.lx + kFocalLanes * i];
+      vv[i] = sW[rr][L.ly + kFocalLanes * i];
+    }
+#pragma unroll
+    for (int v = 0; v < kFocalMicro; ++v)
+#pragma unroll
+      for (int u = 0; u < kFocalMicro; ++u) {
+        acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
+        acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
+        acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
+        acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
+      }
+  }
+}
+
+// the lane's 4 x 4 complex sums into the [ny][nx] plane at o, pixels beyond the grid left out
+__device__ __forceinline__ void focal_store(double2* __restrict__ o, const FocalArg& a, const FocalLane& L,
+                                            const FocalAcc& acc_re, const FocalAcc& acc_im) {
 #pragma unroll
   for (int v = 0; v < kFocalMicro; ++v)
 #pragma unroll
     for (int u = 0; u < kFocalMicro; ++u) {
-      const int l = ty0 + ly + kFocalLanes * v, j = tx0 + lx + kFocalLanes * u;
+      const int l = L.ty0 + L.ly + kFocalLanes * v, j = L.tx0 + L.lx + kFocalLanes * u;
       if (l < a.ny && j < a.nx) o[(int64_t)l * a.nx + j] = make_double2(acc_re[v][u], acc_im[v][u]);
     }
+}
+
+__global__ __launch_bounds__(kBlock) void k_focal_field(const FocalArg a, const double* __restrict__ rows,
+                                                        double* __restrict__ out) {
+  __shared__ FocalStage sU;                           // exp(i X_j k d.e1)
+  __shared__ FocalStage sW;                           // amp exp(i (base + s_q k d.n + Y_l k d.e2))
+  const int q = blockIdx.y, slice = blockIdx.z;
+  const FocalLane L = focal_lane(a.tiles_x);
+  const int64_t r0 = (int64_t)slice * a.per_slice;
+  const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
+  const double sh = a.shift[q];
+  FocalAcc acc_re = {}, acc_im = {};
+
+  for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
+    const int64_t r = c0 + L.sr;
+    const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
+    double ph, s_re, s_im, sn, cs;
+    focal_phase_terms(a, rows, L, r, in, sh, ph, s_re, s_im);
+    const double amp = L.colw ? 1.0 : (in ? rows[r] : 0.0);
+    sincos(ph, &sn, &cs);
+    focal_rotate_store(sU, sW, L, amp * cs, amp * sn, s_re, s_im);
+    __syncthreads();
+    focal_accumulate(sU, sW, L, acc_re, acc_im);
+    __syncthreads();
+  }
+  focal_store(reinterpret_cast<double2*>(out) + ((int64_t)slice * a.planes + q) * a.ny * a.nx, a, L, acc_re, acc_im);
 }
 
 // field[p] = sum over the slices in slice order of partial[slice][p]
@@ -1726,7 +1794,7 @@ __global__ __launch_bounds__(kBlock) void k_focal_fold(const double2* __restrict
 // ------------------------------------------------------------------------------------------- focal image
 // art_focal_image: the partially coherent image of an extended source, I_q = sum_g |sum_{r in g} ...|^2 over groups g
 // of slots [seg[g], seg[g+1]) (seg on the device, never read by the host).  k_focal_prep's rows, then k_focal_image:
-// k_focal_field's loop (a copy: shared helpers change k_focal_field's registers) run group by group -- a chunk never
+// k_focal_field's loop run group by group -- a chunk never
 // straddles two groups, the tail of a group's last chunk has amplitude 0 -- and at the end of a group every lane adds
 // re^2 + im^2 of its 16 complex sums to 16 real ones and clears the complex ones.  Grid: (tile, plane x slice), a slice
 // a contiguous range of `per` groups; partials [plane][slice][ny][nx] go through k_focal_image_fold in slice order.
@@ -1737,25 +1805,16 @@ __global__ __launch_bounds__(kBlock) void k_focal_fold(const double2* __restrict
 __global__ __launch_bounds__(kBlock) void k_focal_image(const FocalArg a, const double* __restrict__ rows,
                                                         const int64_t* __restrict__ seg, const int groups, const int per,
                                                         const int slices, const int split, double* __restrict__ out) {
-  __shared__ double2 sU[kFocalChunk][kFocalTile];     // exp(i X_j k d.e1)
-  __shared__ double2 sW[kFocalChunk][kFocalTile];     // amp exp(i (base + s_q k d.n + Y_l k d.e2))
+  __shared__ FocalStage sU;                           // exp(i X_j k d.e1)
+  __shared__ FocalStage sW;                           // amp exp(i (base + s_q k d.n + Y_l k d.e2))
   const int job = blockIdx.y;                         // split == 1: (plane, slice); else (plane, group, piece)
   const int q = split > 1 ? job / (groups * split) : job / slices;
   const int g0 = split > 1 ? (job / split) % groups : (job % slices) * per;
   const int g1 = split > 1 ? g0 + 1 : (g0 + per < groups ? g0 + per : groups);
   const int piece = job % split;
-  const int tx0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * kFocalTile, ty0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * kFocalTile;
-  const int t = threadIdx.x, lx = t % kFocalLanes, ly = t / kFocalLanes;
-  const int64_t st = a.stride;
+  const FocalLane L = focal_lane(a.tiles_x);
   const double sh = a.shift[q];
-  // staging role of this lane: rows (W) or columns (U), ray sr of the chunk, segment sg of the tile
-  const bool colw = t < kBlock / 2;
-  const int sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg), sg = t % (kFocalTile / kFocalSeg);
-  double acc_re[kFocalMicro][kFocalMicro], acc_im[kFocalMicro][kFocalMicro], acc_in[kFocalMicro][kFocalMicro];
-#pragma unroll
-  for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-    for (int u = 0; u < kFocalMicro; ++u) acc_re[v][u] = acc_im[v][u] = acc_in[v][u] = 0.0;
+  FocalAcc acc_re = {}, acc_im = {}, acc_in = {};
 
   for (int g = g0; g < g1; ++g) {
     int64_t r0 = seg[g], r1 = seg[g + 1];
@@ -1768,53 +1827,15 @@ __global__ __launch_bounds__(kBlock) void k_focal_image(const FocalArg a, const 
       if (r0 + len < r1) r1 = r0 + len;
     }
     for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
-      const int64_t r = c0 + sr;
+      const int64_t r = c0 + L.sr;
       const bool in = r < r1;                     // beyond the group: a zero row phasor, nothing is added
-      double ph, amp, s_re, s_im;
-      int p0;
-      if (colw) {
-        p0 = tx0 + sg * kFocalSeg;
-        const double ka = in ? rows[2 * st + r] : 0.0;
-        ph = ka * (a.x0 + (double)p0 * a.dx);
-        amp = 1.0;
-        s_re = in ? rows[5 * st + r] : 1.0; s_im = in ? rows[6 * st + r] : 0.0;
-      } else {
-        p0 = ty0 + sg * kFocalSeg;
-        const double base = in ? rows[st + r] : 0.0, kb = in ? rows[3 * st + r] : 0.0, kc = in ? rows[4 * st + r] : 0.0;
-        ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
-        amp = in ? rows[r] : 0.0;
-        s_re = in ? rows[7 * st + r] : 1.0; s_im = in ? rows[8 * st + r] : 0.0;
-      }
-      double sn, cs;
+      double ph, s_re, s_im, sn, cs;
+      focal_phase_terms(a, rows, L, r, in, sh, ph, s_re, s_im);
+      const double amp = L.colw ? 1.0 : (in ? rows[r] : 0.0);
       sincos(ph, &sn, &cs);
-      double z_re = amp * cs, z_im = amp * sn;
-      double2* dst = colw ? &sU[sr][sg * kFocalSeg] : &sW[sr][sg * kFocalSeg];
-#pragma unroll
-      for (int m = 0; m < kFocalSeg; ++m) {
-        dst[m] = make_double2(z_re, z_im);
-        const double n_re = z_re * s_re - z_im * s_im;
-        z_im = z_re * s_im + z_im * s_re;
-        z_re = n_re;
-      }
+      focal_rotate_store(sU, sW, L, amp * cs, amp * sn, s_re, s_im);
       __syncthreads();
-#pragma unroll 2
-      for (int rr = 0; rr < kFocalChunk; ++rr) {
-        double2 uu[kFocalMicro], vv[kFocalMicro];
-#pragma unroll
-        for (int i = 0; i < kFocalMicro; ++i) {
-          uu[i] = sU[rr][lx + kFocalLanes * i];
-          vv[i] = sW[rr][ly + kFocalLanes * i];
-        }
-#pragma unroll
-        for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-          for (int u = 0; u < kFocalMicro; ++u) {
-            acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
-            acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
-            acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
-            acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
-          }
-      }
+      focal_accumulate(sU, sW, L, acc_re, acc_im);
       __syncthreads();
     }
     if (split > 1) break;                         // the piece's complex sum is the result
@@ -1827,15 +1848,16 @@ __global__ __launch_bounds__(kBlock) void k_focal_image(const FocalArg a, const 
       }
   }
   const int64_t o = (int64_t)job * a.ny * a.nx;
+  if (split > 1) {
+    focal_store(reinterpret_cast<double2*>(out) + o, a, L, acc_re, acc_im);
+    return;
+  }
 #pragma unroll
   for (int v = 0; v < kFocalMicro; ++v)
 #pragma unroll
     for (int u = 0; u < kFocalMicro; ++u) {
-      const int l = ty0 + ly + kFocalLanes * v, j = tx0 + lx + kFocalLanes * u;
-      if (l < a.ny && j < a.nx) {
-        if (split > 1) reinterpret_cast<double2*>(out)[o + (int64_t)l * a.nx + j] = make_double2(acc_re[v][u], acc_im[v][u]);
-        else out[o + (int64_t)l * a.nx + j] = acc_in[v][u];
-      }
+      const int l = L.ty0 + L.ly + kFocalLanes * v, j = L.tx0 + L.lx + kFocalLanes * u;
+      if (l < a.ny && j < a.nx) out[o + (int64_t)l * a.nx + j] = acc_in[v][u];
     }
 }
 
@@ -1875,17 +1897,10 @@ __global__ __launch_bounds__(kBlock) void k_focal_image_fold_split(const double2
 // art_focal_spectrum: the focal field at nk wavenumbers k_j = k_0 + j dk from one bundle (mirrors are achromatic, so
 // only the phase k (optical path) changes with k).  k_focal_spectrum_prep writes the k-independent rows of each slot
 // (amp, base / k, d.e1, d.e2, d.n; a dead slot gets amplitude 0).  k_focal_spectrum_field is k_focal_field with
-// (plane, wavenumber) on the grid's y dimension: its staging lanes scale the rows by k_j and form the one-pixel step
-// phasor themselves (one more sincos per lane and chunk), with the operations and their order of k_focal_prep /
-// k_focal_field, so that a slice equals art_focal_field's at k = k_j.  The slices' partials go through k_focal_fold.
-// It is a kernel of its own: k_focal_field, refactored into shared inline helpers, compiles to other instructions.
+// (plane, wavenumber) on the grid's y dimension and focal_phase_terms_at in the staging lanes; everything after the
+// phase terms is k_focal_field's code, so a slice equals art_focal_field's at k = k_j.  The slices' partials go
+// through k_focal_fold.
 constexpr int kFocalSpecRows = 5;     // amp, base / k, d.e1, d.e2, d.n
-
-// a product that is never contracted into an FMA: k_j * row rounds as k * (...) does in k_focal_prep
-__device__ __forceinline__ double focal_mul(const double a, const double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
 
 // k_j = k_0 + j * dk, unfused (k_0 exactly at j = 0); the host's validation forms it the same way
 __host__ __device__ inline double focal_kj(const double k0, const int j, const double dk) {
@@ -1915,84 +1930,29 @@ __global__ __launch_bounds__(kBlock) void k_focal_spectrum_prep(const FocalArg a
 __global__ __launch_bounds__(kBlock) void k_focal_spectrum_field(const FocalArg a, const double dk, const int nk,
                                                                  const double* __restrict__ rows,
                                                                  double* __restrict__ out) {
-  __shared__ double2 sU[kFocalChunk][kFocalTile];     // exp(i X_j k d.e1)
-  __shared__ double2 sW[kFocalChunk][kFocalTile];     // amp exp(i (base + s_q k d.n + Y_l k d.e2))
+  __shared__ FocalStage sU;                           // exp(i X_j k d.e1)
+  __shared__ FocalStage sW;                           // amp exp(i (base + s_q k d.n + Y_l k d.e2))
   const int qj = blockIdx.y, q = qj / nk, slice = blockIdx.z;
   const double kj = focal_kj(a.k, qj - q * nk, dk);
-  const int tx0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * kFocalTile, ty0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * kFocalTile;
-  const int t = threadIdx.x, lx = t % kFocalLanes, ly = t / kFocalLanes;
-  const int64_t st = a.stride, r0 = (int64_t)slice * a.per_slice;
+  const FocalLane L = focal_lane(a.tiles_x);
+  const int64_t r0 = (int64_t)slice * a.per_slice;
   const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
   const double sh = a.shift[q];
-  // staging role of this lane: rows (W) or columns (U), ray sr of the chunk, segment sg of the tile
-  const bool colw = t < kBlock / 2;
-  const int sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg), sg = t % (kFocalTile / kFocalSeg);
-  double acc_re[kFocalMicro][kFocalMicro], acc_im[kFocalMicro][kFocalMicro];
-#pragma unroll
-  for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-    for (int u = 0; u < kFocalMicro; ++u) acc_re[v][u] = acc_im[v][u] = 0.0;
+  FocalAcc acc_re = {}, acc_im = {};
 
   for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
-    const int64_t r = c0 + sr;
+    const int64_t r = c0 + L.sr;
     const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
-    double ph, amp, s_re, s_im;
-    int p0;
-    if (colw) {
-      p0 = tx0 + sg * kFocalSeg;
-      const double ka = focal_mul(kj, in ? rows[2 * st + r] : 0.0);
-      ph = ka * (a.x0 + (double)p0 * a.dx);
-      amp = 1.0;
-      sincos(focal_mul(ka, a.dx), &s_im, &s_re);
-    } else {
-      p0 = ty0 + sg * kFocalSeg;
-      const double base = focal_mul(kj, in ? rows[st + r] : 0.0), kb = focal_mul(kj, in ? rows[3 * st + r] : 0.0),
-                   kc = focal_mul(kj, in ? rows[4 * st + r] : 0.0);
-      ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
-      amp = in ? rows[r] : 0.0;
-      sincos(focal_mul(kb, a.dy), &s_im, &s_re);
-    }
-    double sn, cs;
+    double ph, s_re, s_im, sn, cs;
+    focal_phase_terms_at(kj, a, rows, L, r, in, sh, ph, s_re, s_im);
+    const double amp = L.colw ? 1.0 : (in ? rows[r] : 0.0);
     sincos(ph, &sn, &cs);
-    double z_re = amp * cs, z_im = amp * sn;
-    double2* dst = colw ? &sU[sr][sg * kFocalSeg] : &sW[sr][sg * kFocalSeg];
-#pragma unroll
-    for (int m = 0; m < kFocalSeg; ++m) {
-      dst[m] = make_double2(z_re, z_im);
-      // the fused forms the compiler picks for k_focal_field's contracted expressions: the same roundings
-      const double n_re = fma(z_re, s_re, -(z_im * s_im));
-      z_im = fma(z_re, s_im, z_im * s_re);
-      z_re = n_re;
-    }
+    focal_rotate_store(sU, sW, L, amp * cs, amp * sn, s_re, s_im);
     __syncthreads();
-#pragma unroll 2
-    for (int rr = 0; rr < kFocalChunk; ++rr) {
-      double2 uu[kFocalMicro], vv[kFocalMicro];
-#pragma unroll
-      for (int i = 0; i < kFocalMicro; ++i) {
-        uu[i] = sU[rr][lx + kFocalLanes * i];
-        vv[i] = sW[rr][ly + kFocalLanes * i];
-      }
-#pragma unroll
-      for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-        for (int u = 0; u < kFocalMicro; ++u) {
-          acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
-          acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
-          acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
-          acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
-        }
-    }
+    focal_accumulate(sU, sW, L, acc_re, acc_im);
     __syncthreads();
   }
-  double2* o = reinterpret_cast<double2*>(out) + ((int64_t)slice * gridDim.y + qj) * a.ny * a.nx;
-#pragma unroll
-  for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-    for (int u = 0; u < kFocalMicro; ++u) {
-      const int l = ty0 + ly + kFocalLanes * v, j = tx0 + lx + kFocalLanes * u;
-      if (l < a.ny && j < a.nx) o[(int64_t)l * a.nx + j] = make_double2(acc_re[v][u], acc_im[v][u]);
-    }
+  focal_store(reinterpret_cast<double2*>(out) + ((int64_t)slice * gridDim.y + qj) * a.ny * a.nx, a, L, acc_re, acc_im);
 }
 
 // ------------------------------------------------------------------------------------------- wavefront
@@ -2452,9 +2412,9 @@ __global__ __launch_bounds__(kFoldBlock) void k_polarisation_fold(const ArtPolar
 // hundred operations beside the element's Parratt steps (~150 each).  Views, coatings and materials are wave-uniform:
 // scalar loads.
 // k_vecspec_field is k_focal_spectrum_field with (plane, wavenumber, component) on the grid's y dimension and the row
-// phasor W = (a . u_c) exp(i ...); a kernel of its own for the reason given above k_focal_spectrum_prep, whose rows it
-// reads.  Partials are laid out [plane][slice][wavenumber of the block][component] so that k_focal_fold folds a plane's
-// slices straight into its place in the field.
+// phasor W = (a . u_c) exp(i ...); it reads k_focal_spectrum_prep's rows.  Partials are laid out
+// [plane][slice][wavenumber of the block][component] so that k_focal_fold folds a plane's slices straight into its
+// place in the field.
 struct VecSpecArg {
   const ArtBundleView* views;
   const double* w;
@@ -2523,85 +2483,32 @@ __global__ __launch_bounds__(kBlock) void k_vecspec_field(const FocalArg a, cons
                                                           const double* __restrict__ rows,
                                                           const double* __restrict__ amps, const int64_t plane_stride,
                                                           const int64_t slice_stride, double* __restrict__ out) {
-  __shared__ double2 sU[kFocalChunk][kFocalTile];     // exp(i X_j k d.e1)
-  __shared__ double2 sW[kFocalChunk][kFocalTile];     // (a . u_c) exp(i (base + s_q k d.n + Y_l k d.e2))
+  __shared__ FocalStage sU;                           // exp(i X_j k d.e1)
+  __shared__ FocalStage sW;                           // (a . u_c) exp(i (base + s_q k d.n + Y_l k d.e2))
   const int qjc = blockIdx.y, qj = qjc / 3, comp = qjc - 3 * qj, q = qj / nkb, jj = qj - q * nkb, slice = blockIdx.z;
   const double kj = focal_kj(a.k, j0 + jj, dk);
-  const int tx0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * kFocalTile, ty0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * kFocalTile;
-  const int t = threadIdx.x, lx = t % kFocalLanes, ly = t / kFocalLanes;
+  const FocalLane L = focal_lane(a.tiles_x);
   const int64_t st = a.stride, r0 = (int64_t)slice * a.per_slice;
   const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
   const double sh = a.shift[q];
   const double* am = amps + ((int64_t)jj * 6 + 2 * comp) * st;
-  // staging role of this lane: rows (W) or columns (U), ray sr of the chunk, segment sg of the tile
-  const bool colw = t < kBlock / 2;
-  const int sr = (t % (kBlock / 2)) / (kFocalTile / kFocalSeg), sg = t % (kFocalTile / kFocalSeg);
-  double acc_re[kFocalMicro][kFocalMicro], acc_im[kFocalMicro][kFocalMicro];
-#pragma unroll
-  for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-    for (int u = 0; u < kFocalMicro; ++u) acc_re[v][u] = acc_im[v][u] = 0.0;
+  FocalAcc acc_re = {}, acc_im = {};
 
   for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
-    const int64_t r = c0 + sr;
+    const int64_t r = c0 + L.sr;
     const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
-    double ph, a_re, a_im, s_re, s_im;
-    int p0;
-    if (colw) {
-      p0 = tx0 + sg * kFocalSeg;
-      const double ka = focal_mul(kj, in ? rows[2 * st + r] : 0.0);
-      ph = ka * (a.x0 + (double)p0 * a.dx);
-      a_re = 1.0; a_im = 0.0;
-      sincos(focal_mul(ka, a.dx), &s_im, &s_re);
-    } else {
-      p0 = ty0 + sg * kFocalSeg;
-      const double base = focal_mul(kj, in ? rows[st + r] : 0.0), kb = focal_mul(kj, in ? rows[3 * st + r] : 0.0),
-                   kc = focal_mul(kj, in ? rows[4 * st + r] : 0.0);
-      ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
-      a_re = in ? am[r] : 0.0; a_im = in ? am[st + r] : 0.0;
-      sincos(focal_mul(kb, a.dy), &s_im, &s_re);
-    }
-    double sn, cs;
+    double ph, s_re, s_im, sn, cs;
+    focal_phase_terms_at(kj, a, rows, L, r, in, sh, ph, s_re, s_im);
+    const double a_re = L.colw ? 1.0 : (in ? am[r] : 0.0), a_im = L.colw || !in ? 0.0 : am[st + r];
     sincos(ph, &sn, &cs);
-    double z_re = a_re * cs - a_im * sn, z_im = a_re * sn + a_im * cs;
-    double2* dst = colw ? &sU[sr][sg * kFocalSeg] : &sW[sr][sg * kFocalSeg];
-#pragma unroll
-    for (int m = 0; m < kFocalSeg; ++m) {
-      dst[m] = make_double2(z_re, z_im);
-      const double n_re = fma(z_re, s_re, -(z_im * s_im));
-      z_im = fma(z_re, s_im, z_im * s_re);
-      z_re = n_re;
-    }
+    focal_rotate_store(sU, sW, L, a_re * cs - a_im * sn, a_re * sn + a_im * cs, s_re, s_im);
     __syncthreads();
-#pragma unroll 2
-    for (int rr = 0; rr < kFocalChunk; ++rr) {
-      double2 uu[kFocalMicro], vv[kFocalMicro];
-#pragma unroll
-      for (int i = 0; i < kFocalMicro; ++i) {
-        uu[i] = sU[rr][lx + kFocalLanes * i];
-        vv[i] = sW[rr][ly + kFocalLanes * i];
-      }
-#pragma unroll
-      for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-        for (int u = 0; u < kFocalMicro; ++u) {
-          acc_re[v][u] = fma(vv[v].x, uu[u].x, acc_re[v][u]);
-          acc_re[v][u] = fma(-vv[v].y, uu[u].y, acc_re[v][u]);
-          acc_im[v][u] = fma(vv[v].x, uu[u].y, acc_im[v][u]);
-          acc_im[v][u] = fma(vv[v].y, uu[u].x, acc_im[v][u]);
-        }
-    }
+    focal_accumulate(sU, sW, L, acc_re, acc_im);
     __syncthreads();
   }
-  double2* o = reinterpret_cast<double2*>(out) + (int64_t)q * plane_stride + (int64_t)slice * slice_stride +
-               (int64_t)(jj * 3 + comp) * a.ny * a.nx;
-#pragma unroll
-  for (int v = 0; v < kFocalMicro; ++v)
-#pragma unroll
-    for (int u = 0; u < kFocalMicro; ++u) {
-      const int l = ty0 + ly + kFocalLanes * v, j = tx0 + lx + kFocalLanes * u;
-      if (l < a.ny && j < a.nx) o[(int64_t)l * a.nx + j] = make_double2(acc_re[v][u], acc_im[v][u]);
-    }
+  focal_store(reinterpret_cast<double2*>(out) + (int64_t)q * plane_stride + (int64_t)slice * slice_stride +
+                  (int64_t)(jj * 3 + comp) * a.ny * a.nx,
+              a, L, acc_re, acc_im);
 }
 
 template <bool HAS_W>
@@ -3870,9 +3777,14 @@ int art_histogram(const ArtHistogramDesc* h, const ArtBundleView* b, const doubl
   return launched("art_histogram launch");
 }
 
+// the ranges of a focal grid and its planes
+static bool focal_shape_ok(int32_t nx, int32_t ny, int32_t planes) {
+  return nx >= 1 && ny >= 1 && nx <= ART_FOCAL_MAX_PIXELS && ny <= ART_FOCAL_MAX_PIXELS && planes >= 1 &&
+         planes <= ART_FOCAL_MAX_PLANES;
+}
+
 int64_t art_focal_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int64_t n) {
-  if (nx < 1 || ny < 1 || nx > ART_FOCAL_MAX_PIXELS || ny > ART_FOCAL_MAX_PIXELS || planes < 1 ||
-      planes > ART_FOCAL_MAX_PLANES || n < 0)
+  if (!focal_shape_ok(nx, ny, planes) || n < 0)
     return fail(ART_ERR_BAD_ARG, "focal scratch: nx, ny in [1, 2048], planes in [1, 64], n >= 0");
   const int S = focal_slices(nx, ny, planes, n);
   return (int64_t)kFocalRows * focal_stride(n) + (S > 1 ? (int64_t)S * planes * ny * nx * 2 : 0);
@@ -3880,9 +3792,8 @@ int64_t art_focal_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int64_
 
 // the checks of an ArtFocalDesc that do not depend on the call's other arguments
 static int focal_desc_check(const ArtFocalDesc* f) {
-  if (f->nx < 1 || f->ny < 1 || f->nx > ART_FOCAL_MAX_PIXELS || f->ny > ART_FOCAL_MAX_PIXELS)
-    return fail(ART_ERR_BAD_ARG, "focal grid: nx and ny must be in [1, 2048]");
-  if (f->planes < 1 || f->planes > ART_FOCAL_MAX_PLANES) return fail(ART_ERR_BAD_ARG, "focal planes must be in [1, 64]");
+  if (!focal_shape_ok(f->nx, f->ny, 1)) return fail(ART_ERR_BAD_ARG, "focal grid: nx and ny must be in [1, 2048]");
+  if (!focal_shape_ok(f->nx, f->ny, f->planes)) return fail(ART_ERR_BAD_ARG, "focal planes must be in [1, 64]");
   if (!(isfinite(f->k) && f->k > 0.0)) return fail(ART_ERR_BAD_ARG, "focal k must be finite and > 0");
   if (!(isfinite(f->dx) && isfinite(f->dy))) return fail(ART_ERR_BAD_ARG, "focal pixel pitch must be finite");
   for (int q = 0; q < f->planes; ++q)
@@ -3924,6 +3835,13 @@ static FocalArg focal_arg(const ArtFocalDesc* f, int64_t n, int S) {
   return a;
 }
 
+// field[p] = the sum of the S slices' partials at part, for p < pixels
+static void focal_fold_launch(const double* part, int S, int64_t pixels, double* field, hipStream_t s) {
+  const int64_t want = (pixels + kBlock - 1) / kBlock;
+  hipLaunchKernelGGL(k_focal_fold, dim3((int)(want > kMaxBlocks ? kMaxBlocks : want)), dim3(kBlock), 0, s,
+                     (const double2*)part, S, pixels, reinterpret_cast<double2*>(field));
+}
+
 int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
                     double* field, void* stream) {
   if (!f) return fail(ART_ERR_BAD_ARG, "focal descriptor is NULL");
@@ -3934,19 +3852,15 @@ int art_focal_field(const ArtFocalDesc* f, const ArtBundleView* b, const double*
   if (const int e = focal_call_check(b, n, scratch, field, pixels, s, &done); e || done) return e;
   const int S = focal_slices(f->nx, f->ny, f->planes, n);
   const FocalArg a = focal_arg(f, n, S);
-  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
   per_launch(n, [&](const int64_t off, const int64_t m) {
     hipLaunchKernelGGL(k_focal_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off), w ? w + off : nullptr,
                        m, scratch + off);
     return ART_OK;
   });
   double* part = S > 1 ? scratch + (int64_t)kFocalRows * a.stride : field;
-  hipLaunchKernelGGL(k_focal_field, dim3(tiles, f->planes, S), dim3(kBlock), 0, s, a, (const double*)scratch, part);
-  if (S > 1) {
-    const int64_t want = (pixels + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_focal_fold, dim3((int)(want > kMaxBlocks ? kMaxBlocks : want)), dim3(kBlock), 0, s,
-                       (const double2*)part, S, pixels, reinterpret_cast<double2*>(field));
-  }
+  hipLaunchKernelGGL(k_focal_field, dim3(focal_tiles(f->nx, f->ny), f->planes, S), dim3(kBlock), 0, s, a,
+                     (const double*)scratch, part);
+  if (S > 1) focal_fold_launch(part, S, pixels, field, s);
   return launched("art_focal_field launch");
 }
 
@@ -3959,7 +3873,7 @@ static FocalImagePlan focal_image_plan(int nx, int ny, int planes, int groups, i
   if (s > groups) s = groups;
   p.per = (groups + s - 1) / s;
   p.S = (groups + p.per - 1) / p.per;            // no empty slice
-  const int64_t wgs = (int64_t)((nx + kFocalTile - 1) / kFocalTile) * ((ny + kFocalTile - 1) / kFocalTile) * planes * groups;
+  const int64_t wgs = (int64_t)focal_tiles(nx, ny) * planes * groups;
   int64_t k = kFocalWantBlocks / wgs;
   const int64_t by_rays = (n / groups + 4 * kFocalChunk - 1) / (4 * kFocalChunk);   // 4 chunks of a mean group per piece
   if (k > by_rays) k = by_rays;
@@ -3970,8 +3884,7 @@ static FocalImagePlan focal_image_plan(int nx, int ny, int planes, int groups, i
 }
 
 int64_t art_focal_image_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int32_t groups, int64_t n) {
-  if (nx < 1 || ny < 1 || nx > ART_FOCAL_MAX_PIXELS || ny > ART_FOCAL_MAX_PIXELS || planes < 1 ||
-      planes > ART_FOCAL_MAX_PLANES || groups < 1 || groups > ART_FOCAL_MAX_GROUPS || n < 0)
+  if (!focal_shape_ok(nx, ny, planes) || groups < 1 || groups > ART_FOCAL_MAX_GROUPS || n < 0)
     return fail(ART_ERR_BAD_ARG, "focal image scratch: nx, ny in [1, 2048], planes in [1, 64], groups in [1, 2^20], n >= 0");
   const FocalImagePlan p = focal_image_plan(nx, ny, planes, groups, n);
   const int64_t pixels = (int64_t)planes * ny * nx;
@@ -3998,7 +3911,6 @@ int art_focal_image(const ArtFocalImageDesc* d, const ArtBundleView* b, const do
   }
   const FocalImagePlan p = focal_image_plan(f->nx, f->ny, f->planes, d->groups, n);
   const FocalArg a = focal_arg(f, n, 1);
-  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
   per_launch(n, [&](const int64_t off, const int64_t m) {
     hipLaunchKernelGGL(k_focal_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off), w ? w + off : nullptr,
                        m, scratch + off);
@@ -4007,8 +3919,8 @@ int art_focal_image(const ArtFocalImageDesc* d, const ArtBundleView* b, const do
   const bool direct = p.S == 1 && p.split == 1;
   double* part = direct ? image : scratch + (int64_t)kFocalRows * a.stride;
   const int jobs = p.split > 1 ? f->planes * d->groups * p.split : f->planes * p.S;   // <= 2048 or <= 64 * 64
-  hipLaunchKernelGGL(k_focal_image, dim3(tiles, jobs), dim3(kBlock), 0, s, a, (const double*)scratch, d->seg,
-                     (int)d->groups, p.per, p.S, p.split, part);
+  hipLaunchKernelGGL(k_focal_image, dim3(focal_tiles(f->nx, f->ny), jobs), dim3(kBlock), 0, s, a, (const double*)scratch,
+                     d->seg, (int)d->groups, p.per, p.S, p.split, part);
   if (!direct) {
     const int64_t want = (total + kBlock - 1) / kBlock;
     const dim3 grid((int)(want > kMaxBlocks ? kMaxBlocks : want));
@@ -4032,8 +3944,7 @@ static int focal_spectrum_check(const ArtFocalSpectrumDesc* d) {
 }
 
 int64_t art_focal_spectrum_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int32_t nk, int64_t n) {
-  if (nx < 1 || ny < 1 || nx > ART_FOCAL_MAX_PIXELS || ny > ART_FOCAL_MAX_PIXELS || planes < 1 ||
-      planes > ART_FOCAL_MAX_PLANES || nk < 1 || nk > ART_FOCAL_MAX_WAVENUMBERS || n < 0)
+  if (!focal_shape_ok(nx, ny, planes) || nk < 1 || nk > ART_FOCAL_MAX_WAVENUMBERS || n < 0)
     return fail(ART_ERR_BAD_ARG, "focal spectrum scratch: nx, ny in [1, 2048], planes in [1, 64], nk in [1, 1024], n >= 0");
   const int S = focal_slices(nx, ny, planes * nk, n);
   return (int64_t)kFocalSpecRows * focal_stride(n) + (S > 1 ? (int64_t)S * planes * nk * ny * nx * 2 : 0);
@@ -4053,20 +3964,15 @@ int art_focal_spectrum(const ArtFocalSpectrumDesc* d, const ArtBundleView* b, co
   // the slices of art_focal_field at nk = 1: the same partial sums, so the same bytes
   const int S = focal_slices(f->nx, f->ny, planes, n);
   const FocalArg a = focal_arg(f, n, S);
-  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
   per_launch(n, [&](const int64_t off, const int64_t m) {
     hipLaunchKernelGGL(k_focal_spectrum_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off),
                        w ? w + off : nullptr, m, scratch + off);
     return ART_OK;
   });
   double* part = S > 1 ? scratch + (int64_t)kFocalSpecRows * a.stride : field;
-  hipLaunchKernelGGL(k_focal_spectrum_field, dim3(tiles, planes, S), dim3(kBlock), 0, s, a, d->dk, (int)d->nk,
-                     (const double*)scratch, part);
-  if (S > 1) {
-    const int64_t want = (pixels + kBlock - 1) / kBlock;
-    hipLaunchKernelGGL(k_focal_fold, dim3((int)(want > kMaxBlocks ? kMaxBlocks : want)), dim3(kBlock), 0, s,
-                       (const double2*)part, S, pixels, reinterpret_cast<double2*>(field));
-  }
+  hipLaunchKernelGGL(k_focal_spectrum_field, dim3(focal_tiles(f->nx, f->ny), planes, S), dim3(kBlock), 0, s, a, d->dk,
+                     (int)d->nk, (const double*)scratch, part);
+  if (S > 1) focal_fold_launch(part, S, pixels, field, s);
   return launched("art_focal_spectrum launch");
 }
 
@@ -4284,7 +4190,7 @@ int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBund
   const VecSpecPlan p = vecspec_plan(d);
   const int S = p.S;
   const FocalArg a = focal_arg(f, n, S);
-  const int tiles = a.tiles_x * ((f->ny + kFocalTile - 1) / kFocalTile);
+  const int tiles = focal_tiles(f->nx, f->ny);
   VecSpecArg va;
   memset(&va, 0, sizeof(va));
   va.views = d->views; va.w = d->w;
@@ -4315,11 +4221,8 @@ int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBund
     const int64_t block = (int64_t)m * 3 * pix;               // a plane's pixels of this block
     hipLaunchKernelGGL(k_vecspec_field, dim3(tiles, f->planes * m * 3, S), dim3(kBlock), 0, s, a, d->s.dk, j0, m,
                        (const double*)scratch, (const double*)amps, (int64_t)S * block, block, part);
-    const int64_t want = (block + kBlock - 1) / kBlock;
     for (int q = 0; q < f->planes; ++q)
-      hipLaunchKernelGGL(k_focal_fold, dim3((int)(want > kMaxBlocks ? kMaxBlocks : want)), dim3(kBlock), 0, s,
-                         (const double2*)part + (int64_t)q * S * block, S, block,
-                         reinterpret_cast<double2*>(dst) + (int64_t)q * nk * 3 * pix);
+      focal_fold_launch(part + (int64_t)q * S * block * 2, S, block, dst + (int64_t)q * nk * 3 * pix * 2, s);
   }
   return launched("art_focal_vector_spectrum launch");
 }
