@@ -168,6 +168,14 @@ def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pix
     return _plots.PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size, Pixels)
 
 
+def ChromaticFocus(result):
+    """The focus of a chromatic source (the result of get_ChromaticFocalPulse with several Shifts): the on-axis spectral
+    intensity over (detector shift, omega) with the plane of best focus of every frequency drawn over it, and the
+    pulse duration per plane."""
+    from . import _plots
+    return _plots.ChromaticFocus(result)
+
+
 def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston", "tilt")):
     """The fitted wavefront (Detector.get_Wavefront) on the pupil, in waves, with the terms in `Remove` taken out, and a
     bar chart of the Zernike terms' rms contributions in waves."""

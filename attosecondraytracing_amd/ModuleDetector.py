@@ -263,6 +263,23 @@ class Detector:
         return pulse.focal_pulse(self, RayList, DeltaFT, Size, Pixels, Centre, Shifts, Wavelength, RefPath, Spectrum,
                                  TimeWindow, Times)
 
+    def get_ChromaticFocalPulse(self, RayList, SourceRays, DeltaFT, Divergence=None, Position=None, Axis=None, Size=None,
+                                Pixels=64, Centre=None, Shifts=None, Wavelength=None, RefPath=None, Spectrum=None,
+                                TimeWindow=None, Times=256):
+        """get_FocalPulse for a CHROMATIC source such as high harmonics (chromatic.ChromaticFocalPulse): every
+        frequency has its own divergence and its own apparent source position along the source's axis, applied per ray
+        and frequency in one device call.  SourceRays: the source bundle RayList was traced from, slot for slot (a
+        chain's source_rays and output rays are); Divergence: a callable omega (rad/fs, array) -> the Gaussian beam's
+        1/e^2 half-angle Theta (rad), or None for no apodisation (chromatic.gaussian_divergence makes one from a waist);
+        Position: a callable omega -> z (mm, positive downstream along the axis), a scalar, or None for 0; Axis: the
+        source's axis, default the mean direction of SourceRays.  Every other argument as in get_FocalPulse
+        (chromatic.harmonic_comb makes a Spectrum of harmonics; frequencies of weight 0 cost nothing).  Also gives the
+        plane of best focus per frequency.  Limits: the rays are not re-traced, so the model is first order in z over
+        the distance to the first optic; one axis; Gaussian apodisation only; no gratings; the scalar field only."""
+        from . import chromatic
+        return chromatic.chromatic_focal_pulse(self, RayList, SourceRays, DeltaFT, Divergence, Position, Axis, Size,
+                                               Pixels, Centre, Shifts, Wavelength, RefPath, Spectrum, TimeWindow, Times)
+
     def get_Wavefront(self, RayList, Order=8, Centre=None, Shift=0.0, RefPath=None, PupilCentre=None, PupilRadius=None,
                       Wavelength=None, PerRay=False):
         """Wavefront error of ALL alive rays about a reference point, fitted with Zernike polynomials on the device

@@ -172,6 +172,13 @@ class OpticalChain:
         return vector_pulse.vector_focal_pulse(self, Coatings, Detector, DeltaFT, Polarisation, Size, Pixels, Centre,
                                                Shifts, Wavelength, RefPath, Spectrum, TimeWindow, Times, ScratchBytes)
 
+    def get_ChromaticFocalPulse(self, Detector, DeltaFT, **kw):
+        """The pulse at focus of a chromatic (high-harmonic) source behind this chain (chromatic.ChromaticFocalPulse):
+        Detector.get_ChromaticFocalPulse with the chain's final bundle and its source_rays; every other argument
+        (Divergence, Position, Axis, Spectrum, the grid ...) as there."""
+        self._refuse_gratings("get_ChromaticFocalPulse")
+        return Detector.get_ChromaticFocalPulse(self.get_output_rays()[-1], self.source_rays, DeltaFT, **kw)
+
     def get_VectorFocalField(self, Coatings, Detector, Polarisation, Size=None, Pixels=128, Centre=None, Shifts=None,
                              Wavelength=None, RefPath=None):
         """The vector focal field at one wavelength behind the chain's coatings (vector_pulse.VectorFocalField):

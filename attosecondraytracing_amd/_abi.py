@@ -166,6 +166,15 @@ class ArtFocalSpectrumDesc(C.Structure):
     ]
 
 
+class ArtFocalChromaticDesc(C.Structure):
+    _fields_ = [
+        ("f", ArtFocalDesc),
+        ("axis", C.c_double * 3),
+        ("nk", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 ART_WAVEFRONT_MAX_ORDER = 10
 ART_WAVEFRONT_MAX_COLS = 68
 ART_WAVEFRONT_DOUBLES = 2360
@@ -302,6 +311,9 @@ PROTOTYPES = {
     "art_focal_spectrum_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "art_focal_spectrum": (C.c_int, [C.POINTER(ArtFocalSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "art_focal_chromatic_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "art_focal_chromatic": (C.c_int, [C.POINTER(ArtFocalChromaticDesc), C.POINTER(ArtBundleView), C.POINTER(ArtBundleView),
+                                      C.c_void_p, C.c_int64, C.c_void_p, c_double_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_wavefront_scratch_doubles": (C.c_int64, [C.POINTER(ArtWavefrontJob), C.c_int32]),
     "art_wavefront": (C.c_int, [C.c_void_p, C.POINTER(ArtWavefrontJob), C.c_int32, C.c_void_p, C.c_void_p]),
     "art_polarisation_scratch_doubles": (C.c_int64, [C.POINTER(ArtPolarisationJob), C.c_int32]),

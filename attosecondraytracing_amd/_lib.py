@@ -357,6 +357,28 @@ class HipBackend:
                                                  self.stream_ptr()), "art_focal_spectrum")
         return field
 
+    def focal_chromatic(self, desc, final_view, source_view, w, n, table):
+        """art_focal_chromatic on the current stream: a new device complex128 tensor [planes, nk, ny, nx].  desc: an
+        ArtFocalChromaticDesc (its nk is set here); table: host array [nk, 4] of rows (k_j, c_j, z_j, 0), uploaded here
+        and validated by the library on this host copy; scratch reused per stream."""
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != 4:
+            raise ValueError("the chromatic table must have rows (k_j, c_j, z_j, 0)")
+        f = desc.f
+        desc.nk = nk = int(table.shape[0])
+        ns = self.fn["art_focal_chromatic_scratch_doubles"](f.nx, f.ny, f.planes, nk, n)
+        if ns < 0:
+            raise ArtError(f"art_focal_chromatic_scratch_doubles failed with code {ns}: {self.last_error()}")
+        field = torch.empty((f.planes, nk, f.ny, f.nx), dtype=torch.complex128, device=self.device)
+        scratch = self.scratch("focal", ns, torch.float64)
+        table_dev = self.from_numpy(table)
+        self.check(self.fn["art_focal_chromatic"](C.byref(desc), C.byref(final_view), C.byref(source_view),
+                                                  None if (w is None or n == 0) else w.data_ptr(), n,
+                                                  table_dev.data_ptr(), table.ctypes.data_as(_abi.c_double_p),
+                                                  scratch.data_ptr(), field.data_ptr(), self.stream_ptr()),
+                   "art_focal_chromatic")
+        return field
+
     def focal_image(self, fdesc, seg, groups, view, w, n):
         """art_focal_image on the current stream: a new device float64 tensor [planes, ny, nx].  seg: device int64
         tensor of groups + 1 slot offsets (never read back); scratch reused per stream."""

@@ -559,6 +559,39 @@ def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pix
     return fig
 
 
+def ChromaticFocus(result):
+    """A chromatic.ChromaticFocalPulse through focus: the spectral intensity |E_j|^2 at the pixel nearest the grid's
+    centre over (detector shift, omega) with best_focus drawn over it, and the on-peak and integrated duration (fs) per
+    plane.  Frequencies of weight 0 are blank."""
+    plt = _plt()
+    p = result
+    ny, nx = p.spectrum.shape[2:]
+    on_axis = np.abs(p.spectrum[:, :, (ny - 1) // 2, (nx - 1) // 2].cpu().numpy()) ** 2        # [P, J]
+    used = np.abs(p.weights) > 0
+    image = np.where(used[None, :], on_axis, np.nan)
+    order = np.argsort(p.shifts)
+    plt.ion()
+    fig, (a1, a2) = plt.subplots(2, 1)
+    if len(order) > 1 and len(p.omega) > 1:
+        mesh = a1.pcolormesh(p.shifts[order], p.omega, image[order].T, shading="nearest")
+        fig.colorbar(mesh, ax=a1, label="|E|^2 on axis")
+    else:
+        a1.plot(p.omega, image[0], ".")
+    a1.plot(p.best_focus[used], p.omega[used], "w.", markersize=3, label="best focus")
+    a1.set_xlabel("Detector shift (mm)")
+    a1.set_ylabel("omega (rad/fs)")
+    a1.set_title("Chromatic focus")
+    a1.legend(loc="upper right")
+    a2.plot(p.shifts[order], p.duration[order], "o-", label="on peak")
+    a2.plot(p.shifts[order], p.duration_integrated[order], "s-", label="integrated")
+    a2.set_xlabel("Detector shift (mm)")
+    a2.set_ylabel("Duration (fs)")
+    a2.legend(loc="upper right")
+    fig._art_pulse = p
+    plt.show()
+    return fig
+
+
 def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston", "tilt")):
     """The fitted wavefront on the unit pupil in waves (Detector.get_Wavefront, `Remove`d terms taken out) beside a bar
     chart of every term's rms contribution in waves; rms, rms at the best reference point and the Marechal Strehl ratio

@@ -1955,6 +1955,97 @@ __global__ __launch_bounds__(kBlock) void k_focal_spectrum_field(const FocalArg 
   focal_store(reinterpret_cast<double2*>(out) + ((int64_t)slice * gridDim.y + qj) * a.ny * a.nx, a, L, acc_re, acc_im);
 }
 
+// ------------------------------------------------------------------------------------------- focal chromatic
+// art_focal_chromatic (include/art_hip.h): art_focal_spectrum's sum for a source whose divergence and apparent position
+// along the unit axis a depend on the frequency.  Per slot r, from the slot-aligned SOURCE bundle's direction s_r,
+//     u_r = 0.5 * (((s_x - a_x)^2 + (s_y - a_y)^2) + (s_z - a_z)^2)        (this order, no fma: 1 - cos theta_r)
+// and per wavenumber j a table row (k_j, c_j, z_j, 0):
+//     field[q][j] = sum_r sqrt(w_r) exp(-(u_r c_j)) exp(i [k_j * (base_r / k + z_j * u_r) + shift, X and Y terms])
+// k_focal_chromatic_prep is k_focal_spectrum_prep with a sixth row u (a dead slot of the FINAL bundle gets u = 0,
+// whatever the source slot holds).  k_focal_chromatic_field is k_focal_spectrum_field with k_j read from the table (one
+// row per workgroup, uniform) and the two new terms in the row-phasor staging lanes: base_r / k + z_j * u_r before the
+// product with k_j, and the amplitude times exp(-(u_r c_j)).  With c_j = z_j = 0 these add +0.0 and multiply by 1: the
+// roundings, and so the bytes, of k_focal_spectrum_field at k = k_j.  Everything after the phase terms is the shared code.
+constexpr int kFocalChromRows = 6;    // amp, base / k, d.e1, d.e2, d.n, u
+
+__global__ __launch_bounds__(kBlock) void k_focal_chromatic_prep(const FocalArg a, const ArtBundleView b,
+                                                                 const ArtBundleView src, const double ax,
+                                                                 const double ay, const double az, const double* w,
+                                                                 const int64_t m, double* rows) {
+#pragma clang fp contract(off)
+  const int64_t st = a.stride;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
+    const bool live = b.alive[i] != 0;
+    const double px = b.ox[i], py = b.oy[i], pz = b.oz[i], dx = b.dx[i], dy = b.dy[i], dz = b.dz[i];
+    const double sx = src.dx[i] - ax, sy = src.dy[i] - ay, sz = src.dz[i] - az;
+    // a dead slot's values are unspecified (possibly NaN), in either bundle: selected away
+    const double amp = live ? (w ? sqrt(w[i]) : 1.0) : 0.0;
+    const double base = live ? (b.path[i] - a.L_ref) + ((dx * (a.C[0] - px) + dy * (a.C[1] - py)) + dz * (a.C[2] - pz))
+                             : 0.0;
+    const double da = live ? (dx * a.e1[0] + dy * a.e1[1]) + dz * a.e1[2] : 0.0;
+    const double db = live ? (dx * a.e2[0] + dy * a.e2[1]) + dz * a.e2[2] : 0.0;
+    const double dc = live ? (dx * a.nrm[0] + dy * a.nrm[1]) + dz * a.nrm[2] : 0.0;
+    const double u = live ? 0.5 * ((sx * sx + sy * sy) + sz * sz) : 0.0;
+    rows[i] = amp; rows[st + i] = base; rows[2 * st + i] = da; rows[3 * st + i] = db; rows[4 * st + i] = dc;
+    rows[5 * st + i] = u;
+  }
+}
+
+// base / k + z_j * u, unfused: with z_j = 0 it is base / k itself
+__device__ __forceinline__ double focal_chromatic_path(const double base, const double zj, const double u) {
+#pragma clang fp contract(off)
+  return base + zj * u;
+}
+
+// focal_phase_terms_at for a source moved by zj along the axis (u: the slot's row 5, 0 outside the workgroup's rays):
+// the column lanes' terms are focal_phase_terms_at's own, the row lanes' have base / k + zj * u in place of base / k
+__device__ __forceinline__ void focal_phase_terms_chromatic(const double kj, const double zj, const double u,
+                                                            const FocalArg& a, const double* __restrict__ rows,
+                                                            const FocalLane& L, const int64_t r, const bool in,
+                                                            const double sh, double& ph, double& s_re, double& s_im) {
+  if (L.colw) {
+    focal_phase_terms_at(kj, a, rows, L, r, in, sh, ph, s_re, s_im);
+    return;
+  }
+  const int64_t st = a.stride;
+  const int p0 = L.ty0 + L.sg * kFocalSeg;
+  const double base = focal_mul(kj, focal_chromatic_path(in ? rows[st + r] : 0.0, zj, u)),
+               kb = focal_mul(kj, in ? rows[3 * st + r] : 0.0), kc = focal_mul(kj, in ? rows[4 * st + r] : 0.0);
+  ph = (base + sh * kc) + kb * (a.y0 + (double)p0 * a.dy);
+  sincos(focal_mul(kb, a.dy), &s_im, &s_re);
+}
+
+// blockIdx.y = q * nk + j (plane q, table row j): out is [slice][planes][nk][ny][nx]
+__global__ __launch_bounds__(kBlock) void k_focal_chromatic_field(const FocalArg a, const double* __restrict__ table,
+                                                                  const int nk, const double* __restrict__ rows,
+                                                                  double* __restrict__ out) {
+  __shared__ FocalStage sU;                           // exp(i X_j k d.e1)
+  __shared__ FocalStage sW;                           // amp exp(-u c) exp(i (k (base / k + z u) + s_q k d.n + Y_l k d.e2))
+  const int qj = blockIdx.y, q = qj / nk, slice = blockIdx.z;
+  const double* row = table + 4 * (qj - q * nk);      // (k_j, c_j, z_j, 0): the same for every lane
+  const double kj = row[0], cj = row[1], zj = row[2];
+  const FocalLane L = focal_lane(a.tiles_x);
+  const int64_t r0 = (int64_t)slice * a.per_slice;
+  const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
+  const double sh = a.shift[q];
+  FocalAcc acc_re = {}, acc_im = {};
+
+  for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
+    const int64_t r = c0 + L.sr;
+    const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
+    double ph, s_re, s_im, sn, cs;
+    const double u = (!L.colw && in) ? rows[5 * a.stride + r] : 0.0;
+    focal_phase_terms_chromatic(kj, zj, u, a, rows, L, r, in, sh, ph, s_re, s_im);
+    const double amp = L.colw ? 1.0 : (in ? rows[r] : 0.0) * exp(-focal_mul(u, cj));
+    sincos(ph, &sn, &cs);
+    focal_rotate_store(sU, sW, L, amp * cs, amp * sn, s_re, s_im);
+    __syncthreads();
+    focal_accumulate(sU, sW, L, acc_re, acc_im);
+    __syncthreads();
+  }
+  focal_store(reinterpret_cast<double2*>(out) + ((int64_t)slice * gridDim.y + qj) * a.ny * a.nx, a, L, acc_re, acc_im);
+}
+
 // ------------------------------------------------------------------------------------------- wavefront
 // art_wavefront: per job the Gram matrix G = sum_r w_r v_r v_r^T of the rows v_r = [Z_0 .. Z_{J-1}, d.n, W_r]
 // (include/art_hip.h); the Zernike fit and the best reference point are small dense algebra on G, done by the caller.
@@ -3974,6 +4065,58 @@ int art_focal_spectrum(const ArtFocalSpectrumDesc* d, const ArtBundleView* b, co
                      (int)d->nk, (const double*)scratch, part);
   if (S > 1) focal_fold_launch(part, S, pixels, field, s);
   return launched("art_focal_spectrum launch");
+}
+
+int64_t art_focal_chromatic_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int32_t nk, int64_t n) {
+  if (!focal_shape_ok(nx, ny, planes) || nk < 1 || nk > ART_FOCAL_MAX_WAVENUMBERS || n < 0)
+    return fail(ART_ERR_BAD_ARG, "focal chromatic scratch: nx, ny in [1, 2048], planes in [1, 64], nk in [1, 1024], n >= 0");
+  const int S = focal_slices(nx, ny, planes * nk, n);
+  return (int64_t)kFocalChromRows * focal_stride(n) + (S > 1 ? (int64_t)S * planes * nk * ny * nx * 2 : 0);
+}
+
+// the checks an ArtFocalChromaticDesc and the host copy of its table add to focal_desc_check
+static int focal_chromatic_check(const ArtFocalChromaticDesc* d, const double* table_host) {
+  if (d->nk < 1 || d->nk > ART_FOCAL_MAX_WAVENUMBERS) return fail(ART_ERR_BAD_ARG, "focal chromatic: nk must be in [1, 1024]");
+  if ((int64_t)d->f.planes * d->nk > 65535) return fail(ART_ERR_BAD_ARG, "focal chromatic: planes * nk must be <= 65535");
+  const double a2 = (d->axis[0] * d->axis[0] + d->axis[1] * d->axis[1]) + d->axis[2] * d->axis[2];
+  if (!(isfinite(a2) && fabs(sqrt(a2) - 1.0) <= 1e-12)) return fail(ART_ERR_BAD_ARG, "focal chromatic: axis must be a unit vector");
+  if (!table_host) return fail(ART_ERR_BAD_ARG, "focal chromatic: the host copy of the table must not be NULL");
+  for (int j = 0; j < d->nk; ++j) {
+    const double k = table_host[4 * j], c = table_host[4 * j + 1], z = table_host[4 * j + 2];
+    if (!(isfinite(k) && k > 0.0)) return fail(ART_ERR_BAD_ARG, "focal chromatic: every k_j must be finite and > 0");
+    if (!(isfinite(c) && c >= 0.0)) return fail(ART_ERR_BAD_ARG, "focal chromatic: every c_j must be finite and >= 0");
+    if (!isfinite(z)) return fail(ART_ERR_BAD_ARG, "focal chromatic: every z_j must be finite");
+  }
+  return ART_OK;
+}
+
+int art_focal_chromatic(const ArtFocalChromaticDesc* d, const ArtBundleView* b, const ArtBundleView* src, const double* w,
+                        int64_t n, const double* table_dev, const double* table_host, double* scratch, double* field,
+                        void* stream) {
+  if (!d) return fail(ART_ERR_BAD_ARG, "focal chromatic descriptor is NULL");
+  const ArtFocalDesc* f = &d->f;
+  if (const int e = focal_desc_check(f)) return e;
+  if (const int e = focal_chromatic_check(d, table_host)) return e;
+  if (n > 0 && !table_dev) return fail(ART_ERR_BAD_ARG, "focal chromatic: the device table must not be NULL");
+  if (n > 0 && !view_ok(src)) return fail(ART_ERR_BAD_ARG, "source bundle view has a NULL array");
+  hipStream_t s = (hipStream_t)stream;
+  const int planes = f->planes * d->nk;      // (plane, wavenumber) pairs
+  const int64_t pixels = (int64_t)planes * f->ny * f->nx;
+  bool done;
+  if (const int e = focal_call_check(b, n, scratch, field, pixels, s, &done); e || done) return e;
+  // the slices of art_focal_spectrum at the same nk: the same partial sums, so a neutral table gives its bytes
+  const int S = focal_slices(f->nx, f->ny, planes, n);
+  const FocalArg a = focal_arg(f, n, S);
+  per_launch(n, [&](const int64_t off, const int64_t m) {
+    hipLaunchKernelGGL(k_focal_chromatic_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off),
+                       view_at(*src, off), d->axis[0], d->axis[1], d->axis[2], w ? w + off : nullptr, m, scratch + off);
+    return ART_OK;
+  });
+  double* part = S > 1 ? scratch + (int64_t)kFocalChromRows * a.stride : field;
+  hipLaunchKernelGGL(k_focal_chromatic_field, dim3(focal_tiles(f->nx, f->ny), planes, S), dim3(kBlock), 0, s, a,
+                     table_dev, (int)d->nk, (const double*)scratch, part);
+  if (S > 1) focal_fold_launch(part, S, pixels, field, s);
+  return launched("art_focal_chromatic launch");
 }
 
 // validates a job table; *nmax, *kmax: the largest slot count and column count

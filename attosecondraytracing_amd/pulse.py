@@ -3,7 +3,8 @@ Detector.get_FocalPulse.
 
 All optics are mirrors, so one traced bundle serves every frequency of the pulse; here they are also taken as achromatic
 (only the phase k (optical path) changes with k) -- coatings whose reflection depends on the frequency, and the vector
-field they act on, are OpticalChain.get_FocalPulse (vector_pulse.py).  The focal field of focal.py (see its docstring for the model and its limits) is summed at J
+field they act on, are OpticalChain.get_FocalPulse (vector_pulse.py); sources whose divergence and position depend on the
+frequency are Detector.get_ChromaticFocalPulse (chromatic.py).  The focal field of focal.py (see its docstring for the model and its limits) is summed at J
 wavenumbers k_j = omega_j / c in one device call, and a Fourier sum over them gives the envelope in time:
 
     A(x, y, t) = sum_j g_j E_j(x, y) exp(-i (omega_j - omega_0) t) / sum_j |g_j|,     g_j = s(omega_j) omega_j / omega_0

@@ -389,6 +389,44 @@ int64_t art_focal_spectrum_scratch_doubles(int32_t nx, int32_t ny, int32_t plane
 int art_focal_spectrum(const ArtFocalSpectrumDesc* s, const ArtBundleView* b, const double* w, int64_t n,
                        double* scratch, double* field, void* stream);
 
+/* Focal fields of one bundle from a CHROMATIC source (added under ABI 14: ArtFocalChromaticDesc, art_focal_chromatic,
+ * art_focal_chromatic_scratch_doubles): art_focal_spectrum's sum with an amplitude and a phase per ray AND wavenumber,
+ * for sources (high harmonics) whose divergence and apparent position along the axis depend on the frequency.
+ * b is the bundle at focus, src the SOURCE bundle it was traced from, slot-aligned (slot r of src became slot r of b);
+ * only src's directions s_r are read.  With the unit vector `axis` = a, per slot
+ *     u_r = 0.5 * (((s_x - a_x)^2 + (s_y - a_y)^2) + (s_z - a_z)^2)       (this order, no fma)
+ * which is 1 - cos(angle between s_r and a) without cancellation, and per wavenumber j a table row of four doubles
+ *     (k_j, c_j, z_j, 0):  k_j > 0 the wavenumber (1/mm; ANY list, not a progression), c_j >= 0 the apodisation,
+ *                          z_j (mm) the offset of that wavenumber's apparent source along a, positive downstream,
+ *     field[q][j][l][i] = sum_r sqrt(w_r) exp(-(u_r c_j)) exp(i [k_j * (base_r / k + z_j * u_r) + shift, X and Y terms])
+ * base_r / k and the shift, X and Y terms exactly art_focal_spectrum's, in its operation order; z_j * u_r and the sum
+ * base_r / k + z_j * u_r are each one rounding (no fma), and the amplitude is sqrt(w_r) * exp(-(u_r * c_j)).
+ * k_j z_j u_r is the phase of a spherical wave centred at S + z_j a relative to one centred at the source point S, its
+ * on-axis constant dropped; exp(-u c_j) with c_j = 2 / Theta_j^2 is a Gaussian beam whose intensity falls to 1/e^2 at
+ * the half-angle Theta_j.  The rays are NOT re-traced: the model is first order in z_j over the distance to the first
+ * optic, has one axis, Gaussian apodisation only, and sums the scalar field only.
+ * A row with c_j = 0 and z_j = 0 adds +0.0 and multiplies by exp(-0) = 1: with k_j = f.k + j * dk formed as
+ * art_focal_spectrum forms them, the table gives that function's bytes.
+ * A dead slot of b contributes nothing, whatever it or the slot of src holds (NaN included).
+ * table_dev: DEVICE, 4 * nk doubles; table_host: the same values on the HOST, which the validation reads (the device
+ * copy is never read back).  field (DEVICE, complex128, [planes][nk][ny][nx]) is written, not added to; n = 0 writes
+ * zeros.  Fixed summation order (no float atomics): the same bytes on every call with the same arguments.
+ * scratch: DEVICE, art_focal_chromatic_scratch_doubles(nx, ny, planes, nk, n) doubles (-1 on arguments out of range).
+ * Limits: all of art_focal_field's on f (f.k is checked but not used: the table holds the wavenumbers),
+ * 1 <= nk <= ART_FOCAL_MAX_WAVENUMBERS, planes * nk <= 65535, | |axis| - 1 | <= 1e-12, table_host non-NULL, every k_j
+ * finite and > 0, every c_j finite and >= 0, every z_j finite, table_dev and src's arrays non-NULL when n > 0:
+ * ART_ERR_BAD_ARG otherwise, with nothing launched and field untouched. */
+typedef struct ArtFocalChromaticDesc {
+  ArtFocalDesc f;         /* grid, planes, detector, L_ref: art_focal_field's; f.k only checked                    */
+  double axis[3];         /* a: the unit axis of the source                                                        */
+  int32_t nk;             /* rows of the table                                                                     */
+  int32_t reserved;
+} ArtFocalChromaticDesc;
+int64_t art_focal_chromatic_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, int32_t nk, int64_t n);
+int art_focal_chromatic(const ArtFocalChromaticDesc* d, const ArtBundleView* b, const ArtBundleView* src, const double* w,
+                        int64_t n, const double* table_dev, const double* table_host, double* scratch, double* field,
+                        void* stream);
+
 /* Wavefront aberrations of MANY bundles in one call (added under ABI 14: ArtWavefrontJob, art_wavefront,
  * art_wavefront_scratch_doubles).  Per job, with C = det.centre, e1, e2 = rows 0, 1 of det.rot, n = det.normal (the
  * frame of art_focal_field):
