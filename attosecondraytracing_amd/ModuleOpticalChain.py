@@ -172,12 +172,21 @@ class OpticalChain:
         return vector_pulse.vector_focal_pulse(self, Coatings, Detector, DeltaFT, Polarisation, Size, Pixels, Centre,
                                                Shifts, Wavelength, RefPath, Spectrum, TimeWindow, Times, ScratchBytes)
 
-    def get_ChromaticFocalPulse(self, Detector, DeltaFT, **kw):
+    def get_ChromaticFocalPulse(self, Detector, DeltaFT, *, Coatings=None, **kw):
         """The pulse at focus of a chromatic (high-harmonic) source behind this chain (chromatic.ChromaticFocalPulse):
         Detector.get_ChromaticFocalPulse with the chain's final bundle and its source_rays; every other argument
-        (Divergence, Position, Axis, Spectrum, the grid ...) as there."""
+        (Divergence, Position, Axis, Spectrum, the grid ...) as there.
+        With Coatings= (and Polarisation=, required then; ScratchBytes= optional; all three as in get_FocalPulse) the
+        VECTOR field behind the chain's coatings (chromatic.ChromaticVectorFocalPulse): the chromatic source sets which
+        harmonic focuses where, the coatings which harmonics survive and with what group delay."""
         self._refuse_gratings("get_ChromaticFocalPulse")
-        return Detector.get_ChromaticFocalPulse(self.get_output_rays()[-1], self.source_rays, DeltaFT, **kw)
+        if Coatings is None:
+            for name in ("Polarisation", "ScratchBytes"):
+                if name in kw:
+                    raise TypeError(f"get_ChromaticFocalPulse: {name} needs Coatings")
+            return Detector.get_ChromaticFocalPulse(self.get_output_rays()[-1], self.source_rays, DeltaFT, **kw)
+        from . import chromatic
+        return chromatic.vector_chromatic_focal_pulse(self, Coatings, Detector, DeltaFT, kw.pop("Polarisation", None), **kw)
 
     def get_VectorFocalField(self, Coatings, Detector, Polarisation, Size=None, Pixels=128, Centre=None, Shifts=None,
                              Wavelength=None, RefPath=None):

@@ -263,6 +263,13 @@ class ArtFocalVectorSpectrumDesc(C.Structure):
     ]
 
 
+class ArtFocalVectorChromaticDesc(C.Structure):
+    _fields_ = [
+        ("v", ArtFocalVectorSpectrumDesc),
+        ("axis", C.c_double * 3),
+    ]
+
+
 ART_FOCAL_MAX_GROUPS = 1 << 20
 
 
@@ -323,6 +330,11 @@ PROTOTYPES = {
     "art_focal_vector_spectrum": (C.c_int, [C.POINTER(ArtFocalVectorSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p,
                                             C.POINTER(ArtCoating), C.POINTER(ArtCoatingMaterial), C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    "art_focal_vector_chromatic_scratch_doubles": (C.c_int64, [C.POINTER(ArtFocalVectorChromaticDesc)]),
+    "art_focal_vector_chromatic": (C.c_int, [C.POINTER(ArtFocalVectorChromaticDesc), C.POINTER(ArtBundleView),
+                                             C.POINTER(ArtBundleView), C.c_void_p, C.POINTER(ArtCoating),
+                                             C.POINTER(ArtCoatingMaterial), C.c_void_p, c_double_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "art_focal_image_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "art_focal_image": (C.c_int, [C.POINTER(ArtFocalImageDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),

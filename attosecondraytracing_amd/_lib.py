@@ -622,6 +622,31 @@ class HipBackend:
                    "art_focal_vector_spectrum")
         return field
 
+    def focal_vector_chromatic(self, vcdesc, views, coatings, materials, table):
+        """art_focal_vector_chromatic on the current stream: a new device complex128 tensor [planes, nk, 3, ny, nx].
+        vcdesc: an ArtFocalVectorChromaticDesc (its v.s.nk is set here); views, coatings, materials as
+        focal_vector_tables, one row of materials per row of the table; table: host array [nk, 4] of rows
+        (k_j, c_j, z_j, 0), uploaded here and validated by the library on this host copy; scratch reused per stream."""
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != 4:
+            raise ValueError("the chromatic table must have rows (k_j, c_j, z_j, 0)")
+        v = vcdesc.v
+        v.s.nk = nk = int(table.shape[0])
+        f = v.s.f
+        cdev, carr, marr = self.focal_vector_tables(v, views, coatings, materials)
+        ns = self.fn["art_focal_vector_chromatic_scratch_doubles"](C.byref(vcdesc))
+        if ns < 0:
+            raise ArtError(f"art_focal_vector_chromatic_scratch_doubles failed with code {ns}: {self.last_error()}")
+        field = torch.empty((f.planes, nk, 3, f.ny, f.nx), dtype=torch.complex128, device=self.device)
+        scratch = self.scratch("focal vector", ns, torch.float64)
+        table_dev = self.from_numpy(table)
+        self.check(self.fn["art_focal_vector_chromatic"](C.byref(vcdesc), C.byref(views[v.n_elems]), C.byref(views[0]),
+                                                         cdev, carr, marr, table_dev.data_ptr(),
+                                                         table.ctypes.data_as(_abi.c_double_p), scratch.data_ptr(),
+                                                         field.data_ptr(), self.stream_ptr()),
+                   "art_focal_vector_chromatic")
+        return field
+
     def analyse_bundles(self, jobs, n):
         """art_analyse_bundles for a list of ArtAnalysisJob (host structs): uploads the job table, enqueues the four
         launches and returns the DEVICE tensor out[len(jobs), 64] -- nothing is read back here."""

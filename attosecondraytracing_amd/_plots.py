@@ -560,13 +560,17 @@ def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pix
 
 
 def ChromaticFocus(result):
-    """A chromatic.ChromaticFocalPulse through focus: the spectral intensity |E_j|^2 at the pixel nearest the grid's
-    centre over (detector shift, omega) with best_focus drawn over it, and the on-peak and integrated duration (fs) per
-    plane.  Frequencies of weight 0 are blank."""
+    """A chromatic.ChromaticFocalPulse, or a chromatic.ChromaticVectorFocalPulse (behind coatings), through focus: the
+    spectral intensity |E_j|^2 (the vector result: sum_c |F_c|^2) at the pixel nearest the grid's centre over (detector
+    shift, omega) with best_focus drawn over it, and the on-peak and integrated duration (fs) per plane.  Frequencies of
+    weight 0 are blank."""
     plt = _plt()
     p = result
-    ny, nx = p.spectrum.shape[2:]
-    on_axis = np.abs(p.spectrum[:, :, (ny - 1) // 2, (nx - 1) // 2].cpu().numpy()) ** 2        # [P, J]
+    ny, nx = p.spectrum.shape[-2:]
+    if p.spectrum.dim() == 5:
+        on_axis = (np.abs(p.spectrum[:, :, :, (ny - 1) // 2, (nx - 1) // 2].cpu().numpy()) ** 2).sum(axis=2)   # [P, J]
+    else:
+        on_axis = np.abs(p.spectrum[:, :, (ny - 1) // 2, (nx - 1) // 2].cpu().numpy()) ** 2        # [P, J]
     used = np.abs(p.weights) > 0
     image = np.where(used[None, :], on_axis, np.nan)
     order = np.argsort(p.shifts)

@@ -13,8 +13,11 @@ z_j = Position(omega_j) (mm, positive downstream).  All frequencies and planes a
 frequency grid, the weights g_j and the Fourier sum are pulse.py's.
 
 Limits of the model: the rays are not re-traced, so it is first order in z_j over the distance to the first optic;
-there is one axis for all frequencies; the apodisation is Gaussian only; chains with gratings are refused; the field is
-the scalar one (coatings and polarisation: OpticalChain.get_FocalPulse, which takes the source as achromatic)."""
+there is one axis for all frequencies; the apodisation is Gaussian only; chains with gratings are refused.
+Detector.get_ChromaticFocalPulse sums the scalar field; OpticalChain.get_ChromaticFocalPulse(..., Coatings=, Polarisation=)
+sums the vector field behind the chain's coatings (art_focal_vector_chromatic, vector_chromatic_focal_pulse below): per
+ray and frequency the amplitude above times the field vector_pulse.py carries through the mirrors, so the pulse train
+at focus has both what the source and what the coatings do to every harmonic."""
 import math
 
 import numpy as np
@@ -22,6 +25,7 @@ import numpy as np
 from . import _abi
 from . import focal
 from . import pulse
+from . import vector_pulse
 from .bundle import RayBundle
 
 C_MM_PER_FS = pulse.C_MM_PER_FS
@@ -134,33 +138,16 @@ def _axis(Axis, S):
     return a / np.linalg.norm(a)
 
 
-def chromatic_focal_pulse(det, RayList, SourceRays, DeltaFT, Divergence=None, Position=None, Axis=None, Size=None,
-                          Pixels=64, Centre=None, Shifts=None, Wavelength=None, RefPath=None, Spectrum=None,
-                          TimeWindow=None, Times=256):
-    """Detector.get_ChromaticFocalPulse (see the module's docstring).  RayList: the bundle at focus; SourceRays: the
-    source bundle it was traced from, slot for slot.  Divergence: a callable omega (rad/fs, array) -> Theta (rad, finite
-    and > 0) or None (no apodisation); Position: a callable omega -> z (mm), a scalar, or None (0); Axis: the source's
-    axis (default: the mean direction of SourceRays).  Every other argument as in get_FocalPulse.  Frequencies whose
-    weight g_j is 0 are left out of the device call."""
-    import torch
-    DeltaFT, TimeWindow, Nt = pulse.check_pulse_args(DeltaFT, TimeWindow, Times, Spectrum)
+def _check_source_args(Divergence, Position):
     if Divergence is not None and not callable(Divergence):
         raise TypeError("Divergence must be None or a callable omega -> half-angle (rad)")
     if Position is not None and not callable(Position) and (
             isinstance(Position, bool) or not isinstance(Position, (int, float, np.integer, np.floating))):
         raise TypeError("Position must be None, a distance (mm) or a callable omega -> distance")
-    if SourceRays is None:
-        raise TypeError("SourceRays is required: the source bundle the rays were traced from")
-    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
-    S = SourceRays if isinstance(SourceRays, RayBundle) else RayBundle.from_ray_list(SourceRays)
-    if getattr(B, "grooves", None) is not None or getattr(S, "grooves", None) is not None:
-        raise NotImplementedError("get_ChromaticFocalPulse: these rays crossed a grating, so one bundle no longer serves "
-                                  "all frequencies; trace one bundle per wavelength with OpticalChain.get_SpectralRays")
-    if S.n_slots != B.n_slots:
-        raise ValueError(f"SourceRays has {S.n_slots} slots and the rays at focus {B.n_slots}: the two bundles must be "
-                         "slot-aligned (the chain's history is)")
-    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
-    T, omega0, m, dw, omega, g, gsum = pulse.spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, s)
+
+
+def _source_model(Divergence, Position, Axis, S, omega, dw):
+    """Per frequency of omega (spacing dw): Theta_j, z_j, the unit axis, c_j = 2 / Theta_j^2 and the wavenumbers k_j."""
     J = len(omega)
     theta = np.full(J, np.inf) if Divergence is None else _per_frequency(Divergence, omega, "Divergence", True)
     if Position is None or not callable(Position):
@@ -175,6 +162,34 @@ def chromatic_focal_pulse(det, RayList, SourceRays, DeltaFT, Divergence=None, Po
     if not np.isfinite(c).all():
         raise ValueError("Divergence is too small: 2 / Theta^2 overflows")
     kj = omega[0] / C_MM_PER_FS + np.arange(J) * (dw / C_MM_PER_FS)     # art_focal_spectrum's k_j, formed as it forms them
+    return theta, z, axis, c, kj
+
+
+def chromatic_focal_pulse(det, RayList, SourceRays, DeltaFT, Divergence=None, Position=None, Axis=None, Size=None,
+                          Pixels=64, Centre=None, Shifts=None, Wavelength=None, RefPath=None, Spectrum=None,
+                          TimeWindow=None, Times=256):
+    """Detector.get_ChromaticFocalPulse (see the module's docstring).  RayList: the bundle at focus; SourceRays: the
+    source bundle it was traced from, slot for slot.  Divergence: a callable omega (rad/fs, array) -> Theta (rad, finite
+    and > 0) or None (no apodisation); Position: a callable omega -> z (mm), a scalar, or None (0); Axis: the source's
+    axis (default: the mean direction of SourceRays).  Every other argument as in get_FocalPulse.  Frequencies whose
+    weight g_j is 0 are left out of the device call."""
+    import torch
+    DeltaFT, TimeWindow, Nt = pulse.check_pulse_args(DeltaFT, TimeWindow, Times, Spectrum)
+    _check_source_args(Divergence, Position)
+    if SourceRays is None:
+        raise TypeError("SourceRays is required: the source bundle the rays were traced from")
+    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+    S = SourceRays if isinstance(SourceRays, RayBundle) else RayBundle.from_ray_list(SourceRays)
+    if getattr(B, "grooves", None) is not None or getattr(S, "grooves", None) is not None:
+        raise NotImplementedError("get_ChromaticFocalPulse: these rays crossed a grating, so one bundle no longer serves "
+                                  "all frequencies; trace one bundle per wavelength with OpticalChain.get_SpectralRays")
+    if S.n_slots != B.n_slots:
+        raise ValueError(f"SourceRays has {S.n_slots} slots and the rays at focus {B.n_slots}: the two bundles must be "
+                         "slot-aligned (the chain's history is)")
+    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+    T, omega0, m, dw, omega, g, gsum = pulse.spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, s)
+    J = len(omega)
+    theta, z, axis, c, kj = _source_model(Divergence, Position, Axis, S, omega, dw)
     keep = np.abs(g) > 0
     table = np.stack([kj[keep], c[keep], z[keep], np.zeros(int(keep.sum()))], axis=1)
     d = _abi.ArtFocalChromaticDesc()
@@ -204,3 +219,66 @@ def chromatic_focal_pulse(det, RayList, SourceRays, DeltaFT, Divergence=None, Po
         best[keep] = np.asarray(shifts, dtype=float)[np.argmax(on_axis, axis=0)]
     return ChromaticFocalPulse(theta, z, axis, best, spectrum, envelope.reshape(P, Nt, ny, nx), omega, omega0, g, t, T, x,
                                y, shifts, DeltaFT, wavelength, ref, amplitude_sum)
+
+
+class ChromaticVectorFocalPulse(vector_pulse.VectorFocalPulse):
+    """vector_pulse.VectorFocalPulse of a chromatic source, and: divergence [J], position [J], axis as in
+    ChromaticFocalPulse; best_focus [J]: the value of Shifts with the largest sum_c |F_c|^2 at the pixel nearest the
+    grid's centre (NaN for a frequency of weight 0 and without alive rays).  amplitude_sum is ChromaticFocalPulse's, the
+    ideal peak of the same apodised source, so `strehl` reads "against a perfect focus of this apodised source behind
+    lossless mirrors".  The slices of `spectrum` at frequencies of weight 0 are 0."""
+
+    def __init__(self, divergence, position, axis, best_focus, *args):
+        super().__init__(*args)
+        self.divergence, self.position = np.asarray(divergence, dtype=float), np.asarray(position, dtype=float)
+        self.axis, self.best_focus = np.asarray(axis, dtype=float), np.asarray(best_focus, dtype=float)
+
+
+def vector_chromatic_focal_pulse(chain, Coatings, Detector, DeltaFT, Polarisation, Divergence=None, Position=None, Axis=None,
+                                 Size=None, Pixels=64, Centre=None, Shifts=None, Wavelength=None, RefPath=None,
+                                 Spectrum=None, TimeWindow=None, Times=256, ScratchBytes=None):
+    """OpticalChain.get_ChromaticFocalPulse with Coatings (see the module's docstring): chromatic_focal_pulse's source
+    model, frequency grid and weights with vector_pulse.vector_focal_pulse's coatings, input state and history, in one
+    device call.  Frequencies whose weight g_j is 0 are left out of it, and the materials' tables are evaluated at the
+    others only."""
+    import torch
+    DeltaFT, TimeWindow, Nt = pulse.check_pulse_args(DeltaFT, TimeWindow, Times, Spectrum)
+    _check_source_args(Divergence, Position)
+    coats, P, bundles = vector_pulse._setup(chain, Coatings, Detector, Polarisation)
+    S, B = bundles[0], bundles[-1]
+    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(Detector, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+    T, omega0, m, dw, omega, g, gsum = pulse.spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, s)
+    vector_pulse._check_state(bundles, P)
+    J = len(omega)
+    theta, z, axis, c, kj = _source_model(Divergence, Position, Axis, S, omega, dw)
+    keep = np.abs(g) > 0
+    table = np.stack([kj[keep], c[keep], z[keep], np.zeros(int(keep.sum()))], axis=1)
+    sd = _abi.ArtFocalSpectrumDesc()             # (k_0 and dk are checked by the library, not used: the table holds the k_j)
+    sd.f = fd
+    sd.f.k = omega[0] / C_MM_PER_FS
+    sd.dk = dw / C_MM_PER_FS
+    sd.nk = len(table)
+    field = vector_pulse._vector_spectrum(bundles, coats, P, sd, 2 * math.pi / kj[keep], ScratchBytes,
+                                          chromatic=(axis, table))                    # [P, kept, 3, ny, nx]
+    Pn, Jk, _, ny, nx = field.shape
+    dev = field.device
+    kept = field * torch.as_tensor(g[keep], device=dev)[None, :, None, None, None]
+    if Jk == J:
+        spectrum = kept
+    else:
+        spectrum = torch.zeros((Pn, J, 3, ny, nx), dtype=kept.dtype, device=dev)
+        spectrum[:, torch.as_tensor(np.flatnonzero(keep), device=dev)] = kept
+    t, M = pulse.time_axis(T, Nt, m, dw, gsum)                                # M [Nt, J]
+    envelope = torch.matmul(torch.as_tensor(np.ascontiguousarray(M[:, keep]), device=dev), kept.reshape(Pn, Jk, 3 * ny * nx))
+    if Divergence is None:
+        amplitude_sum = focal.amplitude_sum(B)          # every S_j is the plain sum
+    else:
+        alive = B.alive[:B.n_slots] != 0
+        Sj = apodised_amplitude_sums(B, source_u(S, axis, alive), c[keep])
+        amplitude_sum = float((np.abs(g[keep]) * Sj).sum() / gsum)
+    best = np.full(J, np.nan)
+    if amplitude_sum > 0:
+        on_axis = (torch.abs(field[:, :, :, (ny - 1) // 2, (nx - 1) // 2]) ** 2).sum(dim=2).cpu().numpy()   # [P, kept]
+        best[keep] = np.asarray(shifts, dtype=float)[np.argmax(on_axis, axis=0)]
+    return ChromaticVectorFocalPulse(theta, z, axis, best, spectrum, envelope.reshape(Pn, Nt, 3, ny, nx), omega, omega0, g,
+                                     t, T, x, y, shifts, DeltaFT, wavelength, ref, amplitude_sum)

@@ -2516,13 +2516,18 @@ struct VecSpecArg {
   int32_t coating[ART_POLARISATION_MAX_ELEMS];
 };
 
-__global__ __launch_bounds__(kBlock, 4) void k_vecspec_rays(const VecSpecArg a, const ArtCoating* __restrict__ coats,
-                                                         const ArtCoatingMaterial* __restrict__ mats,
-                                                         double* __restrict__ amp) {
+// The body of k_vecspec_rays and of k_vecchrom_rays (art_focal_vector_chromatic, below).  TABLE: k_j is row j of `table`
+// (k_j, c_j, z_j, 0) instead of focal_kj, and the amplitude sqrt(w) is multiplied by exp(-(u c_j)) with the slot's u read
+// from `urow` (k_focal_chromatic_prep's row 5) after the element loop, so that it lives through no Parratt step.
+template <bool TABLE>
+__device__ __forceinline__ void vecspec_rays_body(const VecSpecArg& a, const ArtCoating* __restrict__ coats,
+                                                  const ArtCoatingMaterial* __restrict__ mats,
+                                                  const double* __restrict__ table, const double* __restrict__ urow,
+                                                  double* __restrict__ amp) {
   __shared__ artc::cplx s_kz[ART_COATING_MAX_MATERIALS * kBlock];   // kz / k per material, one column per lane
   __shared__ double s_dir[6 * kBlock];                                     // d_in, d_out, one column per lane
   const int jj = blockIdx.y, j = a.j0 + jj;
-  const double k = focal_kj(a.k0, j, a.dk);
+  const double k = TABLE ? table[4 * j] : focal_kj(a.k0, j, a.dk);
   const int64_t n = a.n;
   const unsigned i = blockIdx.x * kBlock + threadIdx.x;
   const unsigned nb8 = (unsigned)(n * 8), nb1 = (unsigned)n;   // n <= 2^28 (checked by the host)
@@ -2557,7 +2562,8 @@ __global__ __launch_bounds__(kBlock, 4) void k_vecspec_rays(const VecSpecArg a, 
     for (int q = 0; q < 3; ++q) din[q] = dout[q];
   }
   if ((int64_t)i >= n) return;
-  const double sw = live ? sqrt(w) : 0.0;                 // (k_focal_spectrum_prep's amplitude)
+  double sw = live ? sqrt(w) : 0.0;                       // (k_focal_spectrum_prep's amplitude)
+  if (TABLE) sw *= exp(-focal_mul(urow[i], table[4 * j + 1]));   // (a dead slot's u is 0; c_j = 0: times exp(-0) = 1)
   double* row = amp + (int64_t)jj * 6 * a.stride + i;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -2566,6 +2572,12 @@ __global__ __launch_bounds__(kBlock, 4) void k_vecspec_rays(const VecSpecArg a, 
     row[(2 * c) * a.stride] = live ? sw * re : 0.0;       // a dead slot's values are unspecified: selected away
     row[(2 * c + 1) * a.stride] = live ? sw * im : 0.0;
   }
+}
+
+__global__ __launch_bounds__(kBlock, 4) void k_vecspec_rays(const VecSpecArg a, const ArtCoating* __restrict__ coats,
+                                                         const ArtCoatingMaterial* __restrict__ mats,
+                                                         double* __restrict__ amp) {
+  vecspec_rays_body<false>(a, coats, mats, nullptr, nullptr, amp);
 }
 
 // blockIdx.y = ((q * nkb + jj) * 3 + c) (plane q, wavenumber j0 + jj of the block, component c); amps: the rows of
@@ -2590,6 +2602,55 @@ __global__ __launch_bounds__(kBlock) void k_vecspec_field(const FocalArg a, cons
     const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
     double ph, s_re, s_im, sn, cs;
     focal_phase_terms_at(kj, a, rows, L, r, in, sh, ph, s_re, s_im);
+    const double a_re = L.colw ? 1.0 : (in ? am[r] : 0.0), a_im = L.colw || !in ? 0.0 : am[st + r];
+    sincos(ph, &sn, &cs);
+    focal_rotate_store(sU, sW, L, a_re * cs - a_im * sn, a_re * sn + a_im * cs, s_re, s_im);
+    __syncthreads();
+    focal_accumulate(sU, sW, L, acc_re, acc_im);
+    __syncthreads();
+  }
+  focal_store(reinterpret_cast<double2*>(out) + (int64_t)q * plane_stride + (int64_t)slice * slice_stride +
+                  (int64_t)(jj * 3 + comp) * a.ny * a.nx,
+              a, L, acc_re, acc_im);
+}
+
+// ------------------------------------------------------------------------------------------- vector focal chromatic
+// art_focal_vector_chromatic (include/art_hip.h): art_focal_vector_spectrum for art_focal_chromatic's source.  The rows
+// are k_focal_chromatic_prep's (src = views[0]; u in row 5), the wavenumbers the table's.  k_vecchrom_rays is
+// k_vecspec_rays' body with k_j from the table and the amplitude sqrt(w) exp(-(u c_j)); k_vecchrom_field is
+// k_vecspec_field with focal_phase_terms_chromatic in place of focal_phase_terms_at.  With c_j = z_j = 0 both round as
+// the kernels they come from: art_focal_vector_spectrum's bytes at the same k_j.
+__global__ __launch_bounds__(kBlock, 4) void k_vecchrom_rays(const VecSpecArg a, const ArtCoating* __restrict__ coats,
+                                                          const ArtCoatingMaterial* __restrict__ mats,
+                                                          const double* __restrict__ table,
+                                                          const double* __restrict__ urow, double* __restrict__ amp) {
+  vecspec_rays_body<true>(a, coats, mats, table, urow, amp);
+}
+
+// k_vecspec_field's grid, arguments and layout of out; table: the call's rows (k_j, c_j, z_j, 0), row j0 + jj the
+// workgroup's (uniform); rows: k_focal_chromatic_prep's
+__global__ __launch_bounds__(kBlock) void k_vecchrom_field(const FocalArg a, const double* __restrict__ table, const int j0,
+                                                           const int nkb, const double* __restrict__ rows,
+                                                           const double* __restrict__ amps, const int64_t plane_stride,
+                                                           const int64_t slice_stride, double* __restrict__ out) {
+  __shared__ FocalStage sU;                           // exp(i X_j k d.e1)
+  __shared__ FocalStage sW;                           // (a . u_c) exp(i (k (base / k + z u) + s_q k d.n + Y_l k d.e2))
+  const int qjc = blockIdx.y, qj = qjc / 3, comp = qjc - 3 * qj, q = qj / nkb, jj = qj - q * nkb, slice = blockIdx.z;
+  const double* row = table + 4 * (j0 + jj);
+  const double kj = row[0], zj = row[2];
+  const FocalLane L = focal_lane(a.tiles_x);
+  const int64_t st = a.stride, r0 = (int64_t)slice * a.per_slice;
+  const int64_t r1 = (r0 + a.per_slice < a.n) ? r0 + a.per_slice : a.n;
+  const double sh = a.shift[q];
+  const double* am = amps + ((int64_t)jj * 6 + 2 * comp) * st;
+  FocalAcc acc_re = {}, acc_im = {};
+
+  for (int64_t c0 = r0; c0 < r1; c0 += kFocalChunk) {
+    const int64_t r = c0 + L.sr;
+    const bool in = r < r1;                       // beyond the slice: a zero row phasor, nothing is added
+    double ph, s_re, s_im, sn, cs;
+    const double u = (!L.colw && in) ? rows[5 * st + r] : 0.0;
+    focal_phase_terms_chromatic(kj, zj, u, a, rows, L, r, in, sh, ph, s_re, s_im);
     const double a_re = L.colw ? 1.0 : (in ? am[r] : 0.0), a_im = L.colw || !in ? 0.0 : am[st + r];
     sincos(ph, &sn, &cs);
     focal_rotate_store(sU, sW, L, a_re * cs - a_im * sn, a_re * sn + a_im * cs, s_re, s_im);
@@ -4074,20 +4135,25 @@ int64_t art_focal_chromatic_scratch_doubles(int32_t nx, int32_t ny, int32_t plan
   return (int64_t)kFocalChromRows * focal_stride(n) + (S > 1 ? (int64_t)S * planes * nk * ny * nx * 2 : 0);
 }
 
-// the checks an ArtFocalChromaticDesc and the host copy of its table add to focal_desc_check
-static int focal_chromatic_check(const ArtFocalChromaticDesc* d, const double* table_host) {
-  if (d->nk < 1 || d->nk > ART_FOCAL_MAX_WAVENUMBERS) return fail(ART_ERR_BAD_ARG, "focal chromatic: nk must be in [1, 1024]");
-  if ((int64_t)d->f.planes * d->nk > 65535) return fail(ART_ERR_BAD_ARG, "focal chromatic: planes * nk must be <= 65535");
-  const double a2 = (d->axis[0] * d->axis[0] + d->axis[1] * d->axis[1]) + d->axis[2] * d->axis[2];
+// the checks of art_focal_chromatic's axis and of the host copy of its table of nk rows
+static int focal_chromatic_table_check(const double* axis, const int nk, const double* table_host) {
+  const double a2 = (axis[0] * axis[0] + axis[1] * axis[1]) + axis[2] * axis[2];
   if (!(isfinite(a2) && fabs(sqrt(a2) - 1.0) <= 1e-12)) return fail(ART_ERR_BAD_ARG, "focal chromatic: axis must be a unit vector");
   if (!table_host) return fail(ART_ERR_BAD_ARG, "focal chromatic: the host copy of the table must not be NULL");
-  for (int j = 0; j < d->nk; ++j) {
+  for (int j = 0; j < nk; ++j) {
     const double k = table_host[4 * j], c = table_host[4 * j + 1], z = table_host[4 * j + 2];
     if (!(isfinite(k) && k > 0.0)) return fail(ART_ERR_BAD_ARG, "focal chromatic: every k_j must be finite and > 0");
     if (!(isfinite(c) && c >= 0.0)) return fail(ART_ERR_BAD_ARG, "focal chromatic: every c_j must be finite and >= 0");
     if (!isfinite(z)) return fail(ART_ERR_BAD_ARG, "focal chromatic: every z_j must be finite");
   }
   return ART_OK;
+}
+
+// the checks an ArtFocalChromaticDesc and the host copy of its table add to focal_desc_check
+static int focal_chromatic_check(const ArtFocalChromaticDesc* d, const double* table_host) {
+  if (d->nk < 1 || d->nk > ART_FOCAL_MAX_WAVENUMBERS) return fail(ART_ERR_BAD_ARG, "focal chromatic: nk must be in [1, 1024]");
+  if ((int64_t)d->f.planes * d->nk > 65535) return fail(ART_ERR_BAD_ARG, "focal chromatic: planes * nk must be <= 65535");
+  return focal_chromatic_table_check(d->axis, d->nk, table_host);
 }
 
 int art_focal_chromatic(const ArtFocalChromaticDesc* d, const ArtBundleView* b, const ArtBundleView* src, const double* w,
@@ -4263,7 +4329,7 @@ struct VecSpecPlan {
   int S, nkb;
   int64_t stride, total;
 };
-static VecSpecPlan vecspec_plan(const ArtFocalVectorSpectrumDesc* d) {
+static VecSpecPlan vecspec_plan(const ArtFocalVectorSpectrumDesc* d, const int prep_rows = kFocalSpecRows) {
   const ArtFocalDesc& f = d->s.f;
   VecSpecPlan p;
   // (the grid rows of ONE wavenumber: a block may hold no more, and a count taken from all nk leaves a launch of a
@@ -4273,7 +4339,7 @@ static VecSpecPlan vecspec_plan(const ArtFocalVectorSpectrumDesc* d) {
   p.nkb = 1;
   p.total = 0;
   if (d->n == 0) return p;
-  const int64_t rows = (int64_t)kFocalSpecRows * p.stride;
+  const int64_t rows = (int64_t)prep_rows * p.stride;
   const int64_t per_k = 6 * p.stride + (p.S > 1 ? (int64_t)p.S * f.planes * 3 * f.ny * f.nx * 2 : 0);
   const int64_t bound = d->scratch_bound ? d->scratch_bound : ART_FOCAL_VECTOR_SCRATCH_DEFAULT;
   const int64_t fit = (bound - rows) / per_k;
@@ -4307,10 +4373,18 @@ int64_t art_focal_vector_spectrum_scratch_doubles(const ArtFocalVectorSpectrumDe
   return vecspec_plan(d).total;
 }
 
-int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBundleView* b, const ArtCoating* coatings_dev,
-                              const ArtCoating* coatings_host, const ArtCoatingMaterial* materials_host, double* scratch,
-                              double* field, void* stream) {
-  if (const int e = vecspec_check(d)) return e;
+// what art_focal_vector_chromatic adds to art_focal_vector_spectrum's call: the source view, the axis and the table
+struct VecChromArg {
+  const ArtBundleView* src;
+  const double* axis;
+  const double* table_dev;
+};
+
+// art_focal_vector_spectrum (ch NULL) and art_focal_vector_chromatic after the checks of the descriptor: the checks of
+// the tables and buffers, then the launches
+static int vecspec_run(const ArtFocalVectorSpectrumDesc* d, const VecChromArg* ch, const ArtBundleView* b,
+                       const ArtCoating* coatings_dev, const ArtCoating* coatings_host,
+                       const ArtCoatingMaterial* materials_host, double* scratch, double* field, void* stream) {
   const ArtFocalDesc* f = &d->s.f;
   const int nk = d->s.nk, nc = d->n_coatings;
   if (nc > 0 && (!coatings_dev || !coatings_host || !materials_host || !d->materials))
@@ -4326,11 +4400,14 @@ int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBund
       }
   }
   if (d->n > 0 && !d->views) return fail(ART_ERR_BAD_ARG, "focal vector spectrum: views is NULL");
+  if (ch && d->n > 0 && !ch->table_dev) return fail(ART_ERR_BAD_ARG, "focal vector chromatic: the device table must not be NULL");
+  if (ch && d->n > 0 && !view_ok(ch->src)) return fail(ART_ERR_BAD_ARG, "source bundle view has a NULL array");
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = d->n, pix = (int64_t)f->ny * f->nx;
   bool done;
   if (const int e = focal_call_check(b, n, scratch, field, (int64_t)f->planes * nk * 3 * pix, s, &done); e || done) return e;
-  const VecSpecPlan p = vecspec_plan(d);
+  const int prep_rows = ch ? kFocalChromRows : kFocalSpecRows;
+  const VecSpecPlan p = vecspec_plan(d, prep_rows);
   const int S = p.S;
   const FocalArg a = focal_arg(f, n, S);
   const int tiles = focal_tiles(f->nx, f->ny);
@@ -4344,30 +4421,72 @@ int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBund
   va.n_elems = d->n_elems; va.n_coatings = nc;
   for (int e = 0; e < d->n_elems; ++e) va.coating[e] = d->coating[e];
   per_launch(n, [&](const int64_t off, const int64_t m) {       // (one launch: n <= 2^28)
-    hipLaunchKernelGGL(k_focal_spectrum_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off),
-                       d->w ? d->w + off : nullptr, m, scratch + off);
+    if (ch)
+      hipLaunchKernelGGL(k_focal_chromatic_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off),
+                         view_at(*ch->src, off), ch->axis[0], ch->axis[1], ch->axis[2], d->w ? d->w + off : nullptr, m,
+                         scratch + off);
+    else
+      hipLaunchKernelGGL(k_focal_spectrum_prep, dim3(grid_for(m)), dim3(kBlock), 0, s, a, view_at(*b, off),
+                         d->w ? d->w + off : nullptr, m, scratch + off);
     return ART_OK;
   });
-  double* amps = scratch + (int64_t)kFocalSpecRows * a.stride;
+  double* amps = scratch + (int64_t)prep_rows * a.stride;
   double* part = amps + (int64_t)p.nkb * 6 * a.stride;
+  // the field kernel of a block of m wavenumbers from j0: planes (and slices) strided as given, into out
+  const auto field_launch = [&](const int j0, const int m, const int slices, const int64_t plane_stride,
+                                const int64_t slice_stride, double* out) {
+    const dim3 grid(tiles, f->planes * m * 3, slices);
+    if (ch)
+      hipLaunchKernelGGL(k_vecchrom_field, grid, dim3(kBlock), 0, s, a, ch->table_dev, j0, m, (const double*)scratch,
+                         (const double*)amps, plane_stride, slice_stride, out);
+    else
+      hipLaunchKernelGGL(k_vecspec_field, grid, dim3(kBlock), 0, s, a, d->s.dk, j0, m, (const double*)scratch,
+                         (const double*)amps, plane_stride, slice_stride, out);
+  };
   for (int j0 = 0; j0 < nk; j0 += p.nkb) {
     const int m = nk - j0 < p.nkb ? nk - j0 : p.nkb;
     va.j0 = j0; va.nkb = m;
-    hipLaunchKernelGGL(k_vecspec_rays, dim3((unsigned)pol_tiles(n), m), dim3(kBlock), 0, s, va, coatings_dev, d->materials,
-                       amps);
+    const dim3 rays_grid((unsigned)pol_tiles(n), m);
+    if (ch)
+      hipLaunchKernelGGL(k_vecchrom_rays, rays_grid, dim3(kBlock), 0, s, va, coatings_dev, d->materials, ch->table_dev,
+                         (const double*)scratch + 5 * a.stride, amps);
+    else
+      hipLaunchKernelGGL(k_vecspec_rays, rays_grid, dim3(kBlock), 0, s, va, coatings_dev, d->materials, amps);
     double* dst = field + (int64_t)j0 * 3 * pix * 2;          // plane 0's place of this block in the field
     if (S == 1) {
-      hipLaunchKernelGGL(k_vecspec_field, dim3(tiles, f->planes * m * 3, 1), dim3(kBlock), 0, s, a, d->s.dk, j0, m,
-                         (const double*)scratch, (const double*)amps, (int64_t)nk * 3 * pix, (int64_t)0, dst);
+      field_launch(j0, m, 1, (int64_t)nk * 3 * pix, 0, dst);
       continue;
     }
     const int64_t block = (int64_t)m * 3 * pix;               // a plane's pixels of this block
-    hipLaunchKernelGGL(k_vecspec_field, dim3(tiles, f->planes * m * 3, S), dim3(kBlock), 0, s, a, d->s.dk, j0, m,
-                       (const double*)scratch, (const double*)amps, (int64_t)S * block, block, part);
+    field_launch(j0, m, S, (int64_t)S * block, block, part);
     for (int q = 0; q < f->planes; ++q)
       focal_fold_launch(part + (int64_t)q * S * block * 2, S, block, dst + (int64_t)q * nk * 3 * pix * 2, s);
   }
-  return launched("art_focal_vector_spectrum launch");
+  return launched(ch ? "art_focal_vector_chromatic launch" : "art_focal_vector_spectrum launch");
+}
+
+int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBundleView* b, const ArtCoating* coatings_dev,
+                              const ArtCoating* coatings_host, const ArtCoatingMaterial* materials_host, double* scratch,
+                              double* field, void* stream) {
+  if (const int e = vecspec_check(d)) return e;
+  return vecspec_run(d, nullptr, b, coatings_dev, coatings_host, materials_host, scratch, field, stream);
+}
+
+int64_t art_focal_vector_chromatic_scratch_doubles(const ArtFocalVectorChromaticDesc* d) {
+  if (!d) return fail(ART_ERR_BAD_ARG, "focal vector chromatic descriptor is NULL");
+  if (const int e = vecspec_check(&d->v)) return e;
+  return vecspec_plan(&d->v, kFocalChromRows).total;
+}
+
+int art_focal_vector_chromatic(const ArtFocalVectorChromaticDesc* d, const ArtBundleView* b, const ArtBundleView* src,
+                               const ArtCoating* coatings_dev, const ArtCoating* coatings_host,
+                               const ArtCoatingMaterial* materials_host, const double* table_dev,
+                               const double* table_host, double* scratch, double* field, void* stream) {
+  if (!d) return fail(ART_ERR_BAD_ARG, "focal vector chromatic descriptor is NULL");
+  if (const int e = vecspec_check(&d->v)) return e;
+  if (const int e = focal_chromatic_table_check(d->axis, d->v.s.nk, table_host)) return e;
+  const VecChromArg ch = {src, d->axis, table_dev};
+  return vecspec_run(&d->v, &ch, b, coatings_dev, coatings_host, materials_host, scratch, field, stream);
 }
 
 int64_t art_reduce_scratch_doubles(void) { return (int64_t)8 * kReadoutBlocks * kReadoutSlots + 64; }

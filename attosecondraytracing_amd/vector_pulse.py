@@ -83,9 +83,11 @@ def _setup(chain, Coatings, Detector, Polarisation):
     return coats, P, _pol.history(chain)
 
 
-def _vector_spectrum(bundles, coats, P, sd, wavelengths, scratch_bytes):
+def _vector_spectrum(bundles, coats, P, sd, wavelengths, scratch_bytes, chromatic=None):
     """art_focal_vector_spectrum for the history `bundles`, one Coating or None per element, the ArtFocalSpectrumDesc
-    sd and the wavelengths (mm) of its wavenumbers: device complex128 [planes, nk, 3, ny, nx]."""
+    sd and the wavelengths (mm) of its wavenumbers: device complex128 [planes, nk, 3, ny, nx].  chromatic = (axis,
+    table): art_focal_vector_chromatic with that unit axis and that table of sd.nk rows (k_j, c_j, z_j, 0) instead,
+    `wavelengths` those of the table's k_j."""
     last = bundles[-1]
     n = last.n_slots
     if scratch_bytes is None:
@@ -116,7 +118,12 @@ def _vector_spectrum(bundles, coats, P, sd, wavelengths, scratch_bytes):
     mats = np.stack([c.material_table(wavelengths) for c in coat_list], axis=1) if coat_list else \
         np.zeros((len(wavelengths), 0, _abi.ART_COATING_MAX_MATERIALS, 2))
     views = (_abi.ArtBundleView * (len(coats) + 1))(*[b.view() for b in bundles])
-    return last.backend.focal_vector_spectrum(d, views, structs, mats)
+    if chromatic is None:
+        return last.backend.focal_vector_spectrum(d, views, structs, mats)
+    vc = _abi.ArtFocalVectorChromaticDesc()
+    vc.v = d
+    vc.axis[:] = [float(a) for a in chromatic[0]]
+    return last.backend.focal_vector_chromatic(vc, views, structs, mats, chromatic[1])
 
 
 def _check_state(bundles, P):

@@ -602,6 +602,44 @@ int art_focal_vector_spectrum(const ArtFocalVectorSpectrumDesc* d, const ArtBund
                               const ArtCoating* coatings_host, const ArtCoatingMaterial* materials_host, double* scratch,
                               double* field, void* stream);
 
+/* Vector focal fields of a pulse from a CHROMATIC source behind dispersive coatings (added under ABI 14:
+ * ArtFocalVectorChromaticDesc, art_focal_vector_chromatic, art_focal_vector_chromatic_scratch_doubles):
+ * art_focal_vector_spectrum's sum with art_focal_chromatic's amplitude and phase per ray and wavenumber, for high
+ * harmonics sent through coated mirrors.  b is views[n_elems] and src is views[0] (the source bundle is the first view
+ * of the history), both as HOST structs; only src's directions s_r are read.  With the unit vector `axis` = a,
+ *     u_r  = 0.5 * (((s_x - a_x)^2 + (s_y - a_y)^2) + (s_z - a_z)^2)      (this order, no fma)
+ *     row j of the table = (k_j, c_j, z_j, 0)                             art_focal_chromatic's row, ANY list of k_j
+ *     a_r(k_j)        = (sqrt(w_r) * exp(-(u_r * c_j))) * E_r(k_j)        E_r: art_focal_vector_spectrum's field at k_j
+ *                                                                         with materials[j][c][.] (row j of the table
+ *                                                                         = row j of materials)
+ *     field[q][j][c]  = sum_r (a_r(k_j) . u_c) exp(i [k_j * (base_r / k + z_j * u_r) + shift, X and Y terms])
+ * base_r / k, the shift, X and Y terms and every rounding are art_focal_chromatic's; the frames, cos t, the Parratt
+ * recursion and the projection on u_c = e1, e2, n are art_focal_vector_spectrum's.  v.s.nk is the number of rows;
+ * v.s.f.k and v.s.dk are checked as there but NOT used: the table holds the k_j.
+ * A row with c_j = 0 and z_j = 0 multiplies by exp(-0) = 1 and adds +0.0: with k_j = v.s.f.k + j * v.s.dk formed as
+ * art_focal_spectrum forms them, the call gives art_focal_vector_spectrum's bytes.
+ * A dead slot of views[n_elems] contributes nothing, whatever any view holds there (NaN included).
+ * field (DEVICE, complex128, [planes][nk][3][ny][nx]) is written, not added to; n = 0 writes zeros.  Fixed summation
+ * order (no float atomics): the same bytes on every call with the same arguments.
+ * v.scratch_bound blocks the wavenumbers exactly as in art_focal_vector_spectrum, and the slicing of the rays depends
+ * neither on nk nor on the block: slice j of the field has the same bytes whichever other rows share the call, whatever
+ * their order and whatever the bound -- a comb of harmonics pays for its lines only.
+ * table_dev: DEVICE, 4 * nk doubles; table_host: the same values on the HOST, which the validation reads.
+ * scratch: DEVICE, art_focal_vector_chromatic_scratch_doubles(d) doubles (the negative error code on a bad descriptor).
+ * Limits: all of art_focal_vector_spectrum's, except that the k_j come from the table, and art_focal_chromatic's on the
+ * table and the axis: | |axis| - 1 | <= 1e-12, table_host non-NULL, every k_j finite and > 0, every c_j finite and
+ * >= 0, every z_j finite, table_dev and src's arrays non-NULL when n > 0: ART_ERR_BAD_ARG otherwise (ART_ERR_UNSUPPORTED
+ * for n > 2^28), with nothing launched and field untouched. */
+typedef struct ArtFocalVectorChromaticDesc {
+  ArtFocalVectorSpectrumDesc v;   /* everything of art_focal_vector_spectrum; v.s.nk = rows of the table              */
+  double axis[3];                 /* a: the unit axis of the source                                                    */
+} ArtFocalVectorChromaticDesc;
+int64_t art_focal_vector_chromatic_scratch_doubles(const ArtFocalVectorChromaticDesc* d);
+int art_focal_vector_chromatic(const ArtFocalVectorChromaticDesc* d, const ArtBundleView* b, const ArtBundleView* src,
+                               const ArtCoating* coatings_dev, const ArtCoating* coatings_host,
+                               const ArtCoatingMaterial* materials_host, const double* table_dev,
+                               const double* table_host, double* scratch, double* field, void* stream);
+
 /* Partially coherent focal image of an extended source (added under ABI 14: ArtFocalImageDesc, art_focal_image,
  * art_focal_image_scratch_doubles): the rays of one bundle in mutually incoherent groups of contiguous slots, summed
  * coherently inside a group and as intensities across groups,

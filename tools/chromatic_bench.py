@@ -10,7 +10,12 @@ z along the axis (z / distance to the first optic = --ratio, default 1e-3) again
 actually moved by z and traced again, as the relative L2 difference of the two fields (global phase removed) in three
 planes.
 
-    python tools/chromatic_bench.py [--reps 5] [--rounds 3] [--rays 1000000] [--retrace [--ratio 1e-3]]"""
+With --vector the script times art_focal_vector_chromatic against art_focal_vector_spectrum the same way (same history,
+grid and wavenumbers; 40-period Mo/Si of constant illustrative indices on relay4's four toroids; host tables included in
+both): once with a NEUTRAL table, which is the cost of the table variant itself, and once with every fourth row of it
+(a comb that keeps a quarter of the frequencies) over the full call.
+
+    python tools/chromatic_bench.py [--reps 5] [--rounds 3] [--rays 1000000] [--retrace [--ratio 1e-3]] [--vector]"""
 import argparse
 import math
 import os
@@ -94,6 +99,48 @@ def bench(args):
     print(f"  ratio chromatic / spectrum {mc / ms:.4f}", flush=True)
 
 
+def vector(args):
+    from attosecondraytracing_amd import _abi, polarisation, vector_pulse
+    from attosecondraytracing_amd.coating import Coating
+    chain, last, D = _scene(args.rays)
+    bundles = polarisation.history(chain)
+    n = last.n_slots
+    fd = _focal_desc(D, last, PIXELS)
+    k = fd.k
+    sd = _abi.ArtFocalSpectrumDesc()
+    sd.f = fd
+    sd.f.k, sd.dk, sd.nk = 0.9 * k, 0.2 * k / (NK - 1), NK
+    kj = sd.f.k + np.arange(NK) * sd.dk
+    si, mo = (0.0010, 0.0018), (0.0769, 0.0064)              # illustrative (delta, beta) at 13.5 nm
+    coat = Coating(si, [(si, 4.1e-6, 0.3e-6), (mo, 2.8e-6, 0.3e-6)] * 40, Roughness=0.3e-6)
+    coats = polarisation.resolve_coatings(list(chain.optical_elements), coat)
+    P = np.array([0.0, 1.0, 0.0], dtype=complex)
+    axis = _axis(chain.source_rays)
+    table = np.stack([kj, 0 * kj, 0 * kj, 0 * kj], axis=1)
+    quarter = table[::4]
+    sq = _abi.ArtFocalSpectrumDesc.from_buffer_copy(sd)
+    sq.nk = len(quarter)
+    spectrum = lambda: vector_pulse._vector_spectrum(bundles, coats, P, sd, 2 * np.pi / kj, None)
+    chromatic = lambda: vector_pulse._vector_spectrum(bundles, coats, P, sd, 2 * np.pi / kj, None, chromatic=(axis, table))
+    comb = lambda: vector_pulse._vector_spectrum(bundles, coats, P, sq, 2 * np.pi / quarter[:, 0], None,
+                                                 chromatic=(axis, quarter))
+    same = spectrum().cpu().numpy().tobytes() == chromatic().cpu().numpy().tobytes()
+    ts, tc, tq = [], [], []
+    for _ in range(args.rounds):
+        ts.append(_time(spectrum, args.reps))
+        tc.append(_time(chromatic, args.reps))
+        tq.append(_time(comb, args.reps))
+    ms, mc, mq = statistics.median(ts), statistics.median(tc), statistics.median(tq)
+    print(f"{args.rays:.0e} rays ({n} slots, {len(last)} alive) x {PIXELS}^2 x {NK} wavenumbers x 1 plane x 3 components, "
+          f"4 x 80 layers, {args.rounds} rounds of {args.reps} calls, alternating; neutral table = the spectrum's bytes: {same}",
+          flush=True)
+    print(f"  art_focal_vector_spectrum                {ms:9.3f} ms/call ({min(ts):.3f}-{max(ts):.3f})", flush=True)
+    print(f"  art_focal_vector_chromatic, {NK} rows      {mc:9.3f} ms/call ({min(tc):.3f}-{max(tc):.3f})", flush=True)
+    print(f"  art_focal_vector_chromatic, {len(quarter)} rows      {mq:9.3f} ms/call ({min(tq):.3f}-{max(tq):.3f})", flush=True)
+    print(f"  ratio chromatic / spectrum {mc / ms:.4f}; comb of {len(quarter)} / all {NK} rows {mq / mc:.4f} "
+          f"(kept fraction {len(quarter) / NK:.4f})", flush=True)
+
+
 def retrace(args):
     import ART.ModuleProcessing as mp
     from attosecondraytracing_amd import ModuleGeometry as mgeo
@@ -140,10 +187,11 @@ def main():
     ap.add_argument("--rays", type=int, default=10 ** 6)
     ap.add_argument("--retrace", action="store_true")
     ap.add_argument("--ratio", type=float, default=1e-3)
+    ap.add_argument("--vector", action="store_true")
     args = ap.parse_args()
     import __graft_entry__
     __graft_entry__.ensure_built()
-    (retrace if args.retrace else bench)(args)
+    (retrace if args.retrace else vector if args.vector else bench)(args)
 
 
 if __name__ == "__main__":
