@@ -325,11 +325,164 @@ class MirrorCylindrical(_Mirror):
         return -np.sqrt(self.radius ** 2 - y * y) + 0.0 * x
 
 
+class MirrorQuadric(_Mirror):
+    """General quadric mirror in its own POLE frame (no counterpart in the reference): the surface
+        F(P) = P^T Q P + 2 b.P + c = 0
+    with the origin on the surface (c = 0) and grad F(0) = 2b along -z; the reflecting sheet is the one with dF/dz < 0,
+    its normal n = -grad F / |grad F| is +z at the pole, so `OEPlacement`'s IncidenceAngle is the true incidence angle
+    there.  Q: symmetric 3x3 matrix.  The coefficients are rescaled to grad F(0) = (0, 0, -1).  Traced by
+    art_trace_quadric (include/art_hip.h), one element per launch; no defects, no gratings."""
+    _abi_kind = _abi.ART_PLANE            # by convention: art_trace_quadric ignores the kind
+
+    def __init__(self, Support, Q, b, c=0.0):
+        Q = np.asarray(Q, dtype=np.longdouble)
+        b = np.asarray(b, dtype=np.longdouble)
+        if Q.shape != (3, 3) or b.shape != (3,):
+            raise ValueError("MirrorQuadric: Q must be a 3x3 matrix and b a 3-vector")
+        if not (np.isfinite(Q).all() and np.isfinite(b).all() and np.isfinite(c)):
+            raise ValueError("MirrorQuadric: every coefficient must be finite")
+        if np.abs(Q - Q.T).max() > 1e-14 * max(float(np.abs(Q).max()), 1e-300):
+            raise ValueError("MirrorQuadric: Q must be symmetric")
+        if not b[2] < 0 or max(abs(b[0]), abs(b[1])) > 1e-14 * abs(b[2]):
+            raise ValueError("MirrorQuadric: grad F(0) = 2b must point along -z (the mirror's normal at its pole is +z)")
+        if abs(c) > 1e-14 * abs(b[2]):
+            raise ValueError("MirrorQuadric: the origin must lie on the surface (c = 0)")
+        k = -1 / (2 * b[2])
+        self._set(Support, [Q[0, 0] * k, Q[1, 1] * k, Q[2, 2] * k, Q[0, 1] * k, Q[0, 2] * k, Q[1, 2] * k, 0.0, 0.0, -0.5,
+                            np.longdouble(c) * k], "Quadric Mirror")
+
+    def _set(self, Support, coefficients, tname):
+        self.support = Support
+        self.type = tname
+        self._coeff = tuple(float(v) for v in coefficients)      # q[6] (xx yy zz xy xz yz), b[3], c: ArtQuadricDesc
+
+    def _abi_params(self):
+        return []
+
+    def _quadric_coefficients(self):
+        return self._coeff
+
+    def _content_hash(self):
+        return hash((self.type, hash(self.support)) + self._coeff)
+
+    def get_centre(self):
+        return np.array([0.0, 0.0, 0.0])
+
+    def _half_gradient(self, P):
+        q, x, y, z = self._coeff, P[0], P[1], P[2]
+        return np.array([q[0] * x + q[3] * y + q[4] * z + q[6], q[3] * x + q[1] * y + q[5] * z + q[7],
+                         q[4] * x + q[5] * y + q[2] * z + q[8]])
+
+    def get_normal(self, Point):
+        return mgeo.Normalize(-self._half_gradient(np.asarray(Point, dtype=float)))
+
+    def _sag(self, x, y):
+        """The root in z of F(x, y, z) = A z^2 + B z + C on the sheet with dF/dz = 2 A z + B < 0, i.e. the root
+        (-B - sqrt(D)) / (2A), in the form that does not cancel; NaN where there is none."""
+        q = self._coeff
+        x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+        A = q[2] + 0.0 * x
+        B = 2 * (q[4] * x + q[5] * y + q[8])
+        Cc = q[0] * x * x + q[1] * y * y + 2 * q[3] * x * y + 2 * (q[6] * x + q[7] * y) + q[9]
+        with np.errstate(all="ignore"):
+            D = B * B - 4 * A * Cc
+            s = np.sqrt(np.where(D > 0, D, np.nan))
+            w = -0.5 * (B + np.where(B < 0, -s, s))             # B < 0: (-B + s) / 2, B >= 0: (-B - s) / 2
+            z = np.where(B < 0, Cc / w, w / A)
+            return np.where(A == 0, np.where(B < 0, -Cc / B, np.nan), z)
+
+
+class MirrorConic(MirrorQuadric):
+    """Conic mirror between two conjugate points, in its pole frame: origin on the surface, z the normal there, x
+    tangential in the plane of incidence and pointing downstream, `GrazingAngle` (degrees, in (0, 90]) between the
+    central ray and the surface.  The signs of the two distances select the surface:
+        f_object, f_image > 0, finite      ellipse    (point to point)
+        one of them np.inf                 parabola   (collimated in, or collimating out)
+        one of them < 0                    hyperbola  (virtual object or virtual image)
+    With foci F1, F2 and s = f_object + f_image the surface is (g.P + h)^2 - 4 s^2 |P - F1|^2 = 0, g = -2 (F2 - F1),
+    h = |F2|^2 - |F1|^2 - s^2 (hyperbola: s = |f_object| - |f_image|); a real object sits at p (-cos t, 0, sin t), a real
+    image at q (cos t, 0, sin t), a virtual focus mirrored behind the surface; the parabola for a beam along
+    d = (cos t, 0, -+sin t) is |P|^2 - (d.P)^2 - 4 f sin t z = 0.  Cylindrical=True: y drops out of every squared distance
+    (a plane-elliptical, parabolic or hyperbolic cylinder with its generators along y).  The coefficients are formed in
+    np.longdouble, c = 0 exactly, scaled to grad F(0) = (0, 0, -1)."""
+
+    def __init__(self, Support, f_object, f_image, GrazingAngle, Cylindrical=False):
+        L = np.longdouble
+        p, q, deg = float(f_object), float(f_image), float(GrazingAngle)
+        if not (0 < deg <= 90):
+            raise ValueError("MirrorConic: GrazingAngle must lie in (0, 90] degrees")
+        if p == 0 or q == 0 or np.isnan(p) or np.isnan(q):
+            raise ValueError("MirrorConic: f_object and f_image must not be zero")
+        if np.isinf(p) and np.isinf(q):
+            raise ValueError("MirrorConic: f_object and f_image are both infinite: that is a MirrorPlane")
+        if (p < 0 and q < 0) or ((np.isinf(p) or np.isinf(q)) and min(p, q) < 0):
+            raise ValueError("MirrorConic: at most one of f_object, f_image may be negative, and then both are finite")
+        th = np.deg2rad(L(deg))
+        ct, st = (L(0), L(1)) if deg == 90 else (np.cos(th), np.sin(th))
+        I = np.diag([L(1), L(0) if Cylindrical else L(1), L(1)])
+        if np.isinf(p) or np.isinf(q):
+            d = np.array([ct, L(0), -st if np.isinf(p) else st])
+            f = L(q if np.isinf(p) else p)
+            k = 1 / (4 * f * st)
+            Q = (I - np.outer(d, d)) * k
+            kind = "Parabolic"
+        else:
+            if p < 0 or q < 0:
+                if abs(p) == abs(q):
+                    raise ValueError("MirrorConic: a hyperbola with |f_object| = |f_image| degenerates into a MirrorPlane")
+                s = L(abs(p)) - L(abs(q))
+                kind = "Hyperbolic"
+            else:
+                s = L(p) + L(q)
+                kind = "Elliptical"
+            F1 = L(abs(p)) * (np.array([-ct, L(0), st]) if p > 0 else np.array([ct, L(0), -st]))
+            F2 = L(abs(q)) * (np.array([ct, L(0), st]) if q > 0 else np.array([-ct, L(0), -st]))
+            g = -2 * (F2 - F1)
+            h = F2.dot(F2) - F1.dot(F1) - s * s
+            bz = h * g[2] + 4 * s * s * F1[2]               # b = h g + 4 s^2 F1; its x component vanishes analytically
+            k = -1 / (2 * bz)
+            Q = (np.outer(g, g) - 4 * s * s * I) * k
+        self._set(Support, [Q[0, 0], Q[1, 1], Q[2, 2], Q[0, 1], Q[0, 2], Q[1, 2], 0.0, 0.0, -0.5, 0.0],
+                  kind + (" Cylinder Mirror" if Cylindrical else " Conic Mirror"))
+        self.f_object, self.f_image, self.grazingangle, self.cylindrical = p, q, deg, bool(Cylindrical)
+
+
+def MirrorEllipticalCylinder(Support, f_object, f_image, GrazingAngle):
+    """Plane-elliptical cylinder (one mirror of a Kirkpatrick-Baez pair): focuses in its plane of incidence only."""
+    if not (0 < f_object < np.inf and 0 < f_image < np.inf):
+        raise ValueError("MirrorEllipticalCylinder: f_object and f_image must be positive and finite")
+    return MirrorConic(Support, f_object, f_image, GrazingAngle, Cylindrical=True)
+
+
+def MirrorParabolicCylinder(Support, Focal, GrazingAngle, Collimating=False):
+    """Parabolic cylinder: focuses a collimated beam onto a line at `Focal` (Collimating=True: the reverse)."""
+    if not 0 < Focal < np.inf:
+        raise ValueError("MirrorParabolicCylinder: Focal must be positive and finite")
+    return MirrorConic(Support, Focal if Collimating else np.inf, np.inf if Collimating else Focal, GrazingAngle, Cylindrical=True)
+
+
+def _hyperbolic(Support, f_object, f_image, GrazingAngle, Cylindrical, name):
+    if not (np.isfinite(f_object) and np.isfinite(f_image) and min(f_object, f_image) < 0):
+        raise ValueError(name + ": one of f_object, f_image must be negative (a virtual focus), both finite")
+    return MirrorConic(Support, f_object, f_image, GrazingAngle, Cylindrical=Cylindrical)
+
+
+def MirrorHyperboloidal(Support, f_object, f_image, GrazingAngle):
+    """Hyperboloid of revolution between a real and a virtual focus (the secondary of a Wolter or Cassegrain pair)."""
+    return _hyperbolic(Support, f_object, f_image, GrazingAngle, False, "MirrorHyperboloidal")
+
+
+def MirrorHyperbolicCylinder(Support, f_object, f_image, GrazingAngle):
+    return _hyperbolic(Support, f_object, f_image, GrazingAngle, True, "MirrorHyperbolicCylinder")
+
+
 class DeformedMirror(_Mirror):
     """A mirror with surface defects (ART/ModuleMirror.py:945-980).  The defect offset always shifts the hit
     point; the perturbed normal is used only when tracing with IgnoreDefects=False (reference default: True)."""
 
     def __init__(self, Mirror, DeformationList):
+        if hasattr(Mirror, "_quadric_coefficients"):
+            raise ValueError("DeformedMirror: defects on a MirrorQuadric / MirrorConic are not supported")
         self.Mirror = Mirror
         self.DeformationList = list(DeformationList)
         self.type = Mirror.type
@@ -410,6 +563,8 @@ class Grating(_Mirror):
     def __init__(self, Mirror, LinesPerMm, Order=1, GrooveAngle=0.0):
         if isinstance(Mirror, (DeformedMirror, Grating)) or hasattr(Mirror, "DeformationList"):
             raise ValueError("Grating: mirrors with defects (DeformedMirror) or gratings are not supported as substrates")
+        if hasattr(Mirror, "_quadric_coefficients"):
+            raise ValueError("Grating: a MirrorQuadric / MirrorConic is not supported as a substrate")
         tname = getattr(Mirror, "type", None)
         if not (isinstance(tname, str) and "Mirror" in tname) or getattr(Mirror, "_abi_kind", None) is None:
             raise ValueError("Grating: the substrate must be one of the mirror classes (a Mask cannot carry a grating)")

@@ -85,6 +85,11 @@ def _build_descriptor(oe, IgnoreDefects, backend):
         # ModuleMirror.Grating: traced by art_trace_grating only, one element per launch (like the recurrence layout)
         d.flags |= _abi.ART_FLAG_GRATING
         d.grating = optic
+    d.quadric = None
+    if hasattr(optic, "_quadric_coefficients"):
+        # ModuleMirror.MirrorQuadric and its kin: traced by art_trace_quadric only, one element per launch
+        d.flags |= _abi.ART_FLAG_QUADRIC
+        d.quadric = optic
     if hasattr(optic, "DeformationList") and len(optic.DeformationList) > 0:
         be = backend or _lib.get_backend()
         keep = []
@@ -133,13 +138,16 @@ def _as_bundle(rays, backend=None):
 
 _CHAIN_MAX = 8          # elements per fused launch (kChainMax in csrc/art_scene.h)
 # elements the fused launches, the scene table and the guide kernel refuse: traced element by element, a launch each
-_STEPWISE_FLAGS = _abi.ART_FLAG_ZERN_RECURRENCE | _abi.ART_FLAG_GRATING
+_STEPWISE_FLAGS = _abi.ART_FLAG_ZERN_RECURRENCE | _abi.ART_FLAG_GRATING | _abi.ART_FLAG_QUADRIC
 
 
 def _trace_one(be, desc, vin, vout, n, wavelength, grooves):
-    """One element, one launch: art_trace_element, or art_trace_grating for a ModuleMirror.Grating at the bundle's
-    wavelength.  `grooves`: the groove counts the rays arrive with (device tensor [n] or None); returns those they leave
-    with -- the same object unless the element is a grating."""
+    """One element, one launch: art_trace_element, art_trace_quadric for a ModuleMirror.MirrorQuadric, or
+    art_trace_grating for a ModuleMirror.Grating at the bundle's wavelength.  `grooves`: the groove counts the rays arrive
+    with (device tensor [n] or None); returns those they leave with -- the same object unless the element is a grating."""
+    if desc.flags & _abi.ART_FLAG_QUADRIC:
+        be.trace_quadric(desc, desc.quadric._quadric_coefficients(), vin, vout, n)
+        return grooves
     if not desc.flags & _abi.ART_FLAG_GRATING:
         be.trace_element(desc, vin, vout, n)
         return grooves
@@ -203,8 +211,8 @@ def RayTracingCalculation(source_rays, optical_elements, IgnoreDefects=True, mod
         keep.append(k)
     mode = mode or DEFAULT_TRACE_MODE
     if any(d.flags & _STEPWISE_FLAGS for d in descs):
-        # Zernike orders above 16 run the recurrences per ray, a grating fans out in wavelength: kernels of their own, one
-        # element per launch
+        # Zernike orders above 16 run the recurrences per ray, a grating fans out in wavelength, a general quadric has its
+        # own intersection: kernels of their own, one element per launch
         mode = "element"
     bad = next((k for k, d in enumerate(descs) if d.nonfinite), None)
     if bad is not None:

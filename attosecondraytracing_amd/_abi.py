@@ -17,6 +17,7 @@ ART_SUP_ROUND, ART_SUP_ROUNDHOLE, ART_SUP_RECT, ART_SUP_RECTHOLE, ART_SUP_RECTRE
 ART_FLAG_PERTURBED_NORMAL = 1
 ART_FLAG_ZERN_RECURRENCE = 2
 ART_FLAG_GRATING = 4
+ART_FLAG_QUADRIC = 8
 ART_ZERN_RECURRENCE_MAX_ORDER = 64
 
 ART_ZERN_MAX_ORDER = 16
@@ -76,6 +77,10 @@ class ArtGratingDesc(C.Structure):
         ("grooves_in", C.c_void_p),
         ("grooves_out", C.c_void_p),
     ]
+
+
+class ArtQuadricDesc(C.Structure):
+    _fields_ = [("q", C.c_double * 6), ("b", C.c_double * 3), ("c", C.c_double)]
 
 
 class ArtDetectorDesc(C.Structure):
@@ -291,6 +296,8 @@ PROTOTYPES = {
                                     C.c_int64, C.c_void_p]),
     "art_trace_grating": (C.c_int, [C.POINTER(ArtElementDesc), C.POINTER(ArtGratingDesc), c_double_p,
                                     C.POINTER(ArtBundleView), C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
+    "art_trace_quadric": (C.c_int, [C.POINTER(ArtElementDesc), C.POINTER(ArtQuadricDesc), C.POINTER(ArtBundleView),
+                                    C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
     "art_trace_chain": (C.c_int, [C.POINTER(ArtElementDesc), C.c_int32, C.POINTER(ArtBundleView),
                                   C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
     "art_scene_bytes": (C.c_int64, [C.c_int32, C.c_int32]),

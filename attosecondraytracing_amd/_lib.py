@@ -146,6 +146,16 @@ class HipBackend:
                                                                     C.byref(view_in), n, sp)), "art_trace_grating")
         return wl_dev, v_dev          # (read by the launch: the caller keeps them alive with the outputs)
 
+    def trace_quadric(self, desc, coefficients, view_in, view_out, n):
+        """art_trace_quadric: `desc` (an ArtElementDesc with ART_FLAG_QUADRIC) reflects the bundle `view_in` off the quadric
+        whose ten coefficients (q[6], b[3], c: include/art_hip.h) are `coefficients`."""
+        q = _abi.ArtQuadricDesc()
+        co = [float(v) for v in coefficients]
+        q.q[:], q.b[:], q.c = co[0:6], co[6:9], co[9]
+        sp = self.stream_ptr()
+        self.check(self._timed(lambda: self.fn["art_trace_quadric"](C.byref(desc), C.byref(q), C.byref(view_in),
+                                                                    C.byref(view_out), n, sp)), "art_trace_quadric")
+
     def trace_chain(self, descs, view_in, views_out, n, readout=None):
         """art_trace_chain, or art_trace_chain_readout when `readout` (from new_chain_readout) is given."""
         m = len(descs)

@@ -992,6 +992,67 @@ ART_HD bool grating_ray(const ArtElementDesc& e, double qx, double qy, double N,
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// General quadric mirror (ART_FLAG_QUADRIC, art_trace_quadric; the reference has no counterpart): the surface
+//     F(P) = P^T Q P + 2 b.P + c = 0,   Q symmetric = [q0 q3 q4; q3 q1 q5; q4 q5 q2]   (ArtQuadricDesc: xx yy zz xy xz yz)
+// in the optic frame.  The host classes (ModuleMirror.MirrorConic and its kin) write it in the mirror's POLE frame: the
+// origin lies on the surface (c = 0 exactly) and grad F(0) = 2b = (0, 0, -1), so that qc = F(A) is a sum of terms of the
+// size of the ray's distance to the pole instead of the difference of two squared distances to a conic centre metres
+// away -- at grazing incidence that difference loses what the stable root below would keep.
+// Along the ray P = A + t u:  F = qa t^2 + qb t + qc  with  qa = u^T Q u, qb = 2 u.(Q A + b), qc = A.(Q A + 2b) + c, and
+// half the gradient  h(t) = Q P + b = (Q A + b) + t Q u  is linear in t: one FMA per component and candidate.
+// A root counts when t > 1e-12, dF/dz < 0 there (the sheet that faces +z: the analogue of z < 0 on the sphere; it rejects
+// the far sheet of a hyperboloid and the far side of a closed ellipse) and the support contains (x - cx, y - cy); one
+// candidate -> it, two -> the closer (the later one on a tie), as `consider` rules.  Normal n = -grad F / |grad F|.
+// What trace_ray does for a mirror without defects, otherwise step by step the same.  `e` is a PREPARED descriptor whose
+// kind is ignored.  A lost ray leaves r untouched.
+ART_HD bool quadric_trace(const ArtElementDesc& e, const ArtQuadricDesc& Q, Ray& r) {
+  double Ax, Ay, Az, ux, uy, uz;
+  mat3_apply_off(e.fwd, e.ART_D_IN_OFF, r.ox, r.oy, r.oz, Ax, Ay, Az);
+  mat3_apply(e.fwd, r.dx, r.dy, r.dz, ux, uy, uz);
+  // Q u and Q A + b
+  const double wx = fma(Q.q[0], ux, fma(Q.q[3], uy, Q.q[4] * uz));
+  const double wy = fma(Q.q[3], ux, fma(Q.q[1], uy, Q.q[5] * uz));
+  const double wz = fma(Q.q[4], ux, fma(Q.q[5], uy, Q.q[2] * uz));
+  const double hx = fma(Q.q[0], Ax, fma(Q.q[3], Ay, Q.q[4] * Az)) + Q.b[0];
+  const double hy = fma(Q.q[3], Ax, fma(Q.q[1], Ay, Q.q[5] * Az)) + Q.b[1];
+  const double hz = fma(Q.q[4], Ax, fma(Q.q[5], Ay, Q.q[2] * Az)) + Q.b[2];
+  const double qa = dot3(ux, uy, uz, wx, wy, wz);
+  const double qb = 2.0 * dot3(ux, uy, uz, hx, hy, hz);
+  const double qc = dot3(Ax, Ay, Az, hx + Q.b[0], hy + Q.b[1], hz + Q.b[2]) + Q.c;
+  double t1 = 0.0, t2 = 0.0;
+  const int nr = quadratic_roots(qa, qb, qc, t1, t2);
+  int cnt = 0;
+  double t = 0.0;
+  for (int k = 0; k < 2; ++k) {
+    const double tk = k ? t2 : t1;
+    const double x = fma(tk, ux, Ax), y = fma(tk, uy, Ay);
+    const bool ok = (nr > k) && (tk > 1e-12) && (fma(tk, wz, hz) < 0.0) &&
+                    include_support(e.support_kind, e.sp, x - e.centre[0], y - e.centre[1]);
+    const bool take = ok && (cnt == 0 || !(t < tk));
+    t = take ? tk : t;
+    cnt += ok ? 1 : 0;
+  }
+  if (cnt == 0) return false;
+  const double Px = fma(t, ux, Ax), Py = fma(t, uy, Ay), Pz = fma(t, uz, Az);
+  const double gx = fma(t, wx, hx), gy = fma(t, wy, hy), gz = fma(t, wz, hz);
+  const double ig = -rsqrt_full(dot3(gx, gy, gz, gx, gy, gz));
+  const double nx = gx * ig, ny = gy * ig, nz = gz * ig;
+  // reflection, incidence angle, way back and renormalisation: trace_ray's
+  const double dn = dot3(ux, uy, uz, nx, ny, nz);
+  const double vx = fma(-2.0 * dn, nx, ux), vy = fma(-2.0 * dn, ny, uy), vz = fma(-2.0 * dn, nz, uz);
+  const double inc = kahan_angle_unit(-ux, -uy, -uz, nx, ny, nz, -dn);
+  double dx, dy, dz;
+  mat3t_apply_off(e.fwd, e.ART_D_OUT_OFF, Px, Py, Pz, r.ox, r.oy, r.oz);
+  mat3t_apply(e.fwd, vx, vy, vz, dx, dy, dz);
+  const double s2 = dot3(dx, dy, dz, dx, dy, dz);
+  const double kk = fma(-0.5, s2, 1.5);
+  r.dx = dx * kk; r.dy = dy * kk; r.dz = dz * kk;
+  r.path += t;
+  r.inc = inc;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Detector read-out for one ray (ART/ModuleDetector.py:191-234, :272-275; ModuleGeometry.py:48-57)
 ART_HD void detector_ray(const ArtDetectorDesc& d, const Ray& r, double& Ix, double& Iy, double& Iz, double& X,
                          double& Y, double& opl) {

@@ -715,6 +715,23 @@ __global__ __launch_bounds__(kBlock) void k_trace_grating(const ElemArg ea, cons
   }
 }
 
+// General quadric mirror (ART_FLAG_QUADRIC, art_device.h quadric_trace): one ray per thread, no loop, no LDS, no
+// barrier.  The ten coefficients arrive in the kernel arguments: wave-uniform, i.e. scalar registers, and every product
+// with them takes one as its scalar operand.
+__global__ __launch_bounds__(kBlock) void k_trace_quadric(const ElemArg ea, const ArtQuadricDesc q, const ArtBundleView in,
+                                                          const ArtBundleView out, const int64_t n) {
+  const ArtElementDesc& e = ea.e[blockIdx.y];
+  const BundleRsrc bi = make_rsrc(in, n), bo = make_rsrc(out, n);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  art::Ray r;
+  r.inc = 0.0;
+  uint8_t a;
+  load_slot(bi, i, r, a);
+  bool ok = a != 0;
+  if (ok) ok = art::quadric_trace(e, q, r);
+  store_slot(bo, i, r, ok);
+}
+
 using art::ChainArgs;
 using art::kChainMax;
 
@@ -3332,6 +3349,7 @@ int check_elem(const ArtElementDesc* e) {
 }
 
 const char* const kGratingRefusal = "an element is a grating: trace it with art_trace_grating";
+const char* const kQuadricRefusal = "an element is a general quadric: trace it with art_trace_quadric";
 
 template <int KIND>
 void launch_element(const ArtElementDesc& e, const ArtBundleView& in, const ArtBundleView& out, int64_t n,
@@ -3551,6 +3569,7 @@ int art_trace_element(const ArtElementDesc* e, const ArtBundleView* in, const Ar
   int rc = check_elem(e);
   if (rc) return rc;
   if (e->flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
+  if (e->flags & ART_FLAG_QUADRIC) return fail(ART_ERR_UNSUPPORTED, kQuadricRefusal);
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   if (n == 0) return ART_OK;  // an empty bundle has no arrays to point to
   if (!view_ok(in) || !view_ok(out)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
@@ -3583,6 +3602,7 @@ int art_trace_grating(const ArtElementDesc* e, const ArtGratingDesc* g, const do
                       const ArtBundleView* outs_host, const ArtBundleView* in, int64_t n, void* stream) {
   int rc = check_elem(e);
   if (rc) return rc;
+  if (e->flags & ART_FLAG_QUADRIC) return fail(ART_ERR_UNSUPPORTED, kQuadricRefusal);
   if (e->kind == ART_MASK) return fail(ART_ERR_BAD_ARG, "art_trace_grating: a mask cannot be a grating");
   if (e->n_defects > 0 || e->n_grid > 0) return fail(ART_ERR_BAD_ARG, "art_trace_grating: mirrors with defects are not supported as substrates");
   if (!g || !wavelengths_host || !outs_host) return fail(ART_ERR_BAD_ARG, "art_trace_grating: NULL argument");
@@ -3608,6 +3628,31 @@ int art_trace_grating(const ArtElementDesc* e, const ArtGratingDesc* g, const do
   return launched("art_trace_grating launch");
 }
 
+int art_trace_quadric(const ArtElementDesc* e, const ArtQuadricDesc* q, const ArtBundleView* in, const ArtBundleView* out,
+                      int64_t n, void* stream) {
+  int rc = check_elem(e);
+  if (rc) return rc;
+  if (!q || !in || !out) return fail(ART_ERR_BAD_ARG, "art_trace_quadric: NULL argument");
+  if (e->n_defects > 0 || e->n_grid > 0) return fail(ART_ERR_BAD_ARG, "art_trace_quadric: mirrors with defects are not supported");
+  bool finite = isfinite(q->c), any = false;
+  for (int k = 0; k < 6; ++k) { finite = finite && isfinite(q->q[k]); any = any || q->q[k] != 0.0; }
+  for (int k = 0; k < 3; ++k) { finite = finite && isfinite(q->b[k]); any = any || q->b[k] != 0.0; }
+  if (!finite) return fail(ART_ERR_BAD_ARG, "art_trace_quadric: every coefficient must be finite");
+  if (!any) return fail(ART_ERR_BAD_ARG, "art_trace_quadric: q and b are all zero: no surface");
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (n == 0) return ART_OK;  // an empty bundle has no arrays to point to
+  if (!view_ok(in) || !view_ok(out)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
+  ElemArg ea;
+  ea.e[0] = *e;
+  art::prepare_element(ea.e[0]);
+  per_launch(n, [&](const int64_t off, const int64_t m) {
+    hipLaunchKernelGGL(k_trace_quadric, dim3(grid_stream(m)), dim3(kBlock), 0, (hipStream_t)stream, ea, *q, view_at(*in, off),
+                       view_at(*out, off), m);
+    return ART_OK;
+  });
+  return launched("art_trace_quadric launch");
+}
+
 static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const ArtBundleView* in,
                             const ArtBundleView* outs, const ArtChainReadout* ro, int64_t n, void* stream) {
   if (!elems || !outs || n_elems <= 0) return fail(ART_ERR_BAD_ARG, "empty chain");
@@ -3618,6 +3663,7 @@ static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const 
     if (elems[k].flags & ART_FLAG_ZERN_RECURRENCE)
       return fail(ART_ERR_UNSUPPORTED, "an element carries Zernike tables in the recurrence layout: trace it with art_trace_element");
     if (elems[k].flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
+    if (elems[k].flags & ART_FLAG_QUADRIC) return fail(ART_ERR_UNSUPPORTED, kQuadricRefusal);
   }
   hipStream_t s = (hipStream_t)stream;
   if (ro) {
@@ -4709,6 +4755,7 @@ int art_trace_guides(const ArtElementDesc* elems, int32_t count, double* rays, u
     if (elems[k].flags & ART_FLAG_ZERN_RECURRENCE)
       return fail(ART_ERR_UNSUPPORTED, "an element carries Zernike tables in the recurrence layout: trace it with art_trace_element");
     if (elems[k].flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
+    if (elems[k].flags & ART_FLAG_QUADRIC) return fail(ART_ERR_UNSUPPORTED, kQuadricRefusal);
     ga.e[k] = elems[k];
     art::prepare_element(ga.e[k]);
     defects = defects || ga.e[k].n_defects > 0 || ga.e[k].n_grid > 0;

@@ -59,6 +59,7 @@ enum ArtSupportKind {
 #define ART_FLAG_PERTURBED_NORMAL 1u /* IgnoreDefects=False: reflect off the defect-perturbed normal (ModuleMirror.py:933-936) */
 #define ART_FLAG_ZERN_RECURRENCE 2u  /* the element's Zernike tables are in the RECURRENCE layout (any order, below)      */
 #define ART_FLAG_GRATING 4u          /* this element is a grating: only art_trace_grating traces it                        */
+#define ART_FLAG_QUADRIC 8u          /* this element is a general quadric mirror: only art_trace_quadric traces it         */
 
 /* Zernike defect table (ART/ModuleDefects.py:149-174), a DEVICE array of doubles per element.  The polynomials
  * of ART/recursive_zernike_generator.py have integer monomial coefficients; the host expands
@@ -188,6 +189,32 @@ typedef struct ArtGratingDesc {
 } ArtGratingDesc;
 int art_trace_grating(const ArtElementDesc* e, const ArtGratingDesc* g, const double* wavelengths_host,
                       const ArtBundleView* outs_host, const ArtBundleView* in, int64_t n, void* stream);
+
+/* General quadric mirror (added under ABI 14: ART_FLAG_QUADRIC, ArtQuadricDesc, art_trace_quadric): the conics the six
+ * kinds above lack -- plane-elliptical, parabolic and hyperbolic cylinders (Kirkpatrick-Baez pairs), hyperboloids
+ * (Wolter pairs, Cassegrain secondaries) -- and any other surface of second degree.  In the optic frame
+ *     F(P) = q[0] x^2 + q[1] y^2 + q[2] z^2 + 2 q[3] xy + 2 q[4] xz + 2 q[5] yz + 2 b.P + c = 0 .
+ * Per ray, with P = A + t u: the roots of (u^T Q u) t^2 + 2 u.(Q A + b) t + F(A) by the cancellation-free quadratic of
+ * the other kinds (a vanishing leading coefficient -- a ray parallel to a parabola's axis -- gives the one root -c/b).
+ * A root counts when t > 1e-12, dF/dz < 0 at the hit (the sheet that faces +z) and the support contains
+ * (x - centre[0], y - centre[1]); one candidate: it; two: the closer, the later one on a tie; none: the ray is lost.
+ * Normal n = -grad F / |grad F|, reflection v = u - 2 (u.n) n, path += t, incidence as for every mirror.  No defects.
+ * Write the surface in the mirror's own pole frame -- origin on the surface (c = 0), grad F(0) = 2 b = (0, 0, -1) -- as
+ * ModuleMirror.MirrorConic does: F(A) then does not cancel, and |grad F| is of order 1, which the kernel's reciprocal
+ * square root assumes (ordinary magnitudes: no scaling against overflow or denormals).
+ * e->kind is ART_PLANE by convention and ignored; e->mp is unused.  Reads `in`, writes `out` (may alias `in`); slots
+ * dead on input and rays that miss get alive = 0 and their other outputs are left untouched.  Any n >= 0 (chunked like
+ * art_trace_element).  ART_ERR_BAD_ARG: NULL pointers, an invalid element (art_trace_element's rules), defects on the
+ * element, a non-finite coefficient, q and b all zero, n < 0, an incomplete view with n > 0.
+ * art_trace_element, art_trace_grating, art_trace_chain(_readout), art_scene_pack and art_trace_guides return
+ * ART_ERR_UNSUPPORTED for an element with ART_FLAG_QUADRIC set.                                                       */
+typedef struct ArtQuadricDesc {
+  double q[6];                  /* xx, yy, zz, xy, xz, yz (the off-diagonal entries of the symmetric matrix, not doubled) */
+  double b[3];
+  double c;
+} ArtQuadricDesc;
+int art_trace_quadric(const ArtElementDesc* e, const ArtQuadricDesc* q, const ArtBundleView* in,
+                      const ArtBundleView* out, int64_t n, void* stream);
 
 /* Whole chain in ONE launch: the ray stays in registers from element to element.  outs[k] receives the
  * bundle after element k for every k with outs[k].alive != NULL (pass zeroed views to skip history);
