@@ -476,6 +476,123 @@ def MirrorHyperbolicCylinder(Support, f_object, f_image, GrazingAngle):
     return _hyperbolic(Support, f_object, f_image, GrazingAngle, True, "MirrorHyperbolicCylinder")
 
 
+class MirrorFreeform(_Mirror):
+    """Freeform mirror (no counterpart in the reference): a quadric base in its pole frame plus a polynomial height figure,
+        z = sag_base(x, y) + h(x, y),   implicitly  Phi(P) = F(x, y, z - h(x, y)) = 0 ,
+    with h in mm and h > 0 a bump towards the incoming light.  Base: a MirrorQuadric or anything built on it (MirrorConic,
+    MirrorEllipticalCylinder, ...).  Figure: a list of ModuleDefects.Zernike (order <= 16) and / or
+    ModuleDefects.Polynomial; they are summed here into ONE polynomial of total degree <= 16 with one normalisation radius.
+    Terms with different radii cannot be merged exactly and are refused (a constant term has no radius and merges with
+    anything).  The rays are intersected with Phi exactly, by Newton's iteration on the device (art_trace_freeform,
+    include/art_hip.h): nanometres of figure error and millimetres of aspheric departure are the same code."""
+    _abi_kind = _abi.ART_PLANE            # by convention: art_trace_freeform ignores the kind
+
+    def __init__(self, Base, Figure):
+        from . import ModuleDefects as mdef
+        if not isinstance(Base, MirrorQuadric):
+            raise TypeError("MirrorFreeform: Base must be a MirrorQuadric or one of the mirrors built on it (MirrorConic, ...)")
+        if isinstance(Figure, (mdef.Defect, dict)) or not hasattr(Figure, "__iter__"):
+            raise TypeError("MirrorFreeform: Figure must be a list of ModuleDefects.Zernike and / or ModuleDefects.Polynomial")
+        Dm = _abi.ART_ZERN_DIM
+        A, R, N = np.zeros((Dm, Dm)), None, 0
+        for term in Figure:
+            if isinstance(term, mdef.Polynomial):
+                M, order = term._matrix(), term.max_order
+            elif isinstance(term, mdef.Zernike):
+                if term.max_order > _abi.ART_ZERN_MAX_ORDER:
+                    raise ValueError(f"MirrorFreeform: a Zernike figure of order {term.max_order} exceeds the maximum "
+                                     f"{_abi.ART_ZERN_MAX_ORDER} of a freeform's figure")
+                order = max(2, term.max_order)            # the generator's lowest table (ModuleDefects.zernike_table)
+                M = np.zeros((Dm, Dm))
+                Zm = mdef.zernike_monomials(order)
+                for key, c in term.coefficients.items():
+                    Z = Zm[key][:Dm, :Dm]
+                    M[:Z.shape[0], :Z.shape[1]] += c * Z
+            else:
+                raise ValueError(f"MirrorFreeform: a figure term of type {type(term).__name__} is not supported (gridded "
+                                 "Fourrier maps and measured maps are not polynomials): use Zernike or Polynomial")
+            flat = M.copy()
+            flat[0, 0] = 0.0
+            if flat.any():                                  # only a constant is free of the radius
+                if R is not None and float(term.R) != R:
+                    raise ValueError(f"MirrorFreeform: figure terms with the normalisation radii {R:g} and {float(term.R):g} "
+                                     "cannot be merged exactly: give them one Radius")
+                R = float(term.R)
+            A += M
+            N = max(N, order)
+        if not np.isfinite(A).all():
+            raise ValueError("MirrorFreeform: every figure coefficient must be finite")
+        self.Base = Base
+        self.support = Base.support
+        self.type = "Freeform Mirror"
+        self._fig_A, self._fig_R, self._fig_N = A, float(Base.support._CircumCirc()) if R is None else R, int(N)
+
+    def _abi_params(self):
+        return []
+
+    def _base_coefficients(self):
+        return self.Base._quadric_coefficients()
+
+    def _freeform_figure(self):
+        """(table in the dense layout of include/art_hip.h, radius, order)."""
+        from .ModuleDefects import dense_table
+        return dense_table(self._fig_R, self._fig_N, self._fig_A), self._fig_R, self._fig_N
+
+    def _content_hash(self):
+        return hash((self.type, hash(self.Base), self._fig_R, self._fig_N, self._fig_A.tobytes()))
+
+    def get_centre(self):
+        return np.array([0.0, 0.0, 0.0])
+
+    def _figure(self, x, y, derivatives=False):
+        """h (and its two slopes) at pole-frame points, in the float type of x."""
+        from .ModuleDefects import dense_eval
+        return dense_eval(self._fig_R, self._fig_A, x, y, derivatives)
+
+    def get_normal(self, Point):
+        """The true normal -grad Phi / |grad Phi| at ONE point of the surface: grad Phi = (F_x - F_z h_x, F_y - F_z h_y,
+        F_z) with the base's gradient taken at (x, y, z - h)."""
+        P = np.asarray(Point, dtype=float)
+        h, hx, hy = self._figure(P[0], P[1], derivatives=True)
+        g = self.Base._half_gradient(np.array([P[0], P[1], P[2] - float(h)]))
+        return mgeo.Normalize(-np.array([g[0] - g[2] * float(hx), g[1] - g[2] * float(hy), g[2]]))
+
+    def _sag(self, x, y):
+        """Base + figure: the surface the rays meet (the render shows the figure, unlike DeformedMirror's)."""
+        x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
+        return self.Base._sag(x, y) + self._figure(x, y)
+
+
+def MirrorEvenAsphere(Support, Radius, Conic=0.0, Coefficients=()):
+    """The standard even asphere in its vertex frame, reflecting side towards +z,
+        z = c r^2 / (1 + sqrt(1 - (1 + k) c^2 r^2)) + sum_i alpha_i r^(2 i + 2),   i = 1, 2, ...   (c = 1 / Radius),
+    Radius > 0 concave (np.inf: a plane base), Conic = k, Coefficients = (alpha_1, alpha_2, ...) in mm^-(2i+1), at most seven
+    (r^16).  A MirrorFreeform whose base is the conicoid x^2 + y^2 + (1 + k) z^2 - 2 R z = 0 and whose figure is the alpha
+    polynomial, normalised to a power of two >= the support's circumscribed radius (scaling by it is exact)."""
+    from .ModuleDefects import Polynomial
+    R, k = float(Radius), float(Conic)
+    alphas = [float(a) for a in Coefficients]
+    if R == 0 or np.isnan(R) or not np.isfinite(k):
+        raise ValueError("MirrorEvenAsphere: Radius must not be zero and Conic must be finite")
+    if 2 * len(alphas) + 2 > _abi.ART_ZERN_MAX_ORDER:
+        raise ValueError("MirrorEvenAsphere: at most seven coefficients (r^4 ... r^16)")
+    L = np.longdouble
+    s = L(1) if R > 0 else L(-1)
+    c2 = L(0) if np.isinf(R) else s / (2 * abs(L(R)))         # F = s (x^2 + y^2 + (1 + k) z^2) / (2 |R|) - z
+    Q = np.diag([c2, c2, (1 + L(k)) * c2])
+    base = MirrorQuadric(Support, Q, [0.0, 0.0, -0.5])
+    Rn = 2.0 ** math.ceil(math.log2(float(Support._CircumCirc())))
+    co = {}
+    for i, a in enumerate(alphas, start=1):
+        m = i + 1                                                   # alpha_i r^(2m) = alpha_i sum_j C(m, j) x^(2j) y^(2(m-j))
+        for j in range(m + 1):
+            co[(2 * j, 2 * (m - j))] = float(L(a) * math.comb(m, j) * L(Rn) ** (2 * m))
+    M = MirrorFreeform(base, [Polynomial(Support, co, Radius=Rn)])
+    M.type = "Even Asphere Mirror"
+    M.radius, M.conic, M.alphas = R, k, tuple(alphas)
+    return M
+
+
 class DeformedMirror(_Mirror):
     """A mirror with surface defects (ART/ModuleMirror.py:945-980).  The defect offset always shifts the hit
     point; the perturbed normal is used only when tracing with IgnoreDefects=False (reference default: True)."""
@@ -483,6 +600,8 @@ class DeformedMirror(_Mirror):
     def __init__(self, Mirror, DeformationList):
         if hasattr(Mirror, "_quadric_coefficients"):
             raise ValueError("DeformedMirror: defects on a MirrorQuadric / MirrorConic are not supported")
+        if hasattr(Mirror, "_freeform_figure"):
+            raise ValueError("DeformedMirror: defects on a MirrorFreeform are not supported: put them into its Figure")
         self.Mirror = Mirror
         self.DeformationList = list(DeformationList)
         self.type = Mirror.type
@@ -563,8 +682,8 @@ class Grating(_Mirror):
     def __init__(self, Mirror, LinesPerMm, Order=1, GrooveAngle=0.0):
         if isinstance(Mirror, (DeformedMirror, Grating)) or hasattr(Mirror, "DeformationList"):
             raise ValueError("Grating: mirrors with defects (DeformedMirror) or gratings are not supported as substrates")
-        if hasattr(Mirror, "_quadric_coefficients"):
-            raise ValueError("Grating: a MirrorQuadric / MirrorConic is not supported as a substrate")
+        if hasattr(Mirror, "_quadric_coefficients") or hasattr(Mirror, "_freeform_figure"):
+            raise ValueError("Grating: a MirrorQuadric / MirrorConic / MirrorFreeform is not supported as a substrate")
         tname = getattr(Mirror, "type", None)
         if not (isinstance(tname, str) and "Mirror" in tname) or getattr(Mirror, "_abi_kind", None) is None:
             raise ValueError("Grating: the substrate must be one of the mirror classes (a Mask cannot carry a grating)")

@@ -90,6 +90,13 @@ def _build_descriptor(oe, IgnoreDefects, backend):
         # ModuleMirror.MirrorQuadric and its kin: traced by art_trace_quadric only, one element per launch
         d.flags |= _abi.ART_FLAG_QUADRIC
         d.quadric = optic
+    d.freeform = None
+    d.figure = None
+    if hasattr(optic, "_freeform_figure"):
+        # ModuleMirror.MirrorFreeform: traced by art_trace_freeform only, one element per launch; its figure table goes to
+        # the device with the first trace (_trace_one)
+        d.flags |= _abi.ART_FLAG_FREEFORM
+        d.freeform = optic
     if hasattr(optic, "DeformationList") and len(optic.DeformationList) > 0:
         be = backend or _lib.get_backend()
         keep = []
@@ -138,15 +145,22 @@ def _as_bundle(rays, backend=None):
 
 _CHAIN_MAX = 8          # elements per fused launch (kChainMax in csrc/art_scene.h)
 # elements the fused launches, the scene table and the guide kernel refuse: traced element by element, a launch each
-_STEPWISE_FLAGS = _abi.ART_FLAG_ZERN_RECURRENCE | _abi.ART_FLAG_GRATING | _abi.ART_FLAG_QUADRIC
+_STEPWISE_FLAGS = _abi.ART_FLAG_ZERN_RECURRENCE | _abi.ART_FLAG_GRATING | _abi.ART_FLAG_QUADRIC | _abi.ART_FLAG_FREEFORM
 
 
 def _trace_one(be, desc, vin, vout, n, wavelength, grooves):
-    """One element, one launch: art_trace_element, art_trace_quadric for a ModuleMirror.MirrorQuadric, or
-    art_trace_grating for a ModuleMirror.Grating at the bundle's wavelength.  `grooves`: the groove counts the rays arrive
-    with (device tensor [n] or None); returns those they leave with -- the same object unless the element is a grating."""
+    """One element, one launch: art_trace_element, art_trace_quadric for a ModuleMirror.MirrorQuadric, art_trace_freeform
+    for a ModuleMirror.MirrorFreeform, or art_trace_grating for a ModuleMirror.Grating at the bundle's wavelength.
+    `grooves`: the groove counts the rays arrive with (device tensor [n] or None); returns those they leave with -- the
+    same object unless the element is a grating."""
     if desc.flags & _abi.ART_FLAG_QUADRIC:
         be.trace_quadric(desc, desc.quadric._quadric_coefficients(), vin, vout, n)
+        return grooves
+    if desc.flags & _abi.ART_FLAG_FREEFORM:
+        if desc.figure is None:
+            table, radius, order = desc.freeform._freeform_figure()
+            desc.figure = (be.from_numpy(table), radius, order)          # uploaded once per descriptor
+        be.trace_freeform(desc, desc.freeform._base_coefficients(), desc.figure, vin, vout, n)
         return grooves
     if not desc.flags & _abi.ART_FLAG_GRATING:
         be.trace_element(desc, vin, vout, n)
@@ -211,8 +225,8 @@ def RayTracingCalculation(source_rays, optical_elements, IgnoreDefects=True, mod
         keep.append(k)
     mode = mode or DEFAULT_TRACE_MODE
     if any(d.flags & _STEPWISE_FLAGS for d in descs):
-        # Zernike orders above 16 run the recurrences per ray, a grating fans out in wavelength, a general quadric has its
-        # own intersection: kernels of their own, one element per launch
+        # Zernike orders above 16 run the recurrences per ray, a grating fans out in wavelength, a general quadric and a
+        # freeform have their own intersections: kernels of their own, one element per launch
         mode = "element"
     bad = next((k for k, d in enumerate(descs) if d.nonfinite), None)
     if bad is not None:
@@ -580,7 +594,7 @@ def _placeChains(SourceProperties, OpticsList, variants, Description):
     # the source generation enqueued above on the caller's stream (0.5 ms of device work per 1e7 rays that the placement
     # arithmetic below overlaps instead of waiting for).  Only for optics without defect tables: those are uploaded
     # while their descriptor is built, and a table must not change streams between its upload and its readers.
-    plain = not any(hasattr(O, "DeformationList") for O in OpticsList)
+    plain = not any(hasattr(O, "DeformationList") or hasattr(O, "_freeform_figure") for O in OpticsList)
     guide_ctx = be.side_stream_context("guides") if (plain and hasattr(be, "side_stream_context")) else contextlib.nullcontext()
     with guide_ctx, mgeo.frozen_hashes():
         chains = _placeChainsOn(be, Source, OpticsList, variants, Description, c)

@@ -18,6 +18,7 @@ ART_FLAG_PERTURBED_NORMAL = 1
 ART_FLAG_ZERN_RECURRENCE = 2
 ART_FLAG_GRATING = 4
 ART_FLAG_QUADRIC = 8
+ART_FLAG_FREEFORM = 16
 ART_ZERN_RECURRENCE_MAX_ORDER = 64
 
 ART_ZERN_MAX_ORDER = 16
@@ -81,6 +82,10 @@ class ArtGratingDesc(C.Structure):
 
 class ArtQuadricDesc(C.Structure):
     _fields_ = [("q", C.c_double * 6), ("b", C.c_double * 3), ("c", C.c_double)]
+
+
+class ArtFigureDesc(C.Structure):
+    _fields_ = [("table", C.c_void_p), ("radius", C.c_double), ("order", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ArtDetectorDesc(C.Structure):
@@ -298,6 +303,8 @@ PROTOTYPES = {
                                     C.POINTER(ArtBundleView), C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
     "art_trace_quadric": (C.c_int, [C.POINTER(ArtElementDesc), C.POINTER(ArtQuadricDesc), C.POINTER(ArtBundleView),
                                     C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
+    "art_trace_freeform": (C.c_int, [C.POINTER(ArtElementDesc), C.POINTER(ArtQuadricDesc), C.POINTER(ArtFigureDesc),
+                                     C.POINTER(ArtBundleView), C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
     "art_trace_chain": (C.c_int, [C.POINTER(ArtElementDesc), C.c_int32, C.POINTER(ArtBundleView),
                                   C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),
     "art_scene_bytes": (C.c_int64, [C.c_int32, C.c_int32]),

@@ -156,6 +156,21 @@ class HipBackend:
         self.check(self._timed(lambda: self.fn["art_trace_quadric"](C.byref(desc), C.byref(q), C.byref(view_in),
                                                                     C.byref(view_out), n, sp)), "art_trace_quadric")
 
+    def trace_freeform(self, desc, coefficients, figure, view_in, view_out, n):
+        """art_trace_freeform: `desc` (an ArtElementDesc with ART_FLAG_FREEFORM) reflects the bundle `view_in` off the base
+        quadric `coefficients` (q[6], b[3], c) carrying the figure `figure` = (device tensor of ART_ZERN_STRIDE doubles in
+        the dense layout, radius, order): include/art_hip.h."""
+        q = _abi.ArtQuadricDesc()
+        co = [float(v) for v in coefficients]
+        q.q[:], q.b[:], q.c = co[0:6], co[6:9], co[9]
+        table, radius, order = figure
+        if table.numel() < _abi.ART_ZERN_STRIDE:
+            raise ValueError("trace_freeform: the figure table must hold ART_ZERN_STRIDE doubles")
+        f = _abi.ArtFigureDesc(table.data_ptr(), float(radius), int(order), 0)
+        sp = self.stream_ptr()
+        self.check(self._timed(lambda: self.fn["art_trace_freeform"](C.byref(desc), C.byref(q), C.byref(f), C.byref(view_in),
+                                                                     C.byref(view_out), n, sp)), "art_trace_freeform")
+
     def trace_chain(self, descs, view_in, views_out, n, readout=None):
         """art_trace_chain, or art_trace_chain_readout when `readout` (from new_chain_readout) is given."""
         m = len(descs)

@@ -1053,6 +1053,141 @@ ART_HD bool quadric_trace(const ArtElementDesc& e, const ArtQuadricDesc& Q, Ray&
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Freeform mirror (ART_FLAG_FREEFORM, art_trace_freeform; the reference has no counterpart): a quadric base in its pole
+// frame plus a polynomial height figure,
+//     z = sag_base(x, y) + h(x, y),   h = sum_{p+q<=N} a_pq (x/R)^p (y/R)^q,  N <= 16   (mm; h > 0: towards the light)
+// i.e. implicitly  Phi(P) = F(x, y, z - h(x, y)) = 0  with the base's F (ArtQuadricDesc).  `fig` is ONE table in the dense
+// layout of the Zernike defects, [R, N, A, dA/dx, dA/dy] (art_hip.h), read by zernike_offset / zernike_slopes at the
+// pole-frame (x, y).  Half the gradient, taken at P' = (x, y, z - h) with g = Q P' + b:
+//     G = (g_x - g_z h_x, g_y - g_z h_y, g_z),   n = -G / |G| .
+// Intersection along P = A + t u: the candidates are the base quadric's roots with t > 1e-12 and dF/dz < 0
+// (quadric_trace's tests other than the support), in increasing t.  Each is refined by Newton's iteration on
+// phi(t) = Phi(A + t u), phi' = 2 G.u, with F evaluated at P' NEAR THE POLE, F = P'.(g + b) + c (terms of the size of the
+// footprint), not as a polynomial in t from the distant ray origin.  One step: dt = -F / (2 G.u), t += dt; it has
+// converged when |dt| <= ART_FREEFORM_TOL * max(1, |t|) (t the new value), and a candidate that has not after
+// ART_FREEFORM_MAX_STEPS steps is given up (tau = 1e-13, K = 12).  Newton converges quadratically here (a 10 nm figure on
+// a 2 degree ellipsoid: steps of 3e-4, 9e-11, 1e-16 mm; a 2 mm deep paraboloid as the figure of a plane at 45 degrees:
+// 1e-12 by step 4), so the accepted t is exact to rounding although the tolerance is 1e-13, and the gradient -- the one
+// of the last evaluation, |dt| away from the hit -- is off by |dt| times the curvature: 1e-14 on a grazing mirror, 4e-13
+// on the most curved test scene (a closed ellipse of 15 mm radius), against the parity bound of 1e-10.  The converged
+// candidate is the hit when its t is still > 1e-12, G_z < 0 and the support contains the REFINED (x - cx, y - cy);
+// otherwise the other candidate, if any, is refined and tested the same way; none: the ray is lost and r untouched.
+// With h == 0 the first Newton step is a rounding error and the outcome is quadric_trace's.  ONE run-time loop serves
+// both candidates and leaves when no lane of the wave has work left: the order-16 evaluators are inlined once.
+// Reflection, incidence angle, the way back, the renormalisation and path += t: quadric_trace's, step for step.
+// Two halves, as for the grating: freeform_hit (frame change, candidates, Newton) and freeform_reflect (normal,
+// reflection, way back), which share nothing wave-uniform but the frame map -- the kernel hands the second half the
+// descriptor it re-reads after the loop, so that the map does not occupy scalar registers across it.
+// (the support's parameters wait for the converged candidate in VECTOR registers on the device: the scalar file is
+// taken by the base's coefficients and the evaluators' coefficient loads)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define ART_PARK_IN_VGPR(x) asm("" : "+v"(x))
+#else
+#define ART_PARK_IN_VGPR(x) (void)0
+#endif
+#define ART_FREEFORM_TOL 1e-13
+#define ART_FREEFORM_MAX_STEPS 12
+struct FreeformHit {
+  double t, Px, Py, Pz, Gx, Gy, Gz, ux, uy, uz;   // ray parameter, hit point, half of grad Phi, direction (optic frame)
+  int steps;                                      // Newton steps of the accepted candidate
+};
+
+template <typename TP>
+ART_HD bool freeform_hit(const ArtElementDesc& e, const ArtQuadricDesc& Q, TP fig, const Ray& r, FreeformHit& H) {
+  double Ax, Ay, Az, ux, uy, uz;
+  mat3_apply_off(e.fwd, e.ART_D_IN_OFF, r.ox, r.oy, r.oz, Ax, Ay, Az);
+  mat3_apply(e.fwd, r.dx, r.dy, r.dz, ux, uy, uz);
+  // the base's roots: quadric_trace's
+  const double wz = fma(Q.q[4], ux, fma(Q.q[5], uy, Q.q[2] * uz));
+  const double wx = fma(Q.q[0], ux, fma(Q.q[3], uy, Q.q[4] * uz));
+  const double wy = fma(Q.q[3], ux, fma(Q.q[1], uy, Q.q[5] * uz));
+  const double hx = fma(Q.q[0], Ax, fma(Q.q[3], Ay, Q.q[4] * Az)) + Q.b[0];
+  const double hy = fma(Q.q[3], Ax, fma(Q.q[1], Ay, Q.q[5] * Az)) + Q.b[1];
+  const double hz = fma(Q.q[4], Ax, fma(Q.q[5], Ay, Q.q[2] * Az)) + Q.b[2];
+  const double qa = dot3(ux, uy, uz, wx, wy, wz);
+  const double qb = 2.0 * dot3(ux, uy, uz, hx, hy, hz);
+  const double qc = dot3(Ax, Ay, Az, hx + Q.b[0], hy + Q.b[1], hz + Q.b[2]) + Q.c;
+  double t1 = 0.0, t2 = 0.0;
+  const int nr = quadratic_roots(qa, qb, qc, t1, t2);
+  const bool c1 = (nr > 0) && (t1 > 1e-12) && (fma(t1, wz, hz) < 0.0);
+  const bool c2 = (nr > 1) && (t2 > 1e-12) && (fma(t2, wz, hz) < 0.0);
+  // t: the candidate under refinement; tn: the one that waits (left > 1)
+  int left = (c1 ? 1 : 0) + (c2 ? 1 : 0);
+  double t = c1 ? t1 : t2, tn = t2;
+  if (c1 && c2 && t2 < t1) { t = t2; tn = t1; }
+  double sup[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    sup[k] = k < 6 ? e.sp[k] : e.centre[k - 6];
+    ART_PARK_IN_VGPR(sup[k]);
+  }
+  bool busy = left > 0, hit = false;
+  int it = 0;
+  double Px = 0.0, Py = 0.0, Pz = 0.0, Gx = 0.0, Gy = 0.0, Gz = -1.0;
+  while (ART_WAVE_ANY(busy)) {
+    const double x = fma(t, ux, Ax), y = fma(t, uy, Ay), z = fma(t, uz, Az);
+    double sx, sy;
+    const double zp = z - zernike_offset(fig, x, y);
+    zernike_slopes(fig, x, y, sx, sy);
+    const double gx = fma(Q.q[0], x, fma(Q.q[3], y, Q.q[4] * zp)) + Q.b[0];
+    const double gy = fma(Q.q[3], x, fma(Q.q[1], y, Q.q[5] * zp)) + Q.b[1];
+    const double gz = fma(Q.q[4], x, fma(Q.q[5], y, Q.q[2] * zp)) + Q.b[2];
+    const double F = dot3(x, y, zp, gx + Q.b[0], gy + Q.b[1], gz + Q.b[2]) + Q.c;
+    const double ex = fma(-gz, sx, gx), ey = fma(-gz, sy, gy);
+    if (busy) {
+      const double dt = -0.5 * F / dot3(ex, ey, gz, ux, uy, uz);
+      t += dt;
+      ++it;
+      const bool conv = fabs(dt) <= ART_FREEFORM_TOL * fmax(1.0, fabs(t));
+      if (conv) {
+        Px = fma(t, ux, Ax); Py = fma(t, uy, Ay); Pz = fma(t, uz, Az);
+        hit = (t > 1e-12) && (gz < 0.0) && include_support(e.support_kind, sup, Px - sup[6], Py - sup[7]);
+        Gx = ex; Gy = ey; Gz = gz;
+      }
+      if (hit) {
+        busy = false;
+      } else if (conv || it >= ART_FREEFORM_MAX_STEPS) {   // this candidate is out (a NaN step never converges)
+        --left;
+        busy = left > 0;
+        t = tn;
+        it = 0;
+      }
+    }
+  }
+  if (!hit) return false;
+  H.t = t; H.Px = Px; H.Py = Py; H.Pz = Pz; H.Gx = Gx; H.Gy = Gy; H.Gz = Gz; H.ux = ux; H.uy = uy; H.uz = uz;
+  H.steps = it;
+  return true;
+}
+
+ART_HD void freeform_reflect(const ArtElementDesc& e, const FreeformHit& H, Ray& r) {
+  const double ig = -rsqrt_full(dot3(H.Gx, H.Gy, H.Gz, H.Gx, H.Gy, H.Gz));
+  const double nx = H.Gx * ig, ny = H.Gy * ig, nz = H.Gz * ig;
+  // reflection, incidence angle, way back and renormalisation: trace_ray's
+  const double dn = dot3(H.ux, H.uy, H.uz, nx, ny, nz);
+  const double vx = fma(-2.0 * dn, nx, H.ux), vy = fma(-2.0 * dn, ny, H.uy), vz = fma(-2.0 * dn, nz, H.uz);
+  const double inc = kahan_angle_unit(-H.ux, -H.uy, -H.uz, nx, ny, nz, -dn);
+  double dx, dy, dz;
+  mat3t_apply_off(e.fwd, e.ART_D_OUT_OFF, H.Px, H.Py, H.Pz, r.ox, r.oy, r.oz);
+  mat3t_apply(e.fwd, vx, vy, vz, dx, dy, dz);
+  const double s2 = dot3(dx, dy, dz, dx, dy, dz);
+  const double kk = fma(-0.5, s2, 1.5);
+  r.dx = dx * kk; r.dy = dy * kk; r.dz = dz * kk;
+  r.path += H.t;
+  r.inc = inc;
+}
+
+// `steps` (optional): Newton steps of the accepted candidate
+template <typename TP>
+ART_HD bool freeform_trace(const ArtElementDesc& e, const ArtQuadricDesc& Q, TP fig, Ray& r, int* steps = nullptr) {
+  FreeformHit H;
+  if (!freeform_hit(e, Q, fig, r, H)) return false;
+  freeform_reflect(e, H, r);
+  if (steps) *steps = H.steps;
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Detector read-out for one ray (ART/ModuleDetector.py:191-234, :272-275; ModuleGeometry.py:48-57)
 ART_HD void detector_ray(const ArtDetectorDesc& d, const Ray& r, double& Ix, double& Iy, double& Iz, double& X,
                          double& Y, double& opl) {

@@ -732,6 +732,35 @@ __global__ __launch_bounds__(kBlock) void k_trace_quadric(const ElemArg ea, cons
   store_slot(bo, i, r, ok);
 }
 
+// Freeform mirror (ART_FLAG_FREEFORM, art_device.h freeform_trace): k_trace_quadric's shape -- one ray per thread, the
+// base's ten coefficients in the kernel arguments -- plus the figure's dense table, read through scalar loads inside a
+// Newton loop that the whole wave leaves together.  No LDS, no barrier.
+// Scalar registers: the loop keeps the ten coefficients, the support and the evaluators' coefficient loads in them; the
+// frame map and the nine output addresses, which only the code behind the loop needs, would stay there across it (every
+// kernel argument is loaded on entry) and push the allocation over the file.  They are read behind the loop instead,
+// through an index (always blockIdx.y == 0) that the compiler cannot see through before the loop has produced t.
+struct ViewArg {
+  ArtBundleView v[1];
+};
+__global__ __launch_bounds__(kBlock) void k_trace_freeform(const ElemArg ea, const ArtQuadricDesc q, const double* __restrict__ fig,
+                                                           const ArtBundleView in, const ViewArg outs, const int64_t n) {
+  const ArtElementDesc& e = ea.e[blockIdx.y];
+  const BundleRsrc bi = make_rsrc(in, n);
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  art::Ray r;
+  r.inc = 0.0;
+  uint8_t a;
+  load_slot(bi, i, r, a);
+  bool ok = a != 0;
+  art::FreeformHit h = {};
+  if (ok) ok = art::freeform_hit(e, q, ART_ZUNI(fig), r, h);
+  unsigned late = blockIdx.y;
+  asm volatile("" : "+s"(late) : "v"(h.t));
+  if (ok) art::freeform_reflect(ea.e[late], h, r);
+  const BundleRsrc bo = make_rsrc(outs.v[late], n);
+  store_slot(bo, i, r, ok);
+}
+
 using art::ChainArgs;
 using art::kChainMax;
 
@@ -3350,6 +3379,7 @@ int check_elem(const ArtElementDesc* e) {
 
 const char* const kGratingRefusal = "an element is a grating: trace it with art_trace_grating";
 const char* const kQuadricRefusal = "an element is a general quadric: trace it with art_trace_quadric";
+const char* const kFreeformRefusal = "an element is a freeform mirror: trace it with art_trace_freeform";
 
 template <int KIND>
 void launch_element(const ArtElementDesc& e, const ArtBundleView& in, const ArtBundleView& out, int64_t n,
@@ -3570,6 +3600,7 @@ int art_trace_element(const ArtElementDesc* e, const ArtBundleView* in, const Ar
   if (rc) return rc;
   if (e->flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
   if (e->flags & ART_FLAG_QUADRIC) return fail(ART_ERR_UNSUPPORTED, kQuadricRefusal);
+  if (e->flags & ART_FLAG_FREEFORM) return fail(ART_ERR_UNSUPPORTED, kFreeformRefusal);
   if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
   if (n == 0) return ART_OK;  // an empty bundle has no arrays to point to
   if (!view_ok(in) || !view_ok(out)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
@@ -3603,6 +3634,7 @@ int art_trace_grating(const ArtElementDesc* e, const ArtGratingDesc* g, const do
   int rc = check_elem(e);
   if (rc) return rc;
   if (e->flags & ART_FLAG_QUADRIC) return fail(ART_ERR_UNSUPPORTED, kQuadricRefusal);
+  if (e->flags & ART_FLAG_FREEFORM) return fail(ART_ERR_UNSUPPORTED, kFreeformRefusal);
   if (e->kind == ART_MASK) return fail(ART_ERR_BAD_ARG, "art_trace_grating: a mask cannot be a grating");
   if (e->n_defects > 0 || e->n_grid > 0) return fail(ART_ERR_BAD_ARG, "art_trace_grating: mirrors with defects are not supported as substrates");
   if (!g || !wavelengths_host || !outs_host) return fail(ART_ERR_BAD_ARG, "art_trace_grating: NULL argument");
@@ -3632,6 +3664,7 @@ int art_trace_quadric(const ArtElementDesc* e, const ArtQuadricDesc* q, const Ar
                       int64_t n, void* stream) {
   int rc = check_elem(e);
   if (rc) return rc;
+  if (e->flags & ART_FLAG_FREEFORM) return fail(ART_ERR_UNSUPPORTED, kFreeformRefusal);
   if (!q || !in || !out) return fail(ART_ERR_BAD_ARG, "art_trace_quadric: NULL argument");
   if (e->n_defects > 0 || e->n_grid > 0) return fail(ART_ERR_BAD_ARG, "art_trace_quadric: mirrors with defects are not supported");
   bool finite = isfinite(q->c), any = false;
@@ -3653,6 +3686,35 @@ int art_trace_quadric(const ArtElementDesc* e, const ArtQuadricDesc* q, const Ar
   return launched("art_trace_quadric launch");
 }
 
+int art_trace_freeform(const ArtElementDesc* e, const ArtQuadricDesc* q, const ArtFigureDesc* figure, const ArtBundleView* in,
+                       const ArtBundleView* out, int64_t n, void* stream) {
+  int rc = check_elem(e);
+  if (rc) return rc;
+  if (!q || !figure || !in || !out) return fail(ART_ERR_BAD_ARG, "art_trace_freeform: NULL argument");
+  if (e->n_defects > 0 || e->n_grid > 0) return fail(ART_ERR_BAD_ARG, "art_trace_freeform: defects on the element are not supported (they belong into the figure)");
+  if (e->flags & (ART_FLAG_GRATING | ART_FLAG_QUADRIC)) return fail(ART_ERR_BAD_ARG, "art_trace_freeform: the element is flagged as a grating or as a plain quadric");
+  bool finite = isfinite(q->c), any = false;
+  for (int k = 0; k < 6; ++k) { finite = finite && isfinite(q->q[k]); any = any || q->q[k] != 0.0; }
+  for (int k = 0; k < 3; ++k) { finite = finite && isfinite(q->b[k]); any = any || q->b[k] != 0.0; }
+  if (!finite) return fail(ART_ERR_BAD_ARG, "art_trace_freeform: every coefficient must be finite");
+  if (!any) return fail(ART_ERR_BAD_ARG, "art_trace_freeform: q and b are all zero: no surface");
+  if (!figure->table) return fail(ART_ERR_BAD_ARG, "art_trace_freeform: the figure table is NULL");
+  if (figure->order < 0 || figure->order > ART_ZERN_MAX_ORDER) return fail(ART_ERR_BAD_ARG, "art_trace_freeform: figure order outside [0, 16]");
+  if (!(isfinite(figure->radius) && figure->radius > 0.0)) return fail(ART_ERR_BAD_ARG, "art_trace_freeform: the figure's radius must be finite and positive");
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (n == 0) return ART_OK;  // an empty bundle has no arrays to point to
+  if (!view_ok(in) || !view_ok(out)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
+  ElemArg ea;
+  ea.e[0] = *e;
+  art::prepare_element(ea.e[0]);
+  per_launch(n, [&](const int64_t off, const int64_t m) {
+    hipLaunchKernelGGL(k_trace_freeform, dim3(grid_stream(m)), dim3(kBlock), 0, (hipStream_t)stream, ea, *q, figure->table,
+                       view_at(*in, off), ViewArg{{view_at(*out, off)}}, m);
+    return ART_OK;
+  });
+  return launched("art_trace_freeform launch");
+}
+
 static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const ArtBundleView* in,
                             const ArtBundleView* outs, const ArtChainReadout* ro, int64_t n, void* stream) {
   if (!elems || !outs || n_elems <= 0) return fail(ART_ERR_BAD_ARG, "empty chain");
@@ -3664,6 +3726,7 @@ static int trace_chain_impl(const ArtElementDesc* elems, int32_t n_elems, const 
       return fail(ART_ERR_UNSUPPORTED, "an element carries Zernike tables in the recurrence layout: trace it with art_trace_element");
     if (elems[k].flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
     if (elems[k].flags & ART_FLAG_QUADRIC) return fail(ART_ERR_UNSUPPORTED, kQuadricRefusal);
+    if (elems[k].flags & ART_FLAG_FREEFORM) return fail(ART_ERR_UNSUPPORTED, kFreeformRefusal);
   }
   hipStream_t s = (hipStream_t)stream;
   if (ro) {
@@ -4756,6 +4819,7 @@ int art_trace_guides(const ArtElementDesc* elems, int32_t count, double* rays, u
       return fail(ART_ERR_UNSUPPORTED, "an element carries Zernike tables in the recurrence layout: trace it with art_trace_element");
     if (elems[k].flags & ART_FLAG_GRATING) return fail(ART_ERR_UNSUPPORTED, kGratingRefusal);
     if (elems[k].flags & ART_FLAG_QUADRIC) return fail(ART_ERR_UNSUPPORTED, kQuadricRefusal);
+    if (elems[k].flags & ART_FLAG_FREEFORM) return fail(ART_ERR_UNSUPPORTED, kFreeformRefusal);
     ga.e[k] = elems[k];
     art::prepare_element(ga.e[k]);
     defects = defects || ga.e[k].n_defects > 0 || ga.e[k].n_grid > 0;

@@ -95,6 +95,7 @@ inline int scene_pack(const ArtElementDesc* elems, int n_chains, int n_elems, co
         if (e.flags & ART_FLAG_ZERN_RECURRENCE) { *err = "an element carries Zernike tables in the recurrence layout: trace it with art_trace_element"; return ART_ERR_UNSUPPORTED; }
         if (e.flags & ART_FLAG_GRATING) { *err = "an element is a grating: trace it with art_trace_grating"; return ART_ERR_UNSUPPORTED; }
         if (e.flags & ART_FLAG_QUADRIC) { *err = "an element is a general quadric: trace it with art_trace_quadric"; return ART_ERR_UNSUPPORTED; }
+        if (e.flags & ART_FLAG_FREEFORM) { *err = "an element is a freeform mirror: trace it with art_trace_freeform"; return ART_ERR_UNSUPPORTED; }
         a.e[k] = e;
         prepare_element(a.e[k]);
         if (e.n_defects > 0 || e.n_grid > 0) { a.flags |= kFlagDefects; h.flags |= kFlagDefects; }

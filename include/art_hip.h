@@ -60,6 +60,7 @@ enum ArtSupportKind {
 #define ART_FLAG_ZERN_RECURRENCE 2u  /* the element's Zernike tables are in the RECURRENCE layout (any order, below)      */
 #define ART_FLAG_GRATING 4u          /* this element is a grating: only art_trace_grating traces it                        */
 #define ART_FLAG_QUADRIC 8u          /* this element is a general quadric mirror: only art_trace_quadric traces it         */
+#define ART_FLAG_FREEFORM 16u        /* this element is a freeform mirror (quadric + figure): only art_trace_freeform does */
 
 /* Zernike defect table (ART/ModuleDefects.py:149-174), a DEVICE array of doubles per element.  The polynomials
  * of ART/recursive_zernike_generator.py have integer monomial coefficients; the host expands
@@ -215,6 +216,40 @@ typedef struct ArtQuadricDesc {
 } ArtQuadricDesc;
 int art_trace_quadric(const ArtElementDesc* e, const ArtQuadricDesc* q, const ArtBundleView* in,
                       const ArtBundleView* out, int64_t n, void* stream);
+
+/* Freeform and aspheric mirrors (added under ABI 14: ART_FLAG_FREEFORM, ArtFigureDesc, art_trace_freeform): a quadric base
+ * in its pole frame (ArtQuadricDesc as above: origin on the surface, +z its normal there) plus a polynomial height figure
+ *     z = sag_base(x, y) + h(x, y),    h = sum_{p+q<=N} a_pq (x/R)^p (y/R)^q  in mm,  N <= ART_ZERN_MAX_ORDER ,
+ * implicitly Phi(P) = F(x, y, z - h(x, y)) = 0.  Positive h is a bump towards the incoming light.  Figure errors of
+ * nanometres on a KB or Wolter mirror and aspheric departures of millimetres (an even asphere, a corrector plate) are the
+ * same code: the ray is intersected with Phi exactly, by Newton's iteration, not by a first-order slide.
+ * The figure is ONE table in the dense layout of the Zernike defects above (ART_ZERN_STRIDE doubles in DEVICE memory:
+ * [R, N, A, dA/dx, dA/dy], evaluated at the pole-frame (x, y), no centre subtracted), which holds any polynomial of total
+ * degree <= 16; ArtFigureDesc carries its device address and host copies of R and N for the validation.
+ * Per ray, with P = A + t u: the candidates are the base's roots with t > 1e-12 and dF/dz < 0 (art_trace_quadric's tests
+ * other than the support), in increasing t.  Each is refined by Newton on phi(t) = Phi(A + t u): dt = -phi / phi',
+ * phi' = grad Phi . u, grad Phi = (F_x - F_z h_x, F_y - F_z h_y, F_z) at P' = (x, y, z - h), with F evaluated at P'.
+ * Convergence: |dt| <= 1e-13 * max(1, |t|) within at most 12 steps (tau = 1e-13, K = 12; Newton converges quadratically,
+ * so the accepted t is exact to rounding: typical figures take 2 to 5 steps).  A converged candidate is the hit when its
+ * t is still > 1e-12, Phi_z < 0 there and the support contains the REFINED (x - centre[0], y - centre[1]); otherwise the
+ * other candidate, if any, is refined and tested the same way; a candidate that does not converge is given up; no hit:
+ * the ray is lost.  Normal n = -grad Phi / |grad Phi|; reflection, incidence, path += t as for art_trace_quadric, whose
+ * outcome a zero figure reproduces.
+ * e->kind is ART_PLANE by convention and ignored; e->mp is unused.  Reads `in`, writes `out` (may alias `in`); slots dead
+ * on input and lost rays get alive = 0 and their other outputs are left untouched.  Any n >= 0 (chunked like
+ * art_trace_element).  ART_ERR_BAD_ARG, before any device work: NULL pointers, an invalid element (art_trace_element's
+ * rules), an element that also carries defects, ART_FLAG_GRATING or ART_FLAG_QUADRIC, a non-finite coefficient, q and b all
+ * zero, a NULL table, an order outside [0, 16], a radius that is not finite and positive, n < 0, an incomplete view with
+ * n > 0.  art_trace_element, art_trace_grating, art_trace_quadric, art_trace_chain(_readout), art_scene_pack and
+ * art_trace_guides return ART_ERR_UNSUPPORTED for an element with ART_FLAG_FREEFORM set.                              */
+typedef struct ArtFigureDesc {
+  const double* table;          /* DEVICE: ART_ZERN_STRIDE doubles, dense layout; table[0] = radius, table[1] = order        */
+  double radius;                /* host copy of table[0]: R > 0                                                              */
+  int32_t order;                /* host copy of table[1]: N in [0, ART_ZERN_MAX_ORDER]; entries of degree > N are zero       */
+  int32_t reserved;
+} ArtFigureDesc;
+int art_trace_freeform(const ArtElementDesc* e, const ArtQuadricDesc* q, const ArtFigureDesc* figure, const ArtBundleView* in,
+                       const ArtBundleView* out, int64_t n, void* stream);
 
 /* Whole chain in ONE launch: the ray stays in registers from element to element.  outs[k] receives the
  * bundle after element k for every k with outs[k].alive != NULL (pass zeroed views to skip history);
