@@ -1,7 +1,8 @@
 """GPU: diffraction gratings (ModuleMirror.Grating, art_trace_grating) against the fp64 oracle of tests/grating_common.py,
-which tests/test_grating_host.py holds to a long-double truth.  n = 4099 rays (a partial last tile), every 7th input
-slot dead.  Bounds: the project's parity bound (1e-10 of the reference magnitudes for points and paths, 1e-10 absolute
-for directions) unless a test states its own."""
+which tests/test_grating_host.py holds to a long-double truth (sections 1 to 7: plane, sphere, torus), and against that
+long-double truth itself on all six substrates (section 8).  n = 4099 rays (a partial last tile), every 7th input
+slot dead, unless a test says otherwise.  Bounds: the project's parity bound (1e-10 of the reference magnitudes for points and
+paths, 1e-10 absolute for directions) unless a test states its own."""
 import ctypes as C
 
 import numpy as np
@@ -390,3 +391,257 @@ def test_grating_between_two_toroids_eager_lazy_and_many(art, toroid_chains):
             check_against_oracle(many[ci][k], refs[ci][k], f"many chain {ci} element {k}")
     prog_outs = ch.get_output_rays()
     check_against_oracle(prog_outs[-1], refs[1][2], "chain.get_output_rays")
+
+
+# ------------------------------------------------------------------ 8. every substrate against the long-double truth
+# The scenes of grating_common.scenes_six(): a grating on each of the six surfaces and on the convex sphere and cylinder,
+# generic / clipped / straddling the cut-off.  The truth (grating_common.truth, numpy.longdouble) is formed from the state the
+# DEVICE holds and seeded by the same substrate traced as a bare mirror (art_trace_element): the grating must hit exactly
+# those rays.  Every test first asserts about its own input that no ray is marginal (|s| < 1e-9, or within 1e-9 mm of the
+# support's edge); the alive masks are then compared bit for bit.  Bounds: the parity bound -- with s >= 1e-9 the direction's
+# conditioning is 1 / (2 sqrt(s)) <= 1.6e4, and the header's own deviation from this truth is below 3e-12
+# (tests/test_grating_host.py).
+SIX = gc.scenes_six()
+GENERIC_SIX = sorted(k for k, sc in SIX.items() if sc["family"] == "generic")
+SIZES = [1, 63, 64, 65, 257, 70001]          # around a wavefront, more than one workgroup, a partial last tile
+
+
+def mirror_trace(art, oe, src):
+    """The bare substrate in the pose of `oe` through art_trace_element; returns (bundle, seed): segment lengths, NaN = lost."""
+    bare = gc.on_pose(getattr(oe.type, "Mirror", oe.type), oe)
+    out = art.mp.RayTracingCalculation(src, [bare], mode="element")[0]
+    d, alive = out.data[6].cpu().numpy(), out.alive.cpu().numpy() != 0
+    return out, np.where(alive, d - src.data[6].cpu().numpy(), np.nan)
+
+
+def truth_of(art, oe, src, wl, large=None):
+    """(E, truth of `oe` on the device's state of `src`, the same with the large support)."""
+    P, V, path, alive = state(src)
+    g = None if src.grooves is None else src.grooves.cpu().numpy()
+    E = gc.element_spec(oe)
+    ref = gc.truth(E, P, V, path, alive, wl, mirror_trace(art, oe, src)[1], grooves=g)
+    if large is None or large is oe:
+        return E, ref, ref
+    return E, ref, gc.truth(gc.element_spec(large), P, V, path, alive, wl, mirror_trace(art, large, src)[1], grooves=g)
+
+
+def check_against_truth(got, ref, what):
+    assert np.array_equal(got["alive"], ref["alive"]), what + ": alive masks differ"
+    gc.assert_parity(got, ref, ref["alive"], what)
+    dev = gc.worst_deviation(got, ref, ref["alive"])
+    print(what, "worst deviation from the truth", " ".join(f"{k} {v:.1e}" for k, v in dev.items()))
+    return dev
+
+
+@pytest.mark.parametrize("name", sorted(SIX))
+def test_every_substrate_against_the_long_double_truth(art, name):
+    sc = SIX[name]
+    src = upload(art, sc["rays"], sc["wl"])
+    E, ref, ref_large = truth_of(art, sc["oe"], src, sc["wl"], sc["large"])
+    n_hit, n_alive = gc.own_input(sc, E, ref, ref_large, name, alive=state(src)[3])
+    assert (n_alive == 0) == (name in gc.EVANESCENT)    # N900_m1_a33: evanescent on the four grazing substrates, alive elsewhere
+    out = art.mp.RayTracingCalculation(src, [sc["oe"]])[0]
+    got = result(out)
+    check_against_truth(got, ref, name)
+    if sc["family"] == "cutoff":
+        m = ref["alive"]
+        dv = np.abs(np.asarray(got["vector"][m] - ref["vector"][m], dtype=float)).max(axis=1)
+        print(name, "dv * sqrt(s)", f"{float((dv * np.sqrt(np.asarray(ref['s'][m], dtype=float))).max()):.1e}")
+
+
+@pytest.mark.parametrize("name", GENERIC_SIX)
+def test_the_hit_does_not_depend_on_the_order(art, name):
+    """Point, path and incidence angle of a grating are the bare mirror's (the bound of test_order_zero_is_the_bare_toroid);
+    the masks are equal wherever the order propagates, and nothing is alive where it does not."""
+    sc = SIX[name]
+    src = upload(art, sc["rays"], sc["wl"])
+    out = art.mp.RayTracingCalculation(src, [sc["oe"]])[0]
+    ref, _ = mirror_trace(art, sc["oe"], src)
+    assert int(ref.alive.sum()) == int((state(src)[3] != 0).sum())
+    if name in gc.EVANESCENT:
+        assert int(out.alive.sum()) == 0
+        return
+    assert torch.equal(out.alive, ref.alive)
+    live = ref.alive.bool()
+    a, b = out.data[:, live].cpu().numpy(), ref.data[:, live].cpu().numpy()
+    for row in (0, 1, 2, 6, 7):
+        assert np.abs(a[row] - b[row]).max() <= 1e-14 * max(1.0, np.abs(b[row]).max()), row
+
+
+def _bytes_equal(a, b):
+    return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
+
+
+@pytest.mark.parametrize("n", SIZES)
+def test_bundle_sizes_sentinels_repeatability_and_aliasing(art, n):
+    """The clipped ellipsoid through the bare ABI with nw = 2: slots dead on input and lost rays keep what the outputs held."""
+    sc = SIX["ellipsoid_clipped"]
+    oe, wls = sc["oe"], [30e-6, 12e-6]
+    rays = gc.point_source(gc.SUBSTRATES["ellipsoid"][2], n)
+    if n == 1:
+        rays = (rays[0], rays[1], rays[2], np.ones(1, dtype=np.uint8))
+    src = upload(art, rays, None)
+    dev = src.data.device
+    g_in = torch.linspace(-2.0, 2.0, n, dtype=torch.float64, device=dev)
+    src.grooves = g_in
+    alive_in = state(src)[3]
+    refs = []
+    for wl in wls:
+        E, ref, ref_large = truth_of(art, oe, src, wl, sc["large"])
+        n_s, n_edge, s_min, d_min = gc.marginal(E, ref, ref_large, alive_in)
+        assert n_s == 0 and n_edge == 0, (n_s, n_edge, s_min, d_min)
+        refs.append(ref)
+    n_hit = int(refs[0]["hit"].sum())
+    assert n < 64 or 0 < n_hit < int((alive_in != 0).sum())
+    assert n_hit > 0
+
+    def run(source, outs, wl_list, g_out):
+        assert raw_grating(art, oe, wl_list, source, outs, g_in=g_in, g_out=g_out) == 0
+
+    outs = prefilled(art, src, 2)
+    g_out = torch.full((2, n), SENTINEL, dtype=torch.float64, device=dev)
+    run(src, outs, wls, g_out)
+    for j in range(2):
+        got = result(outs[j])
+        got["grooves"] = g_out[j].cpu().numpy()
+        check_against_truth(got, refs[j], f"n={n} wavelength {j}")
+        lost = torch.from_numpy(~refs[j]["alive"]).to(dev)
+        assert bool((outs[j].data[:, lost] == SENTINEL).all()), "a lost ray's slot was written"
+        assert bool((g_out[j, lost] == SENTINEL).all()) and bool((outs[j].alive[lost] == 0).all())
+    again = prefilled(art, src, 2)
+    g_again = torch.full((2, n), SENTINEL, dtype=torch.float64, device=dev)
+    run(src, again, wls, g_again)
+    for j in range(2):                                                                  # two runs, the same bytes
+        assert torch.equal(again[j].alive, outs[j].alive) and _bytes_equal(again[j].data, outs[j].data)
+    assert _bytes_equal(g_again, g_out)
+    inplace = art.RayBundle.allocate(n, like=src)                                      # nw = 1: the output may alias the input
+    inplace.data.copy_(src.data)
+    inplace.alive.copy_(src.alive)
+    g_one = torch.full((1, n), SENTINEL, dtype=torch.float64, device=dev)
+    run(inplace, [inplace], wls[:1], g_one)
+    live = outs[0].alive.bool()
+    assert torch.equal(inplace.alive, outs[0].alive)
+    assert _bytes_equal(inplace.data[:, live], outs[0].data[:, live]) and _bytes_equal(g_one[0, live], g_out[0, live])
+
+
+def test_widest_fan_out_on_the_convex_sphere(art):
+    """nw = ART_GRATING_MAX_WAVELENGTHS at n = 65 with the grating of the cut-off scene: from the whole bundle alive at
+    10 nm to none at 40 nm."""
+    sc = SIX["convex_sphere_cutoff"]
+    oe, nw, n = sc["oe"], art.abi.ART_GRATING_MAX_WAVELENGTHS, 65
+    wls = [float(w) for w in np.linspace(10e-6, 40e-6, nw)]
+    src = upload(art, gc.point_source(gc.SUBSTRATES["convex_sphere"][2], n), None)
+    dev = src.data.device
+    P, V, path, alive = state(src)
+    E = gc.element_spec(oe)
+    seed = mirror_trace(art, oe, src)[1]
+    refs = [gc.truth(E, P, V, path, alive, wl, seed) for wl in wls]
+    assert np.array_equal(refs[0]["hit"], alive != 0)
+    s = np.abs(np.array([np.asarray(r["s"], dtype=float)[r["hit"]] for r in refs]))
+    assert s.min() >= gc.MARGIN_S, f"a ray within {gc.MARGIN_S} of the cut-off: {s.min():.2e}"
+    counts = [int(r["alive"].sum()) for r in refs]
+    assert counts[0] == int((alive != 0).sum()) and counts[-1] == 0 and len(set(counts)) >= 5
+    fan = art.RayBundle.allocate_many(n, nw, src)
+    for b in fan:
+        b.data.fill_(SENTINEL)
+        b.alive.fill_(9)
+    gf = torch.full((nw, n), SENTINEL, dtype=torch.float64, device=dev)
+    assert raw_grating(art, oe, wls, src, fan, g_out=gf) == 0
+    got_alive = torch.stack([b.alive for b in fan]).cpu().numpy() != 0
+    for j in range(nw):
+        assert int(got_alive[j].sum()) == counts[j] and np.array_equal(got_alive[j], refs[j]["alive"]), j
+    half = int(np.argmin(np.abs(np.array(counts) - counts[0] / 2)))          # the wavelength that splits the bundle
+    assert 0 < counts[half] < counts[0]
+    for j in (0, nw // 2, half, nw - 1):
+        one, = prefilled(art, src)
+        g1 = torch.full((1, n), SENTINEL, dtype=torch.float64, device=dev)
+        assert raw_grating(art, oe, [wls[j]], src, [one], g_out=g1) == 0
+        assert torch.equal(fan[j].alive, one.alive) and _bytes_equal(fan[j].data, one.data) and _bytes_equal(gf[j], g1[0])
+    for j in (nw // 2, half):
+        got = result(fan[j])
+        got["grooves"] = gf[j].cpu().numpy()
+        check_against_truth(got, refs[j], f"fan-out, wavelength {j}")
+
+
+def _behind(oe_first, guide, distance, incidence_deg, optic):
+    """`optic` at `distance` along the guide ray that leaves `oe_first`, at `incidence_deg` in the plane spanned by that ray
+    and the first element's normal, major axis in that plane: place() about another axis."""
+    P0, v = np.asarray(guide["point"][0], dtype=float), np.asarray(guide["vector"][0], dtype=float)
+    a = np.asarray(oe_first.normal, dtype=float)
+    a = a - (a @ v) * v
+    a /= np.linalg.norm(a)
+    th = np.deg2rad(incidence_deg)
+    return gc.moe.OpticalElement(optic, P0 + distance * v, -np.cos(th) * v + np.sin(th) * a, np.sin(th) * v + np.cos(th) * a)
+
+
+def test_two_gratings_in_one_chain(art):
+    """A plane grating (600, +1, 33 deg) and a cylinder grating (300, -1, 118 deg) that catches the first one's diffracted
+    central ray.  Truth per element, each from the state the device holds in front of it; the last bundle's groove count is
+    the sum of the two gratings' own terms."""
+    wl = 30e-6
+    g1 = gc.place(art.mm.Grating(art.mm.MirrorPlane(art.ms.SupportRectangle(60.0, 10.0)), 600.0, 1, 33.0), 237.0, 75.0)
+    one = upload(art, (np.zeros((1, 3)), np.array([[1.0, 0.0, 0.0]]), np.zeros(1), np.ones(1, dtype=np.uint8)), wl)
+    guide = truth_of(art, g1, one, wl)[1]
+    assert guide["alive"][0]
+    g2 = _behind(g1, guide, 150.0, 75.0, art.mm.Grating(gc.substrate("cylinder"), 300.0, -1, 118.0))
+    els = [g1, g2]
+    src = upload(art, gc.point_source(2e-3), wl)
+    outs = art.mp.RayTracingCalculation(src, els)
+    assert src.grooves is None and outs[0].grooves is not None and outs[1].grooves is not outs[0].grooves
+    cur, refs = src, []
+    for k, oe in enumerate(els):
+        E, ref, _ = truth_of(art, oe, cur, wl)
+        n_s, n_edge, s_min, d_min = gc.marginal(E, ref, ref, state(cur)[3])
+        assert n_s == 0 and n_edge == 0, (k, n_s, n_edge, s_min, d_min)
+        check_against_truth(result(outs[k]), ref, f"two gratings, element {k}")
+        refs.append(ref)
+        cur = outs[k]
+    m = refs[1]["alive"]
+    assert int(m.sum()) == int((state(src)[3] != 0).sum())
+    total = np.asarray(refs[0]["term"] + refs[1]["term"], dtype=np.float64)
+    got = outs[1].grooves.cpu().numpy()
+    assert float(np.abs(refs[0]["term"][m]).max()) > 1.0 and float(np.abs(refs[1]["term"][m]).max()) > 1.0      # both count
+    assert np.abs(got[m] - total[m]).max() <= gc.PARITY * max(1.0, np.abs(total[m]).max())
+    last = art.mp.RayTracingCalculation(src, els, history=False)[-1]
+    lazy = art.mp.RayTracingCalculation(src, els, history="lazy")
+    live = outs[1].alive.bool()
+    for what, b in (("history=False", last), ("lazy, last", lazy[-1]), ("lazy, materialised", lazy[0])):
+        want = outs[0] if what == "lazy, materialised" else outs[1]
+        lv = want.alive.bool()
+        assert torch.equal(b.alive, want.alive), what
+        assert _bytes_equal(b.data[:, lv], want.data[:, lv]) and _bytes_equal(b.grooves[lv], want.grooves[lv]), what
+    assert int(live.sum()) > 0
+
+
+@pytest.fixture(scope="module")
+def placed_six(art):
+    """An ellipsoidal and a cylindrical grating, each followed by a plane fold mirror, through OEPlacement."""
+    chains = {}
+    for name, G, inc in (("ellipsoid", art.mm.Grating(gc.substrate("ellipsoid"), 600.0, 2, 118.0), 80.0),
+                         ("cylinder", art.mm.Grating(gc.substrate("cylinder"), 900.0, 1, 33.0), 75.0)):
+        sp = {"Divergence": 2e-3, "SourceSize": 0, "Wavelength": 30e-6, "DeltaFT": 0.5, "NumberRays": gc.N_RAYS}
+        fold = art.mm.MirrorPlane(art.ms.SupportRound(80.0))
+        chains[name] = art.mp.OEPlacement(sp, [G, fold], [237.0, 235.0], [inc, 45.0], [0.0, 0.0], name)
+    return chains
+
+
+@pytest.mark.parametrize("name", ["ellipsoid", "cylinder"])
+def test_ellipsoidal_and_cylindrical_gratings_through_placement(art, placed_six, name):
+    chain = placed_six[name]
+    g_el, fold = chain.optical_elements
+    wl = 30e-6
+    one = upload(art, (np.zeros((1, 3)), np.array([[1.0, 0.0, 0.0]]), np.zeros(1), np.ones(1, dtype=np.uint8)), wl)
+    guide = truth_of(art, g_el, one, wl)[1]
+    assert guide["alive"][0]
+    want = np.asarray(guide["point"][0] + 235.0 * guide["vector"][0], dtype=float)
+    assert np.abs(np.asarray(fold.position, dtype=float) - want).max() <= 1e-9
+    src = chain.source_rays
+    outs = art.mp.RayTracingCalculation(src, chain.optical_elements)
+    cur = src
+    for k, oe in enumerate(chain.optical_elements):
+        E, ref, _ = truth_of(art, oe, cur, wl)
+        n_s, n_edge, s_min, d_min = gc.marginal(E, ref, ref, state(cur)[3])
+        assert n_s == 0 and n_edge == 0, (k, n_s, n_edge, s_min, d_min)
+        assert ref["alive"].sum() > 0
+        check_against_truth(result(outs[k]), ref, f"{name} through placement, element {k}")
+        cur = outs[k]

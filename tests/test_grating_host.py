@@ -1,6 +1,6 @@
 """CPU: diffraction gratings -- the oracle against the long-double truth, the header's per-ray function (compiled with
-g++) against the truth, the host shell (Grating, RayBundle.grooves, refusals), the ABI mirror, and the device code's
-resource usage (no scratch memory)."""
+g++) against the truth on all six substrates, the host shell (Grating, RayBundle.grooves, refusals), the ABI mirror, and
+the device code's resource usage (no scratch memory)."""
 import ctypes as C
 import os
 import pickle
@@ -84,24 +84,34 @@ def harness(tmp_path_factory):
     return td, str(exe)
 
 
-@pytest.mark.parametrize("name", sorted(SCENES))
-def test_header_function_agrees_with_long_double_truth(harness, name):
+KIND_NUMBER = {"plane": 0, "sphere": 1, "parabola": 2, "torus": 3, "ellipsoid": 4, "cylinder": 5}     # include/art_hip.h
+
+
+def run_header(harness, tag, E, rays, wl, g_in, N=None, m=None):
+    """grating_ray of the header on every ray of a scene; rows of (ray[8], grooves, alive).  N = 0: the bare mirror."""
     td, exe = harness
-    oe, (P, V, path, alive), wl = SCENES[name]
-    E = gc.element_spec(oe)
+    P, V, path, alive = rays
     n = len(P)
     sp = list(E["support"][1:]) + [0.0] * 6
-    head = ([{"plane": 0, "sphere": 1, "torus": 3}[E["kind"]], 0 if E["support"][0] == "round" else 2] + list(E["fwd"].reshape(9))
+    head = ([KIND_NUMBER[E["kind"]], 0 if E["support"][0] == "round" else 2] + list(E["fwd"].reshape(9))
             + list(E["pos"]) + list(E["centre"]) + sp[:6] + (E["mp"] + [0.0] * 4)[:4]
-            + [E["q"][0], E["q"][1], E["N"], E["m"], wl, n, 0, 0, 0])
-    g_in = np.linspace(-3.0, 3.0, n)
+            + [E["q"][0], E["q"][1], E["N"] if N is None else N, E["m"] if m is None else m, wl, n, 0, 0, 0])
     rows = np.column_stack([P, V, path, alive.astype(float), g_in])
-    fin, fout = str(td / (name + ".in")), str(td / (name + ".out"))
+    fin, fout = str(td / (tag + ".in")), str(td / (tag + ".out"))
     with open(fin, "wb") as f:
         f.write(np.asarray(head, dtype=np.float64).tobytes())
         f.write(np.ascontiguousarray(rows, dtype=np.float64).tobytes())
     subprocess.check_call([exe, fin, fout])
-    out = np.fromfile(fout, dtype=np.float64).reshape(n, 10)
+    return np.fromfile(fout, dtype=np.float64).reshape(n, 10)
+
+
+@pytest.mark.parametrize("name", sorted(SCENES))
+def test_header_function_agrees_with_long_double_truth(harness, name):
+    oe, (P, V, path, alive), wl = SCENES[name]
+    E = gc.element_spec(oe)
+    n = len(P)
+    g_in = np.linspace(-3.0, 3.0, n)
+    out = run_header(harness, name, E, (P, V, path, alive), wl, g_in)
     ref = gc.diffract(E, P, V, path, alive, wl, grooves=g_in, T=gc.LD)
     clear = np.abs(np.asarray(ref["s"], dtype=float)) > 1e-9
     got_alive = out[:, 9] != 0
@@ -110,6 +120,74 @@ def test_header_function_agrees_with_long_double_truth(harness, name):
     gc.assert_parity(res, ref, ref["alive"] & got_alive, name)
     lost = ~got_alive                                   # a lost ray keeps its state and its groove count
     assert (out[lost, 0:3] == P[lost]).all() and (out[lost, 8] == g_in[lost]).all()
+
+
+# ---------------------------------------------------------------- the six substrates: header and oracle against the truth
+SIX = gc.scenes_six()
+THREE_KIND = sorted(k for k, sc in SIX.items() if sc["substrate"] in ("plane", "sphere", "torus"))     # what `diffract` knows
+
+
+def mirror_seed(harness, tag, E, rays):
+    """Which rays the bare substrate catches and their segment lengths (NaN: lost), from the header with N = 0."""
+    P, V, path, alive = rays
+    out = run_header(harness, tag, E, rays, 30e-6, np.zeros(len(P)), N=0.0, m=0)
+    return np.where(out[:, 9] != 0, out[:, 6] - path, np.nan)
+
+
+def six_truth(harness, name, g_in=None):
+    sc = SIX[name]
+    E, EL = gc.element_spec(sc["oe"]), gc.element_spec(sc["large"])
+    P, V, path, alive = sc["rays"]
+    ref = gc.truth(E, P, V, path, alive, sc["wl"], mirror_seed(harness, name + "_m", E, sc["rays"]), grooves=g_in)
+    ref_large = ref if sc["large"] is sc["oe"] else gc.truth(EL, P, V, path, alive, sc["wl"],
+                                                             mirror_seed(harness, name + "_ml", EL, sc["rays"]))
+    return sc, E, ref, ref_large
+
+
+@pytest.mark.parametrize("name", sorted(SIX))
+def test_header_function_agrees_with_long_double_truth_on_every_substrate(harness, name):
+    assert gc.HAVE_LD, "numpy.longdouble has no extended precision on this platform"
+    P, V, path, alive = SIX[name]["rays"]
+    g_in = np.linspace(-3.0, 3.0, len(P))
+    sc, E, ref, ref_large = six_truth(harness, name, g_in)
+    n_hit, n_alive = gc.own_input(sc, E, ref, ref_large, name)
+    if sc["family"] == "clipped":
+        assert n_hit == gc.CLIPPED_HITS[sc["substrate"]]
+    assert (n_alive == 0) == (name in gc.EVANESCENT)    # N900_m1_a33: evanescent on the four grazing substrates, alive elsewhere
+    out = run_header(harness, name, E, sc["rays"], sc["wl"], g_in)
+    got_alive = out[:, 9] != 0
+    assert np.array_equal(got_alive, ref["alive"]), name + ": alive masks differ"
+    res = {"point": out[:, 0:3], "vector": out[:, 3:6], "path": out[:, 6], "inc": out[:, 7], "grooves": out[:, 8]}
+    gc.assert_parity(res, ref, ref["alive"], name)
+    dev = gc.worst_deviation(res, ref, ref["alive"])
+    print(name, "worst deviation from the truth", {k: f"{v:.1e}" for k, v in dev.items()})
+    if sc["family"] == "cutoff":
+        m = ref["alive"]
+        dv = np.abs(np.asarray(res["vector"][m] - ref["vector"][m], dtype=float)).max(axis=1)
+        print(name, "dv * sqrt(s)", f"{float((dv * np.sqrt(np.asarray(ref['s'][m], dtype=float))).max()):.1e}")
+    lost = ~got_alive                                   # a lost ray keeps its state and its groove count
+    assert (out[lost, 0:3] == P[lost]).all() and (out[lost, 8] == g_in[lost]).all()
+
+
+@pytest.mark.parametrize("name", THREE_KIND)
+def test_fp64_oracle_agrees_with_long_double_truth_on_its_three_substrates(harness, name):
+    """`diffract` in fp64 (the oracle of the older GPU tests) against the truth seeded by the bare mirror."""
+    assert gc.HAVE_LD, "numpy.longdouble has no extended precision on this platform"
+    sc, E, ref, ref_large = six_truth(harness, name)
+    gc.own_input(sc, E, ref, ref_large, name)
+    P, V, path, alive = sc["rays"]
+    res = gc.diffract(E, P, V, path, alive, sc["wl"], T=np.float64)
+    assert np.array_equal(res["hit"], ref["hit"]) and np.array_equal(res["alive"], ref["alive"])
+    gc.assert_parity(res, ref, ref["alive"], name)
+    # The two long-double forms of the same equation, written independently (the literal root b^2 - c of `diffract` against
+    # the stable root of truth_common).  Both round at 1.1e-19; the literal root of the sphere loses R^2 / (t sqrt(disc)) ~ 1e5
+    # of that and a direction at the cut-off another 1.6e4: 1e-13 of the magnitudes is three decades above both.
+    full = gc.diffract(E, P, V, path, alive, sc["wl"], T=gc.LD)
+    assert np.array_equal(full["alive"], ref["alive"])
+    m = ref["alive"]
+    for key in ("point", "vector", "path", "inc", "grooves", "s"):
+        if m.any():
+            assert float(np.abs(full[key][m] - ref[key][m]).max()) <= 1e-13 * max(1.0, float(np.abs(ref[key][m]).max())), key
 
 
 # ------------------------------------------------------------------------------------------------------- host shell
