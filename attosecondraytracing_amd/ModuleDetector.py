@@ -147,7 +147,7 @@ class Detector:
         store=False skips the per-ray outputs (statistics only); lite=True: the caller needs only count, sum of paths,
         bounding box and path range of the statistics (a LITE fused read-out, ArtChainReadout.lite, may then be used)."""
         self._iscomplete()
-        B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+        B = RayBundle.of(RayList)
         fused = getattr(B, "_fused_readout", None)
         if fused is not None and not points3d and fused[0] == self._readout_key(path_centre) and fused[1] == B.version \
                 and (fused[2]["X"] is not None or not store) and (lite or not fused[2].get("lite")):
@@ -171,7 +171,7 @@ class Detector:
         (art_detector_scan_moments).  Two passes over the bundle: the first only finds the mean path used to centre
         the second."""
         self._iscomplete()
-        B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+        B = RayBundle.of(RayList)
         be, n, d = B.backend, B.n_slots, self._desc()
         first = be.detector_scan_moments(d, B.view(), B.intensity, n, 0.0)
         co = first[11] / first[0]

@@ -137,12 +137,6 @@ def _build_descriptor(oe, IgnoreDefects, backend):
     return d, keep
 
 
-def _as_bundle(rays, backend=None):
-    if isinstance(rays, RayBundle):
-        return rays
-    return RayBundle.from_ray_list(rays, backend)
-
-
 _CHAIN_MAX = 8          # elements per fused launch (kChainMax in csrc/art_scene.h)
 # elements the fused launches, the scene table and the guide kernel refuse: traced element by element, a launch each
 _STEPWISE_FLAGS = _abi.ART_FLAG_ZERN_RECURRENCE | _abi.ART_FLAG_GRATING | _abi.ART_FLAG_QUADRIC | _abi.ART_FLAG_FREEFORM
@@ -212,7 +206,7 @@ def RayTracingCalculation(source_rays, optical_elements, IgnoreDefects=True, mod
         if history != "lazy":
             raise ValueError("history must be True, False or 'lazy'")
         return LazyHistory(source_rays, optical_elements, IgnoreDefects, mode, detector, path_centre)
-    src = _as_bundle(source_rays)
+    src = RayBundle.of(source_rays)
     be = src.backend
     n = src.n_slots
     m = len(optical_elements)
@@ -301,7 +295,7 @@ def RayTracingSpectral(source_rays, optical_elements, grating_index, Wavelengths
         raise ValueError(f"Wavelengths: 1 to {_abi.ART_GRATING_MAX_WAVELENGTHS} values")
     if not all(np.isfinite(w) and w > 0 for w in wls):
         raise ValueError("Wavelengths must be finite and positive (mm)")
-    src = _as_bundle(source_rays)
+    src = RayBundle.of(source_rays)
     be, n, k = src.backend, src.n_slots, int(grating_index)
     head = RayTracingCalculation(src, optical_elements[:k], IgnoreDefects, history=False)[-1] if k > 0 else src
     desc, _ = element_descriptor(optical_elements[k], IgnoreDefects, be)
@@ -359,7 +353,7 @@ class LazyHistory:
     earlier is bit-identical to the one of the full trace (same kernels, same inputs: by construction)."""
 
     def __init__(self, source, elements, IgnoreDefects=True, mode=None, detector=None, path_centre=0.0, want=-1, first=None):
-        self._src, self._els = _as_bundle(source), list(elements)
+        self._src, self._els = RayBundle.of(source), list(elements)
         # what the bundle handed out below was traced through: poses / parameters of the elements (their hashes) and the
         # source's contents (its version).  A later re-trace for the rest of the history must see the same scene.
         self._scene_key = (_hash_list_of_objects(self._els), hash(self._src))
@@ -452,7 +446,7 @@ def _RayTracingCalculationMany(source_rays_list, optical_elements_list, IgnoreDe
     trace of their common prefix (below).  `detectors`: one placed Detector per chain whose read-out is fused behind the
     trace (see RayTracingCalculation); `sums=True` (without detectors): every chain's launch forms pass (1) of the
     analysis of its last bundle instead."""
-    sources = [_as_bundle(s) for s in source_rays_list]
+    sources = [RayBundle.of(s) for s in source_rays_list]
     c = len(sources)
     if c != len(optical_elements_list):
         raise ValueError("need one element list per source bundle")

@@ -85,7 +85,7 @@ def ApplyGaussianIntensityToRayList(RayList, IntensityFraction=1 / np.e ** 2):
               "0 and 1! I'm setting it to 1/e^2.")
         IntensityFraction = 1 / np.e ** 2
     from . import ModuleProcessing as mp
-    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+    B = RayBundle.of(RayList)
     before = B.content_key()
     if hasattr(B.backend, "gaussian_intensity_central") and B.n_slots > 0:
         # the axis (FindCentralRay's mean vector) is formed on the device from the bundle's sums: no host round trip

@@ -107,6 +107,34 @@ class HipBackend:
             self._scratch[key] = t
         return t
 
+    def _scratch_for(self, key, fn_name, *args):
+        """The scratch area `key` of the current stream, sized by the library's `fn_name`(*args)."""
+        ns = self.fn[fn_name](*args)
+        if ns < 0:
+            raise ArtError(f"{fn_name} failed with code {ns}: {self.last_error()}")
+        return self.scratch(key, ns, torch.float64)
+
+    @staticmethod
+    def _ptr(t, n):
+        """The device pointer of the optional per-slot tensor t (mostly the weights): NULL without it or without slots."""
+        return None if (t is None or n == 0) else t.data_ptr()
+
+    @staticmethod
+    def _chromatic_table(table):
+        """`table` as the contiguous float64 host array [nk, 4] of rows (k_j, c_j, z_j, 0) that the chromatic calls take."""
+        table = np.ascontiguousarray(table, dtype=np.float64)
+        if table.ndim != 2 or table.shape[1] != 4:
+            raise ValueError("the chromatic table must have rows (k_j, c_j, z_j, 0)")
+        return table
+
+    @staticmethod
+    def _quadric_desc(coefficients):
+        """The ArtQuadricDesc of ten coefficients (q[6], b[3], c: include/art_hip.h)."""
+        q = _abi.ArtQuadricDesc()
+        co = [float(v) for v in coefficients]
+        q.q[:], q.b[:], q.c = co[0:6], co[6:9], co[9]
+        return q
+
     # ------------------------------------------------------------------ entry points
     def _timed(self, call, sink="trace_events"):
         """Run one launch; when the sink list is set, bracket it with HIP events recorded on the launch stream."""
@@ -149,9 +177,7 @@ class HipBackend:
     def trace_quadric(self, desc, coefficients, view_in, view_out, n):
         """art_trace_quadric: `desc` (an ArtElementDesc with ART_FLAG_QUADRIC) reflects the bundle `view_in` off the quadric
         whose ten coefficients (q[6], b[3], c: include/art_hip.h) are `coefficients`."""
-        q = _abi.ArtQuadricDesc()
-        co = [float(v) for v in coefficients]
-        q.q[:], q.b[:], q.c = co[0:6], co[6:9], co[9]
+        q = self._quadric_desc(coefficients)
         sp = self.stream_ptr()
         self.check(self._timed(lambda: self.fn["art_trace_quadric"](C.byref(desc), C.byref(q), C.byref(view_in),
                                                                     C.byref(view_out), n, sp)), "art_trace_quadric")
@@ -160,9 +186,7 @@ class HipBackend:
         """art_trace_freeform: `desc` (an ArtElementDesc with ART_FLAG_FREEFORM) reflects the bundle `view_in` off the base
         quadric `coefficients` (q[6], b[3], c) carrying the figure `figure` = (device tensor of ART_ZERN_STRIDE doubles in
         the dense layout, radius, order): include/art_hip.h."""
-        q = _abi.ArtQuadricDesc()
-        co = [float(v) for v in coefficients]
-        q.q[:], q.b[:], q.c = co[0:6], co[6:9], co[9]
+        q = self._quadric_desc(coefficients)
         table, radius, order = figure
         if table.numel() < _abi.ART_ZERN_STRIDE:
             raise ValueError("trace_freeform: the figure table must hold ART_ZERN_STRIDE doubles")
@@ -315,9 +339,9 @@ class HipBackend:
         xy = [t.data_ptr() for t in XY] if (XY is not None and n > 0) else [None, None]
         sp, scratch = self.stream_ptr(), self._red_scratch()
         self.check(self._timed(lambda: self.fn["art_detector_readout"](
-            C.byref(ddesc), C.byref(view), None if (w is None or n == 0) else w.data_ptr(), n, float(centres[0]),
+            C.byref(ddesc), C.byref(view), self._ptr(w, n), n, float(centres[0]),
             float(centres[1]), float(centres[2]), p[0], p[1], p[2], xy[0], xy[1],
-            None if (opl is None or n == 0) else opl.data_ptr(), scratch.data_ptr(), out.data_ptr(), sp),
+            self._ptr(opl, n), scratch.data_ptr(), out.data_ptr(), sp),
             "readout_events"), "art_detector_readout")
         return out.cpu().numpy() if to_host else out
 
@@ -350,8 +374,8 @@ class HipBackend:
         else:
             accumulate = 1
         counts, wsums, totals = out
-        self.check(self.fn["art_histogram"](C.byref(hdesc), C.byref(view), None if (w is None or n == 0) else w.data_ptr(),
-                                            n, accumulate, counts.data_ptr(), None if wsums is None else wsums.data_ptr(),
+        self.check(self.fn["art_histogram"](C.byref(hdesc), C.byref(view), self._ptr(w, n), n, accumulate,
+                                            counts.data_ptr(), None if wsums is None else wsums.data_ptr(),
                                             totals.data_ptr(), self.stream_ptr()), "art_histogram")
         return counts, wsums, totals, shift
 
@@ -359,13 +383,9 @@ class HipBackend:
         """art_focal_field on the current stream: a new device complex128 tensor [planes, ny, nx] (scratch reused per
         stream)."""
         field = torch.empty((fdesc.planes, fdesc.ny, fdesc.nx), dtype=torch.complex128, device=self.device)
-        ns = self.fn["art_focal_scratch_doubles"](fdesc.nx, fdesc.ny, fdesc.planes, n)
-        if ns < 0:
-            raise ArtError(f"art_focal_scratch_doubles failed with code {ns}: {self.last_error()}")
-        scratch = self.scratch("focal", ns, torch.float64)
-        self.check(self.fn["art_focal_field"](C.byref(fdesc), C.byref(view), None if (w is None or n == 0) else w.data_ptr(),
-                                              n, scratch.data_ptr(), field.data_ptr(), self.stream_ptr()),
-                   "art_focal_field")
+        scratch = self._scratch_for("focal", "art_focal_scratch_doubles", fdesc.nx, fdesc.ny, fdesc.planes, n)
+        self.check(self.fn["art_focal_field"](C.byref(fdesc), C.byref(view), self._ptr(w, n), n, scratch.data_ptr(),
+                                              field.data_ptr(), self.stream_ptr()), "art_focal_field")
         return field
 
     def focal_spectrum(self, sdesc, view, w, n):
@@ -373,33 +393,23 @@ class HipBackend:
         reused per stream)."""
         f = sdesc.f
         field = torch.empty((f.planes, sdesc.nk, f.ny, f.nx), dtype=torch.complex128, device=self.device)
-        ns = self.fn["art_focal_spectrum_scratch_doubles"](f.nx, f.ny, f.planes, sdesc.nk, n)
-        if ns < 0:
-            raise ArtError(f"art_focal_spectrum_scratch_doubles failed with code {ns}: {self.last_error()}")
-        scratch = self.scratch("focal", ns, torch.float64)
-        self.check(self.fn["art_focal_spectrum"](C.byref(sdesc), C.byref(view), None if (w is None or n == 0) else
-                                                 w.data_ptr(), n, scratch.data_ptr(), field.data_ptr(),
-                                                 self.stream_ptr()), "art_focal_spectrum")
+        scratch = self._scratch_for("focal", "art_focal_spectrum_scratch_doubles", f.nx, f.ny, f.planes, sdesc.nk, n)
+        self.check(self.fn["art_focal_spectrum"](C.byref(sdesc), C.byref(view), self._ptr(w, n), n, scratch.data_ptr(),
+                                                 field.data_ptr(), self.stream_ptr()), "art_focal_spectrum")
         return field
 
     def focal_chromatic(self, desc, final_view, source_view, w, n, table):
         """art_focal_chromatic on the current stream: a new device complex128 tensor [planes, nk, ny, nx].  desc: an
         ArtFocalChromaticDesc (its nk is set here); table: host array [nk, 4] of rows (k_j, c_j, z_j, 0), uploaded here
         and validated by the library on this host copy; scratch reused per stream."""
-        table = np.ascontiguousarray(table, dtype=np.float64)
-        if table.ndim != 2 or table.shape[1] != 4:
-            raise ValueError("the chromatic table must have rows (k_j, c_j, z_j, 0)")
+        table = self._chromatic_table(table)
         f = desc.f
         desc.nk = nk = int(table.shape[0])
-        ns = self.fn["art_focal_chromatic_scratch_doubles"](f.nx, f.ny, f.planes, nk, n)
-        if ns < 0:
-            raise ArtError(f"art_focal_chromatic_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self._scratch_for("focal", "art_focal_chromatic_scratch_doubles", f.nx, f.ny, f.planes, nk, n)
         field = torch.empty((f.planes, nk, f.ny, f.nx), dtype=torch.complex128, device=self.device)
-        scratch = self.scratch("focal", ns, torch.float64)
         table_dev = self.from_numpy(table)
         self.check(self.fn["art_focal_chromatic"](C.byref(desc), C.byref(final_view), C.byref(source_view),
-                                                  None if (w is None or n == 0) else w.data_ptr(), n,
-                                                  table_dev.data_ptr(), table.ctypes.data_as(_abi.c_double_p),
+                                                  self._ptr(w, n), n, table_dev.data_ptr(), table.ctypes.data_as(_abi.c_double_p),
                                                   scratch.data_ptr(), field.data_ptr(), self.stream_ptr()),
                    "art_focal_chromatic")
         return field
@@ -412,13 +422,9 @@ class HipBackend:
         d.groups = int(groups)
         d.seg = seg.data_ptr()
         image = torch.empty((fdesc.planes, fdesc.ny, fdesc.nx), dtype=torch.float64, device=self.device)
-        ns = self.fn["art_focal_image_scratch_doubles"](fdesc.nx, fdesc.ny, fdesc.planes, d.groups, n)
-        if ns < 0:
-            raise ArtError(f"art_focal_image_scratch_doubles failed with code {ns}: {self.last_error()}")
-        scratch = self.scratch("focal", ns, torch.float64)
-        self.check(self.fn["art_focal_image"](C.byref(d), C.byref(view), None if (w is None or n == 0) else w.data_ptr(),
-                                              n, scratch.data_ptr(), image.data_ptr(), self.stream_ptr()),
-                   "art_focal_image")
+        scratch = self._scratch_for("focal", "art_focal_image_scratch_doubles", fdesc.nx, fdesc.ny, fdesc.planes, d.groups, n)
+        self.check(self.fn["art_focal_image"](C.byref(d), C.byref(view), self._ptr(w, n), n, scratch.data_ptr(),
+                                              image.data_ptr(), self.stream_ptr()), "art_focal_image")
         return image
 
     def _red_scratch(self):
@@ -426,7 +432,7 @@ class HipBackend:
 
     def detector_stats(self, alive, X, Y, opl, w, n, to_host=True):
         out = self.empty(16)      # n == 0: one workgroup with nothing to add leaves the reduction identities
-        ptr = lambda t: None if (t is None or n == 0) else t.data_ptr()
+        ptr = lambda t: self._ptr(t, n)
         if n == 0:
             alive = self.zeros(1, torch.uint8)
         self.check(self.fn["art_detector_stats"](alive.data_ptr(), ptr(X), ptr(Y), ptr(opl), ptr(w), n,
@@ -522,7 +528,7 @@ class HipBackend:
         the uint8 tensor `send` (art_pack_survivors); nothing returns to the host."""
         n = int(alive.numel())
         sc = self.scratch("compact", self.fn["art_compact_scratch_ints"](n), torch.int32)
-        ptr = lambda t: None if (t is None or n == 0) else t.data_ptr()
+        ptr = lambda t: self._ptr(t, n)
         self.check(self.fn["art_pack_survivors"](ptr(alive), n, ptr(X), ptr(Y), ptr(opl), ptr(number), int(first),
                                                  int(step), sc.data_ptr(), send.data_ptr(), int(send.numel()),
                                                  self.stream_ptr()), "art_pack_survivors")
@@ -579,11 +585,8 @@ class HipBackend:
         for k, j in enumerate(jobs):
             j.out = out.data_ptr() + 8 * _abi.ART_WAVEFRONT_DOUBLES * k
         arr = (_abi.ArtWavefrontJob * c)(*jobs)
-        ns = self.fn["art_wavefront_scratch_doubles"](arr, c)
-        if ns < 0:
-            raise ArtError(f"art_wavefront_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self._scratch_for("wavefront", "art_wavefront_scratch_doubles", arr, c)
         dev = self._upload_table(arr)
-        scratch = self.scratch("wavefront", ns, torch.float64)
         self.check(self.fn["art_wavefront"](dev.data_ptr(), arr, c, scratch.data_ptr(), self.stream_ptr()), "art_wavefront")
         return out
 
@@ -604,11 +607,8 @@ class HipBackend:
             off += C.sizeof(v)
         carr = (_abi.ArtCoating * max(len(coatings), 1))(*coatings)
         cdev = dev.data_ptr() + off if coatings else None
-        ns = self.fn["art_polarisation_scratch_doubles"](jarr, c)
-        if ns < 0:
-            raise ArtError(f"art_polarisation_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self._scratch_for("polarisation", "art_polarisation_scratch_doubles", jarr, c)
         jdev = self._upload_table(jarr)
-        scratch = self.scratch("polarisation", ns, torch.float64)
         self.check(self.fn["art_polarisation"](jdev.data_ptr(), jarr, c, cdev, carr, len(coatings), scratch.data_ptr(),
                                                self.stream_ptr()), "art_polarisation")
         return out
@@ -638,10 +638,7 @@ class HipBackend:
         f = vdesc.s.f
         field = torch.empty((f.planes, vdesc.s.nk, 3, f.ny, f.nx), dtype=torch.complex128, device=self.device)
         cdev, carr, marr = self.focal_vector_tables(vdesc, views, coatings, materials)
-        ns = self.fn["art_focal_vector_spectrum_scratch_doubles"](C.byref(vdesc))
-        if ns < 0:
-            raise ArtError(f"art_focal_vector_spectrum_scratch_doubles failed with code {ns}: {self.last_error()}")
-        scratch = self.scratch("focal vector", ns, torch.float64)
+        scratch = self._scratch_for("focal vector", "art_focal_vector_spectrum_scratch_doubles", C.byref(vdesc))
         self.check(self.fn["art_focal_vector_spectrum"](C.byref(vdesc), C.byref(views[vdesc.n_elems]), cdev, carr, marr,
                                                         scratch.data_ptr(), field.data_ptr(), self.stream_ptr()),
                    "art_focal_vector_spectrum")
@@ -652,18 +649,13 @@ class HipBackend:
         vcdesc: an ArtFocalVectorChromaticDesc (its v.s.nk is set here); views, coatings, materials as
         focal_vector_tables, one row of materials per row of the table; table: host array [nk, 4] of rows
         (k_j, c_j, z_j, 0), uploaded here and validated by the library on this host copy; scratch reused per stream."""
-        table = np.ascontiguousarray(table, dtype=np.float64)
-        if table.ndim != 2 or table.shape[1] != 4:
-            raise ValueError("the chromatic table must have rows (k_j, c_j, z_j, 0)")
+        table = self._chromatic_table(table)
         v = vcdesc.v
         v.s.nk = nk = int(table.shape[0])
         f = v.s.f
         cdev, carr, marr = self.focal_vector_tables(v, views, coatings, materials)
-        ns = self.fn["art_focal_vector_chromatic_scratch_doubles"](C.byref(vcdesc))
-        if ns < 0:
-            raise ArtError(f"art_focal_vector_chromatic_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self._scratch_for("focal vector", "art_focal_vector_chromatic_scratch_doubles", C.byref(vcdesc))
         field = torch.empty((f.planes, nk, 3, f.ny, f.nx), dtype=torch.complex128, device=self.device)
-        scratch = self.scratch("focal vector", ns, torch.float64)
         table_dev = self.from_numpy(table)
         self.check(self.fn["art_focal_vector_chromatic"](C.byref(vcdesc), C.byref(views[v.n_elems]), C.byref(views[0]),
                                                          cdev, carr, marr, table_dev.data_ptr(),

@@ -20,10 +20,6 @@ def _plt():
     return plt
 
 
-def _as_bundle(rays):
-    return rays if isinstance(rays, RayBundle) else RayBundle.from_ray_list(rays)
-
-
 def _sample_positions(m, cap=None):
     cap = cap or MAX_POINTS
     return np.arange(m) if m <= cap else np.unique(np.linspace(0, m - 1, cap).astype(np.int64))
@@ -58,7 +54,7 @@ def _ray_property(B, slots, which):
 def _getDetectorPoints(RayListAnalysed, Detector):
     """(x in um, y in um, spot diameter in mm, spot standard deviation in mm), ART/ModuleAnalysisAndPlots.py:28-58;
     the coordinate arrays hold the displayed sample, the two numbers describe all rays."""
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     d = _detector_sample(B, Detector, _sample_positions(len(B)))
     return d["x_um"], d["y_um"], d["size"], d["spot_sd"]
 
@@ -83,7 +79,7 @@ def _shift(moving, dist, step, key):
 
 def SpotDiagram(RayListAnalysed, Detector, DrawAiryAndFourier=False, ColorCoded=None):
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     NA = mp.ReturnNumericalAperture(B, 1)
     airy = mp.ReturnAiryRadius(B.wavelength, NA) * 1e3 if DrawAiryAndFourier else 0
     pos = _sample_positions(len(B))
@@ -181,7 +177,7 @@ def _draw_delay_graph(B, Detector, dist, DeltaFT, DrawAiryAndFourier, ColorCoded
 
 def DelayGraph(RayListAnalysed, Detector, DeltaFT, DrawAiryAndFourier=False, ColorCoded=None):
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     NA = mp.ReturnNumericalAperture(B, 1)
     pos = _sample_positions(len(B))
     state = {"dist": Detector.get_distance(), "det": Detector.copy_detector()}
@@ -285,7 +281,7 @@ def SpotImage(RayListAnalysed, Detector, Bins=200):
     """Image of the X-Y histogram of ALL rays on the detector (intensity, or counts without intensities), in µm about
     the bounding-box centre; left/right move the detector and re-bin."""
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     h, extent, size, spot_sd = _spot_image_data(B, Detector, Bins)
     plt.ion()
     fig, ax = plt.subplots()
@@ -324,7 +320,7 @@ def DelayProfile(RayListAnalysed, Detector, Bins=200):
     """Step plot of the delay histogram of ALL rays on the detector (fs about the mean path; intensity, or counts
     without intensities); left/right move the detector and re-bin."""
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     h, size, dur_sd = _delay_profile_data(B, Detector, Bins)
     plt.ion()
     fig, ax = plt.subplots()
@@ -368,7 +364,7 @@ def FocalSpot(RayListAnalysed, Detector, Size=None, Pixels=128, Log=False):
     """Image of the coherent focal intensity (Detector.get_FocalField) in µm, detector coordinates, with the Airy circle
     about the grid centre and the Strehl ratio in the title; left/right move the detector and re-sum."""
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     f, img, extent, size = _focal_spot_data(B, Detector, Size, Pixels, Log)
     airy = mp.ReturnAiryRadius(f.wavelength, mp.ReturnNumericalAperture(B, 1)) * 1e3
     cx, cy = 0.5 * (extent[0] + extent[1]), 0.5 * (extent[2] + extent[3])
@@ -403,7 +399,7 @@ def SourceImage(RayListAnalysed, Detector, RaysPerSource=None, Groups=None, Size
     (Detector.get_FocalImage, its Strehl ratio and rms widths in the title) and the fully coherent |get_FocalField|^2
     of the same bundle, each over its own maximum."""
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     g = Detector.get_FocalImage(B, RaysPerSource=RaysPerSource, Groups=Groups, Size=Size, Pixels=Pixels)
     centre = (0.5 * (g.x[0] + g.x[-1]), 0.5 * (g.y[0] + g.y[-1]))
     size = (max(g.x[-1] - g.x[0], np.finfo(float).tiny), max(g.y[-1] - g.y[0], np.finfo(float).tiny))
@@ -437,7 +433,7 @@ def ThroughFocus(RayListAnalysed, Detector, Shifts, Size=None, Pixels=64):
     """Strehl ratio and peak position (µm, detector coordinates) of the coherent focal field against the detector shift
     (mm, Detector.shiftByDistance's sign); all planes are summed in one device call."""
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     f = Detector.get_FocalField(B, Size=Size, Pixels=Pixels, Shifts=Shifts)
     plt.ion()
     fig, (a1, a2) = plt.subplots(2, 1, sharex=True)
@@ -459,7 +455,7 @@ def PulseAtFocus(RayListAnalysed, Detector, DeltaFT, Size=None, Pixels=64):
     I(Y, t) along its column (µm, fs), and the on-peak and pixel-integrated temporal profiles, each over its maximum,
     against the Fourier-limited Gaussian of DeltaFT centred on the peak."""
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     p = Detector.get_FocalPulse(B, DeltaFT, Size=Size, Pixels=Pixels)
     I = p.intensity[0]
     n, l, j = np.unravel_index(int(np.argmax(I)), I.shape)
@@ -541,7 +537,7 @@ def PulseThroughFocus(RayListAnalysed, Detector, DeltaFT, Shifts, Size=None, Pix
     """Space-time Strehl ratio and on-peak duration (fs) of the pulse against the detector shift (mm,
     Detector.shiftByDistance's sign); all planes and frequencies are summed in one device call."""
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     p = Detector.get_FocalPulse(B, DeltaFT, Size=Size, Pixels=Pixels, Shifts=Shifts)
     plt.ion()
     fig, (a1, a2) = plt.subplots(2, 1, sharex=True)
@@ -601,7 +597,7 @@ def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston
     chart of every term's rms contribution in waves; rms, rms at the best reference point and the Marechal Strehl ratio
     in the title.  Without a wavelength the numbers are in nm."""
     plt = _plt()
-    B = _as_bundle(RayListAnalysed)
+    B = RayBundle.of(RayListAnalysed)
     wf = Detector.get_Wavefront(B, Order=Order)
     scale, unit = (1.0 / wf.wavelength, "waves") if np.isfinite(wf.wavelength) else (1e6, "nm")
     img = wf.map(Pixels, remove=Remove) * scale
@@ -747,7 +743,7 @@ def render_scene(OpticalChain, EndDistance=None, maxRays=300, OEpoints=3000, dra
     segment end points per stage (source -> element 0, ..., last element -> EndDistance further), "optics": one
     (p, 3) lab-frame point cloud per optical element, "loops": their hole outlines as index loops, "EndDistance",
     "triangles": with draw_mesh, the surface mesh of every optic as index triples into its cloud}."""
-    history = [_as_bundle(OpticalChain.source_rays)] + [_as_bundle(b) for b in OpticalChain.get_output_rays()]
+    history = [RayBundle.of(OpticalChain.source_rays)] + [RayBundle.of(b) for b in OpticalChain.get_output_rays()]
     if EndDistance is None:
         EndDistance = float(np.linalg.norm(np.asarray(OpticalChain.source_rays[0].point, dtype=float)
                                            - np.asarray(OpticalChain.optical_elements[0].position, dtype=float)))

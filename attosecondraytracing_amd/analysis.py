@@ -95,7 +95,7 @@ def analyse(requests):
     modes = {"sums": _abi.ART_JOB_SUMS, "autoplace": _abi.ART_JOB_AUTOPLACE, "manual": _abi.ART_JOB_MANUAL}
     groups = {}
     for pos, (bundle, kind, arg) in enumerate(requests):
-        B = bundle if isinstance(bundle, RayBundle) else RayBundle.from_ray_list(bundle)
+        B = RayBundle.of(bundle)
         groups.setdefault((id(B.backend), B.n_slots), []).append((pos, B, modes[kind], arg))
     pending = []
     for (_, n), items in groups.items():

@@ -210,6 +210,11 @@ class RayBundle:
             b.path_head = np.array([r.path for r in rays], dtype=np.float64)
         return b
 
+    @classmethod
+    def of(cls, rays, backend=None):
+        """`rays` itself when it is a RayBundle already, else the bundle of that list of Ray."""
+        return rays if isinstance(rays, RayBundle) else cls.from_ray_list(rays, backend)
+
     def _share_grouping(self, other):
         """Bundles over the same slots keep ExtendedSource's rays_per_source (image.py: the incoherent groups)."""
         if hasattr(self, "rays_per_source"):

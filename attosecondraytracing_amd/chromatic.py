@@ -80,17 +80,21 @@ def gaussian_divergence(Waist):
     return divergence
 
 
-class ChromaticFocalPulse(pulse.FocalPulse):
-    """pulse.FocalPulse of a chromatic source, and: divergence [J] (Theta_j, rad; inf without apodisation), position [J]
-    (z_j, mm), axis (the unit axis a), best_focus [J] (the value of Shifts with the largest |E_j| at the pixel nearest
-    the grid's centre; NaN for a frequency of weight 0 and without alive rays).  amplitude_sum is the ideal peak of the
-    same apodised source, sum_j |g_j| S_j / sum_j |g_j| with S_j = sum over the alive rays of sqrt(w_r) exp(-u_r c_j), so
-    `strehl` stays "against a perfect focus of this source".  The slices of `spectrum` at frequencies of weight 0 are 0."""
+class _ChromaticSource:
+    """What a chromatic source adds to a pulse: divergence, position, axis, best_focus (see ChromaticFocalPulse)."""
 
     def __init__(self, divergence, position, axis, best_focus, *args):
         super().__init__(*args)
         self.divergence, self.position = np.asarray(divergence, dtype=float), np.asarray(position, dtype=float)
         self.axis, self.best_focus = np.asarray(axis, dtype=float), np.asarray(best_focus, dtype=float)
+
+
+class ChromaticFocalPulse(_ChromaticSource, pulse.FocalPulse):
+    """pulse.FocalPulse of a chromatic source, and: divergence [J] (Theta_j, rad; inf without apodisation), position [J]
+    (z_j, mm), axis (the unit axis a), best_focus [J] (the value of Shifts with the largest |E_j| at the pixel nearest
+    the grid's centre; NaN for a frequency of weight 0 and without alive rays).  amplitude_sum is the ideal peak of the
+    same apodised source, sum_j |g_j| S_j / sum_j |g_j| with S_j = sum over the alive rays of sqrt(w_r) exp(-u_r c_j), so
+    `strehl` stays "against a perfect focus of this source".  The slices of `spectrum` at frequencies of weight 0 are 0."""
 
 
 def _per_frequency(f, omega, name, positive):
@@ -178,60 +182,56 @@ def chromatic_focal_pulse(det, RayList, SourceRays, DeltaFT, Divergence=None, Po
     _check_source_args(Divergence, Position)
     if SourceRays is None:
         raise TypeError("SourceRays is required: the source bundle the rays were traced from")
-    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
-    S = SourceRays if isinstance(SourceRays, RayBundle) else RayBundle.from_ray_list(SourceRays)
+    B, S = RayBundle.of(RayList), RayBundle.of(SourceRays)
     if getattr(B, "grooves", None) is not None or getattr(S, "grooves", None) is not None:
         raise NotImplementedError("get_ChromaticFocalPulse: these rays crossed a grating, so one bundle no longer serves "
                                   "all frequencies; trace one bundle per wavelength with OpticalChain.get_SpectralRays")
     if S.n_slots != B.n_slots:
         raise ValueError(f"SourceRays has {S.n_slots} slots and the rays at focus {B.n_slots}: the two bundles must be "
                          "slot-aligned (the chain's history is)")
-    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
-    T, omega0, m, dw, omega, g, gsum = pulse.spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, s)
-    J = len(omega)
-    theta, z, axis, c, kj = _source_model(Divergence, Position, Axis, S, omega, dw)
+    setup = pulse.PulseSetup(det, B, DeltaFT, TimeWindow, Nt, Spectrum, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+
+    def call(axis, table, kj):
+        d = _abi.ArtFocalChromaticDesc()
+        d.f = setup.fd
+        d.axis[:] = [float(a) for a in axis]
+        return B.backend.focal_chromatic(d, B.view(), S.view(), B.intensity, B.n_slots, table)     # [P, kept, ny, nx]
+
+    return _chromatic_pulse(ChromaticFocalPulse, setup, B, S, Divergence, Position, Axis, call, torch.abs)
+
+
+def _chromatic_pulse(cls, setup, B, S, Divergence, Position, Axis, call, on_axis):
+    """What the two chromatic drivers share once their own checks have passed and the PulseSetup stands: the source
+    model, the mask `keep` of the frequencies whose weight is not 0, the table of rows (k_j, c_j, z_j, 0) for those, the
+    driver's device call(axis, table, kept k_j) -> field [P, kept, *rest], the Fourier sum, amplitude_sum and best_focus.
+    on_axis maps the field at the centre pixel, [P, kept] or [P, kept, 3], to the measure [P, kept] whose argmax over the
+    planes is best_focus."""
+    g = setup.g
+    theta, z, axis, c, kj = _source_model(Divergence, Position, Axis, S, setup.omega, setup.dw)
     keep = np.abs(g) > 0
     table = np.stack([kj[keep], c[keep], z[keep], np.zeros(int(keep.sum()))], axis=1)
-    d = _abi.ArtFocalChromaticDesc()
-    d.f = fd
-    for i in range(3):
-        d.axis[i] = axis[i]
-    field = B.backend.focal_chromatic(d, B.view(), S.view(), B.intensity, B.n_slots, table)     # [P, kept, ny, nx]
-    P, Jk, ny, nx = field.shape
-    dev = field.device
-    kept = field * torch.as_tensor(g[keep], device=dev)[None, :, None, None]
-    if Jk == J:
-        spectrum = kept
-    else:
-        spectrum = torch.zeros((P, J, ny, nx), dtype=kept.dtype, device=dev)
-        spectrum[:, torch.as_tensor(np.flatnonzero(keep), device=dev)] = kept
-    t, M = pulse.time_axis(T, Nt, m, dw, gsum)                                # M [Nt, J]
-    envelope = torch.matmul(torch.as_tensor(np.ascontiguousarray(M[:, keep]), device=dev), kept.reshape(P, Jk, ny * nx))
+    field = call(axis, table, kj[keep])
+    spectrum, envelope = setup.fourier_sum(field, keep)
     if Divergence is None:
         amplitude_sum = focal.amplitude_sum(B)          # every S_j is the plain sum
     else:
         alive = B.alive[:B.n_slots] != 0
         Sj = apodised_amplitude_sums(B, source_u(S, axis, alive), c[keep])
-        amplitude_sum = float((np.abs(g[keep]) * Sj).sum() / gsum)
-    best = np.full(J, np.nan)
+        amplitude_sum = float((np.abs(g[keep]) * Sj).sum() / setup.gsum)
+    best = np.full(len(g), np.nan)
     if amplitude_sum > 0:
-        on_axis = torch.abs(field[:, :, (ny - 1) // 2, (nx - 1) // 2]).cpu().numpy()       # [P, kept]
-        best[keep] = np.asarray(shifts, dtype=float)[np.argmax(on_axis, axis=0)]
-    return ChromaticFocalPulse(theta, z, axis, best, spectrum, envelope.reshape(P, Nt, ny, nx), omega, omega0, g, t, T, x,
-                               y, shifts, DeltaFT, wavelength, ref, amplitude_sum)
+        ny, nx = field.shape[-2:]
+        measure = on_axis(field[..., (ny - 1) // 2, (nx - 1) // 2]).cpu().numpy()
+        best[keep] = np.asarray(setup.shifts, dtype=float)[np.argmax(measure, axis=0)]
+    return cls(theta, z, axis, best, setup, spectrum, envelope, amplitude_sum)
 
 
-class ChromaticVectorFocalPulse(vector_pulse.VectorFocalPulse):
+class ChromaticVectorFocalPulse(_ChromaticSource, vector_pulse.VectorFocalPulse):
     """vector_pulse.VectorFocalPulse of a chromatic source, and: divergence [J], position [J], axis as in
     ChromaticFocalPulse; best_focus [J]: the value of Shifts with the largest sum_c |F_c|^2 at the pixel nearest the
     grid's centre (NaN for a frequency of weight 0 and without alive rays).  amplitude_sum is ChromaticFocalPulse's, the
     ideal peak of the same apodised source, so `strehl` reads "against a perfect focus of this apodised source behind
     lossless mirrors".  The slices of `spectrum` at frequencies of weight 0 are 0."""
-
-    def __init__(self, divergence, position, axis, best_focus, *args):
-        super().__init__(*args)
-        self.divergence, self.position = np.asarray(divergence, dtype=float), np.asarray(position, dtype=float)
-        self.axis, self.best_focus = np.asarray(axis, dtype=float), np.asarray(best_focus, dtype=float)
 
 
 def vector_chromatic_focal_pulse(chain, Coatings, Detector, DeltaFT, Polarisation, Divergence=None, Position=None, Axis=None,
@@ -246,39 +246,13 @@ def vector_chromatic_focal_pulse(chain, Coatings, Detector, DeltaFT, Polarisatio
     _check_source_args(Divergence, Position)
     coats, P, bundles = vector_pulse._setup(chain, Coatings, Detector, Polarisation)
     S, B = bundles[0], bundles[-1]
-    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(Detector, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
-    T, omega0, m, dw, omega, g, gsum = pulse.spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, s)
+    setup = pulse.PulseSetup(Detector, B, DeltaFT, TimeWindow, Nt, Spectrum, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
     vector_pulse._check_state(bundles, P)
-    J = len(omega)
-    theta, z, axis, c, kj = _source_model(Divergence, Position, Axis, S, omega, dw)
-    keep = np.abs(g) > 0
-    table = np.stack([kj[keep], c[keep], z[keep], np.zeros(int(keep.sum()))], axis=1)
-    sd = _abi.ArtFocalSpectrumDesc()             # (k_0 and dk are checked by the library, not used: the table holds the k_j)
-    sd.f = fd
-    sd.f.k = omega[0] / C_MM_PER_FS
-    sd.dk = dw / C_MM_PER_FS
-    sd.nk = len(table)
-    field = vector_pulse._vector_spectrum(bundles, coats, P, sd, 2 * math.pi / kj[keep], ScratchBytes,
-                                          chromatic=(axis, table))                    # [P, kept, 3, ny, nx]
-    Pn, Jk, _, ny, nx = field.shape
-    dev = field.device
-    kept = field * torch.as_tensor(g[keep], device=dev)[None, :, None, None, None]
-    if Jk == J:
-        spectrum = kept
-    else:
-        spectrum = torch.zeros((Pn, J, 3, ny, nx), dtype=kept.dtype, device=dev)
-        spectrum[:, torch.as_tensor(np.flatnonzero(keep), device=dev)] = kept
-    t, M = pulse.time_axis(T, Nt, m, dw, gsum)                                # M [Nt, J]
-    envelope = torch.matmul(torch.as_tensor(np.ascontiguousarray(M[:, keep]), device=dev), kept.reshape(Pn, Jk, 3 * ny * nx))
-    if Divergence is None:
-        amplitude_sum = focal.amplitude_sum(B)          # every S_j is the plain sum
-    else:
-        alive = B.alive[:B.n_slots] != 0
-        Sj = apodised_amplitude_sums(B, source_u(S, axis, alive), c[keep])
-        amplitude_sum = float((np.abs(g[keep]) * Sj).sum() / gsum)
-    best = np.full(J, np.nan)
-    if amplitude_sum > 0:
-        on_axis = (torch.abs(field[:, :, :, (ny - 1) // 2, (nx - 1) // 2]) ** 2).sum(dim=2).cpu().numpy()   # [P, kept]
-        best[keep] = np.asarray(shifts, dtype=float)[np.argmax(on_axis, axis=0)]
-    return ChromaticVectorFocalPulse(theta, z, axis, best, spectrum, envelope.reshape(Pn, Nt, 3, ny, nx), omega, omega0, g,
-                                     t, T, x, y, shifts, DeltaFT, wavelength, ref, amplitude_sum)
+
+    def call(axis, table, kj):
+        sd = setup.spectrum_desc(len(table))     # (k_0 and dk are checked by the library, not used: the table holds the k_j)
+        return vector_pulse._vector_spectrum(bundles, coats, P, sd, 2 * math.pi / kj, ScratchBytes,
+                                             chromatic=(axis, table))                 # [P, kept, 3, ny, nx]
+
+    return _chromatic_pulse(ChromaticVectorFocalPulse, setup, B, S, Divergence, Position, Axis, call,
+                            lambda f: (torch.abs(f) ** 2).sum(dim=2))

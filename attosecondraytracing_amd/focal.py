@@ -135,7 +135,7 @@ def focal_field(det, RayList, Size=None, Pixels=128, Centre=None, Shifts=None, W
     (get_PointList2DCentre's), Size to 16 Airy radii (ReturnAiryRadius(wavelength, ReturnNumericalAperture)), Shifts to
     (0,), Wavelength to the bundle's, RefPath to the mean optical path of the alive rays (what get_Delays subtracts).
     All planes are summed in one device call."""
-    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+    B = RayBundle.of(RayList)
     fd, x, y, shifts, wavelength, ref, _ = focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
     view, _keep = B.phase_path_view(wavelength)
     field = B.backend.focal_field(fd, view, B.intensity, B.n_slots)

@@ -67,7 +67,7 @@ class SceneProgram:
         from . import _abi
         from .bundle import RayBundle
         self._mp, self._abi = mp, _abi
-        self.sources = [mp._as_bundle(s) for s in sources]
+        self.sources = [RayBundle.of(s) for s in sources]
         self.c, self.m = len(self.sources), len(element_lists[0])
         self.n = self.sources[0].n_slots
         self.be = self.sources[0].backend

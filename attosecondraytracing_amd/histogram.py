@@ -73,10 +73,6 @@ def per_axis_ranges(Range, ndim, default):
     return [resolve_range(*r) for r in Range]
 
 
-def as_bundle(rays):
-    return rays if isinstance(rays, RayBundle) else RayBundle.from_ray_list(rays)
-
-
 def bin_bundle(B, desc, axes, bins, ranges):
     """Fill desc's axes, bins and ranges, bin the bundle on its backend, read the result back."""
     desc.ndim = len(axes)
@@ -95,7 +91,7 @@ def detector_histogram(det, RayList, Axes=("X", "Y"), Bins=100, Range=None):
     Axes = (Axes,) if isinstance(Axes, str) else tuple(Axes)
     if not 1 <= len(Axes) <= 3 or any(a not in _DETECTOR_AXES for a in Axes):
         raise ValueError('Axes: one to three of "X", "Y", "Delay"')
-    B = as_bundle(RayList)
+    B = RayBundle.of(RayList)
     s = det.readout(B, store=False, lite=True)["stats"]
     centre = s[1] / s[0] if s[0] > 0 else 0.0
     lims = {"X": (s[2], s[3]), "Y": (s[4], s[5]),
@@ -115,7 +111,7 @@ def spectrometer_histogram(det, bundles, Bins=200, Range=None):
     first bundle's bins, one fixed-point shift for all of them, so the sum is exact.  Range defaults to the joint
     bounding box of the alive rays."""
     import torch
-    Bs = [as_bundle(b) for b in bundles]
+    Bs = [RayBundle.of(b) for b in bundles]
     if not Bs:
         raise ValueError("no bundle to bin")
     stats = [det.readout(B, store=False, lite=True)["stats"] for B in Bs]
@@ -149,7 +145,7 @@ def footprint(oe, RayList, Bins=100, Range=None):
     """OpticalChain.get_Footprint: the hit points on optical element `oe` in its support frame, fwd (P - position)
     (MirrorProjection's coordinates), binned over +-_CircumRect()/2 by default."""
     from . import ModuleGeometry as mgeo
-    B = as_bundle(RayList)
+    B = RayBundle.of(RayList)
     half = np.asarray(oe.type.support._CircumRect(), dtype=float) / 2
     ranges = per_axis_ranges(Range, 2, lambda k: (-half[k], half[k]))
     fwd, _ = mgeo.frame_maps(oe.normal, oe.majoraxis)

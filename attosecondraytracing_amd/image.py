@@ -111,7 +111,7 @@ def focal_image(det, RayList, RaysPerSource=None, Groups=None, Size=None, Pixels
     """Detector.get_FocalImage (see the module's docstring).  The grid, Centre, Size, Shifts, Wavelength and RefPath
     resolve as in focal.focal_field; the groups as in segments.  All groups and planes are summed in one device call."""
     import torch
-    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
+    B = RayBundle.of(RayList)
     seg, groups = segments(B, RaysPerSource, Groups)
     fd, x, y, shifts, wavelength, ref, _ = focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
     if groups == 0:                 # no slot: one empty group for the device

@@ -85,18 +85,27 @@ class FocalPulse:
     rays every metric is NaN and the fields are 0.  Also: omega0, weights (g [J]), time_window (T), delta_ft,
     wavelength, ref_path, amplitude_sum."""
 
-    def __init__(self, spectrum, envelope, omega, omega0, weights, t, time_window, x, y, shifts, delta_ft, wavelength,
-                 ref_path, amplitude_sum):
-        self.spectrum, self.envelope = spectrum, envelope
-        self.omega, self.omega0, self.weights = omega, float(omega0), weights
-        self.t, self.time_window = t, float(time_window)
-        self.x, self.y = x, y
-        self.shifts = np.asarray(shifts, dtype=float)
-        self.delta_ft, self.wavelength = float(delta_ft), float(wavelength)
-        self.ref_path, self.amplitude_sum = float(ref_path), float(amplitude_sum)
-        self.intensity = np.abs(envelope.cpu().numpy()) ** 2
-        (self.strehl, self.peak, self.duration, self.profile, self.duration_integrated, self.fluence,
-         self.arrival) = pulse_metrics(self.intensity, t, x, y, self.time_window / len(t), self.amplitude_sum)
+    def __init__(self, setup, spectrum, envelope, amplitude_sum):
+        fill_pulse(self, setup, spectrum, envelope, amplitude_sum, lambda parts: parts)
+
+
+def fill_pulse(p, setup, spectrum, envelope, amplitude_sum, intensity_of):
+    """The constructor FocalPulse and vector_pulse.VectorFocalPulse share: sets every attribute of FocalPulse's docstring
+    on p from the PulseSetup, the device tensors and amplitude_sum; intensity_of maps |envelope|^2 (numpy, the envelope's
+    shape) to the intensity [P, Nt, ny, nx].  Returns (|envelope|^2, dt)."""
+    p.spectrum, p.envelope = spectrum, envelope
+    p.omega, p.omega0, p.weights = setup.omega, float(setup.omega0), setup.g
+    p.t, p.time_window = setup.t, float(setup.T)
+    p.x, p.y = setup.x, setup.y
+    p.shifts = np.asarray(setup.shifts, dtype=float)
+    p.delta_ft, p.wavelength = float(setup.DeltaFT), float(setup.wavelength)
+    p.ref_path, p.amplitude_sum = float(setup.ref), float(amplitude_sum)
+    parts = np.abs(envelope.cpu().numpy()) ** 2
+    p.intensity = intensity_of(parts)
+    dt = p.time_window / len(p.t)
+    (p.strehl, p.peak, p.duration, p.profile, p.duration_integrated, p.fluence,
+     p.arrival) = pulse_metrics(p.intensity, p.t, p.x, p.y, dt, p.amplitude_sum)
+    return parts, dt
 
 
 def pulse_metrics(I, t, x, y, dt, amplitude_sum):
@@ -162,10 +171,53 @@ def spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, stats):
     return T, omega0, m, dw, omega, g, gsum
 
 
-def time_axis(T, Nt, m, dw, gsum):
-    """(t [Nt], M [Nt, J]): the samples of [-T/2, T/2) and the matrix of the Fourier sum over the offsets m."""
-    t = -0.5 * T + np.arange(Nt) * (T / Nt)
-    return t, np.exp(-1j * (m * dw)[None, :] * t[:, None]) / gsum
+class PulseSetup:
+    """What the four pulse-at-focus drivers (focal_pulse here, vector_pulse.vector_focal_pulse and the two of
+    chromatic.py) share: get_FocalField's arguments resolved by focal.focal_desc for the bundle B on det (fd, x, y,
+    shifts, wavelength, ref), the frequency grid and weights of spectral_setup (T, omega0, m, dw, omega, g, gsum), the
+    samples t [Nt] of [-T/2, T/2) and Nt, DeltaFT as check_pulse_args returned them.  A driver builds one after its own
+    argument checks, hands spectrum_desc() or a table of its own to its backend call and gives the field to fourier_sum."""
+
+    def __init__(self, det, B, DeltaFT, TimeWindow, Nt, Spectrum, Size, Pixels, Centre, Shifts, Wavelength, RefPath):
+        self.fd, self.x, self.y, self.shifts, self.wavelength, self.ref, s = \
+            focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+        self.T, self.omega0, self.m, self.dw, self.omega, self.g, self.gsum = \
+            spectral_setup(self.wavelength, DeltaFT, TimeWindow, Spectrum, s)
+        self.Nt, self.DeltaFT = Nt, DeltaFT
+        self.t = -0.5 * self.T + np.arange(Nt) * (self.T / Nt)
+
+    def spectrum_desc(self, nk=None):
+        """The ArtFocalSpectrumDesc of the grid: k_0 = omega_0 / c, dk = dw / c and nk wavenumbers (default: all J)."""
+        sd = _abi.ArtFocalSpectrumDesc()
+        sd.f = self.fd
+        sd.f.k = self.omega[0] / C_MM_PER_FS
+        sd.dk = self.dw / C_MM_PER_FS
+        sd.nk = len(self.omega) if nk is None else nk
+        return sd
+
+    def fourier_sum(self, field, keep=None):
+        """(spectrum [P, J, *rest], envelope [P, Nt, *rest]) of the device field [P, Jk, *rest] the backend returned, rest
+        = (ny, nx) or (3, ny, nx): the field times the weights g, and the Fourier sum of that over the frequencies.
+        keep=None means that EVERY frequency went to the device, those of weight 0 included (Jk = J); the achromatic
+        drivers (focal_pulse, vector_focal_pulse) pass that.  Only the chromatic drivers drop the frequencies of weight
+        0: they pass keep, the boolean mask [J] of the Jk frequencies in the call, and the slices of spectrum at the
+        others are 0."""
+        import torch
+        g = self.g if keep is None else self.g[keep]
+        P, Jk, rest = field.shape[0], field.shape[1], tuple(field.shape[2:])
+        dev = field.device
+        kept = field * torch.as_tensor(g, device=dev)[(None, slice(None)) + (None,) * len(rest)]
+        if Jk == len(self.omega):
+            spectrum = kept
+        else:
+            spectrum = torch.zeros((P, len(self.omega)) + rest, dtype=kept.dtype, device=dev)
+            spectrum[:, torch.as_tensor(np.flatnonzero(keep), device=dev)] = kept
+        # (the matrix of the Fourier sum, [Nt, J], is formed here, on the host, while the device works on the field)
+        M = np.exp(-1j * (self.m * self.dw)[None, :] * self.t[:, None]) / self.gsum
+        if keep is not None:
+            M = np.ascontiguousarray(M[:, keep])
+        envelope = torch.matmul(torch.as_tensor(M, device=dev), kept.reshape(P, Jk, -1))
+        return spectrum, envelope.reshape((P, self.Nt) + rest)
 
 
 def focal_pulse(det, RayList, DeltaFT, Size=None, Pixels=64, Centre=None, Shifts=None, Wavelength=None, RefPath=None,
@@ -175,20 +227,8 @@ def focal_pulse(det, RayList, DeltaFT, Size=None, Pixels=64, Centre=None, Shifts
     default spectrum; Spectrum: a callable omega (rad/fs, array) -> complex amplitude that replaces the default
     Gaussian (a chirp is a quadratic phase); TimeWindow: T (fs), default 16 DeltaFT + 4 (max opl - min opl) / c over
     the alive rays; Times: samples of [-T/2, T/2).  All wavenumbers and planes are summed in one device call."""
-    import torch
     DeltaFT, TimeWindow, Nt = check_pulse_args(DeltaFT, TimeWindow, Times, Spectrum)
-    B = RayList if isinstance(RayList, RayBundle) else RayBundle.from_ray_list(RayList)
-    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(det, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
-    T, omega0, m, dw, omega, g, gsum = spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, s)
-    sd = _abi.ArtFocalSpectrumDesc()
-    sd.f = fd
-    sd.f.k = omega[0] / C_MM_PER_FS
-    sd.dk = dw / C_MM_PER_FS
-    sd.nk = len(omega)
-    field = B.backend.focal_spectrum(sd, B.view(), B.intensity, B.n_slots)
-    P, J, ny, nx = field.shape
-    spectrum = field * torch.as_tensor(g, device=field.device)[None, :, None, None]
-    t, M = time_axis(T, Nt, m, dw, gsum)                                      # M [Nt, J]
-    envelope = torch.matmul(torch.as_tensor(M, device=field.device), spectrum.reshape(P, J, ny * nx))
-    return FocalPulse(spectrum, envelope.reshape(P, Nt, ny, nx), omega, omega0, g, t, T, x, y, shifts, DeltaFT,
-                      wavelength, ref, focal.amplitude_sum(B))
+    B = RayBundle.of(RayList)
+    setup = PulseSetup(det, B, DeltaFT, TimeWindow, Nt, Spectrum, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
+    field = B.backend.focal_spectrum(setup.spectrum_desc(), B.view(), B.intensity, B.n_slots)
+    return FocalPulse(setup, *setup.fourier_sum(field), focal.amplitude_sum(B))

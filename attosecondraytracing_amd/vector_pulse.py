@@ -36,21 +36,9 @@ class VectorFocalPulse:
     share of the fluence in c = 2 (NaN without fluence).  Also omega0, weights, time_window, x, y, shifts, delta_ft,
     wavelength, ref_path, amplitude_sum, as in pulse.FocalPulse."""
 
-    def __init__(self, spectrum, envelope, omega, omega0, weights, t, time_window, x, y, shifts, delta_ft, wavelength,
-                 ref_path, amplitude_sum):
-        self.spectrum, self.envelope = spectrum, envelope
-        self.omega, self.omega0, self.weights = omega, float(omega0), weights
-        self.t, self.time_window = t, float(time_window)
-        self.x, self.y = x, y
-        self.shifts = np.asarray(shifts, dtype=float)
-        self.delta_ft, self.wavelength = float(delta_ft), float(wavelength)
-        self.ref_path, self.amplitude_sum = float(ref_path), float(amplitude_sum)
-        parts = np.abs(envelope.cpu().numpy()) ** 2                     # [P, Nt, 3, ny, nx]
-        self.intensity = parts.sum(axis=2)
-        dt = self.time_window / len(t)
-        (self.strehl, self.peak, self.duration, self.profile, self.duration_integrated, self.fluence,
-         self.arrival) = pulse.pulse_metrics(self.intensity, t, x, y, dt, self.amplitude_sum)
-        total = self.fluence.sum(axis=(1, 2))
+    def __init__(self, setup, spectrum, envelope, amplitude_sum):
+        parts, dt = pulse.fill_pulse(self, setup, spectrum, envelope, amplitude_sum, lambda parts: parts.sum(axis=2))
+        total = self.fluence.sum(axis=(1, 2))                           # (parts: [P, Nt, 3, ny, nx])
         with np.errstate(invalid="ignore", divide="ignore"):
             self.longitudinal = np.where(total > 0, parts[:, :, 2].sum(axis=(1, 2, 3)) * dt / total, np.nan)
 
@@ -146,26 +134,15 @@ def _check_state(bundles, P):
 def vector_focal_pulse(chain, Coatings, Detector, DeltaFT, Polarisation, Size=None, Pixels=64, Centre=None, Shifts=None,
                        Wavelength=None, RefPath=None, Spectrum=None, TimeWindow=None, Times=256, ScratchBytes=None):
     """OpticalChain.get_FocalPulse (see the module's docstring and pulse.focal_pulse for the shared arguments)."""
-    import torch
     DeltaFT, TimeWindow, Nt = pulse.check_pulse_args(DeltaFT, TimeWindow, Times, Spectrum)
     coats, P, bundles = _setup(chain, Coatings, Detector, Polarisation)
     B = bundles[-1]
-    fd, x, y, shifts, wavelength, ref, s = focal.focal_desc(Detector, B, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
-    T, omega0, m, dw, omega, g, gsum = pulse.spectral_setup(wavelength, DeltaFT, TimeWindow, Spectrum, s)
+    setup = pulse.PulseSetup(Detector, B, DeltaFT, TimeWindow, Nt, Spectrum, Size, Pixels, Centre, Shifts, Wavelength, RefPath)
     _check_state(bundles, P)
-    sd = _abi.ArtFocalSpectrumDesc()
-    sd.f = fd
-    sd.f.k = omega[0] / pulse.C_MM_PER_FS
-    sd.dk = dw / pulse.C_MM_PER_FS
-    sd.nk = len(omega)
+    sd = setup.spectrum_desc()
     k = sd.f.k + np.arange(sd.nk) * sd.dk                  # (the device's k_j)
     field = _vector_spectrum(bundles, coats, P, sd, 2 * math.pi / k, ScratchBytes)
-    Pn, J, _, ny, nx = field.shape
-    spectrum = field * torch.as_tensor(g, device=field.device)[None, :, None, None, None]
-    t, M = pulse.time_axis(T, Nt, m, dw, gsum)
-    envelope = torch.matmul(torch.as_tensor(M, device=field.device), spectrum.reshape(Pn, J, 3 * ny * nx))
-    return VectorFocalPulse(spectrum, envelope.reshape(Pn, Nt, 3, ny, nx), omega, omega0, g, t, T, x, y, shifts, DeltaFT,
-                            wavelength, ref, focal.amplitude_sum(B))
+    return VectorFocalPulse(setup, *setup.fourier_sum(field), focal.amplitude_sum(B))
 
 
 def vector_focal_field(chain, Coatings, Detector, Polarisation, Size=None, Pixels=128, Centre=None, Shifts=None,

@@ -213,7 +213,7 @@ def wavefronts(requests):
     items = []
     for B, det, kw in requests:
         p = resolve(**(kw or {}))
-        B = B if isinstance(B, RayBundle) else RayBundle.from_ray_list(B)
+        B = RayBundle.of(B)
         det._iscomplete()
         if p["wavelength"] is None:
             p["wavelength"] = B.wavelength

@@ -122,6 +122,19 @@ def test_spectrum_slices_are_focal_fields_with_the_weights(twin):
         assert np.abs(p.spectrum[:, j].numpy() - p.weights[j] * f.field.numpy()).max() <= 1e-9 * f.amplitude_sum
 
 
+def test_frequencies_of_weight_zero_still_reach_the_backend(twin):
+    """Only the chromatic drivers leave frequencies of weight 0 out of the device call: get_FocalPulse sends them all."""
+    B = fc.converging_bundle(12, 0.05, 2.0, wavelength=5e-5, backend=twin)
+    p = _detector().get_FocalPulse(B, 0.5, Spectrum=lambda w: np.where(np.arange(len(w)) % 3 == 0, 0.0, 1.0), Size=0.004,
+                                   Pixels=3, Centre=(0.0, 0.0), RefPath=2.0, TimeWindow=6.0, Times=8)
+    J = len(p.omega)
+    zero = p.weights == 0
+    assert twin.last_spectrum.nk == J and zero.sum() == (J + 2) // 3 and J > 3
+    sp = p.spectrum.numpy()
+    assert sp.shape == (1, J, 3, 3) and p.envelope.shape == (1, 8, 3, 3)
+    assert not sp[:, zero].any() and np.abs(sp[:, ~zero]).max(axis=(0, 2, 3)).min() > 0
+
+
 @pytest.mark.parametrize("kw, match", [
     (dict(TimeWindow=4000.0), "wavenumbers"), (dict(DeltaFT=1e-3), "wavenumbers|too short"),
     (dict(Wavelength=1e-3, DeltaFT=1.0), "too short"),

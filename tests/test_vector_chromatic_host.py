@@ -76,7 +76,8 @@ class NumpyVectorBackend(TwinBackend):
 
     def focal_vector_spectrum(self, vdesc, views, coatings, materials):
         self.calls["vector"] += 1
-        k = vdesc.s.f.k + np.arange(vdesc.s.nk) * vdesc.s.dk
+        self.last_vector_nk, self.last_vector_materials = int(vdesc.s.nk), np.array(materials, dtype=float)
+        k =vdesc.s.f.k + np.arange(vdesc.s.nk) * vdesc.s.dk
         return self._vector(vdesc, views, materials, [0.0, 0.0, 1.0], np.stack([k, 0 * k, 0 * k, 0 * k], axis=1))
 
     def focal_vector_chromatic(self, vcdesc, views, coatings, materials, table):
@@ -160,6 +161,24 @@ def test_only_the_kept_frequencies_reach_the_backend(twin, setup):
     chain.get_ChromaticFocalPulse(D, 0.3, Coatings=narrow, Polarisation=P, Spectrum=_comb(), **KW)
     with pytest.raises(ValueError, match="outside the material's table"):
         chain.get_FocalPulse(narrow, D, 0.3, P, Spectrum=_comb(), **KW)
+
+
+def test_get_FocalPulse_sends_the_frequencies_of_weight_zero_too(twin, setup):
+    """Only the chromatic drivers leave frequencies out: behind the same comb get_FocalPulse sends the whole grid."""
+    chain, D, coat = setup
+    before = dict(twin.calls)
+    p = chain.get_FocalPulse(coat, D, 0.3, P, Spectrum=_comb(), Size=2e-3, Pixels=3, TimeWindow=4.0, Times=8)
+    assert twin.calls == dict(before, vector=before["vector"] + 1)
+    J = len(p.omega)
+    zero = p.weights == 0
+    assert 3 < zero.sum() < J - 3
+    assert twin.last_vector_nk == J
+    assert twin.last_vector_materials.shape == (J, 1, _abi.ART_COATING_MAX_MATERIALS, 2)
+    kj = p.omega[0] / C_FS + np.arange(J) * (2 * math.pi / 4.0 / C_FS)
+    assert np.array_equal(twin.last_vector_materials[:, 0], coat.material_table(2 * math.pi / kj))
+    sp = p.spectrum.numpy()
+    assert sp.shape == (1, J, 3, 3, 3) and p.envelope.shape == (1, 8, 3, 3, 3)
+    assert not sp[:, zero].any() and np.abs(sp[:, ~zero]).max(axis=(0, 2, 3, 4)).min() > 0
 
 
 def test_the_same_result_as_with_every_frequency_in_the_call(twin, setup):
