@@ -158,6 +158,17 @@ class OpticalChain:
         from . import polarisation
         return polarisation.polarisation(self, Coatings, Polarisation, Detector, Wavelength, PerRay)
 
+    def get_RayTubes(self, Detector=None, Source=None, PerRay=True):
+        """Ray tubes along the chain (tubes.RayTubes): differential ray tracing in one device pass over get_output_rays()
+        and source_rays.  Per ray the image-space solid angle per unit source measure, the tube's cross-section on
+        Detector (without one: at the last hit point) and the two principal wavefront curvatures with their focal lines;
+        `rays` is the final bundle re-weighted by |solid_angle| (total power kept) for the focal sums.  Source: "point",
+        "plane", or None to take what ModuleSource recorded on the source bundle; PerRay=False keeps only the sums and
+        the weights.  DeformedMirror, Grating and MirrorFreeform elements raise NotImplementedError.  A lazy history is
+        materialised by its own mechanism, which costs one re-trace."""
+        from . import tubes
+        return tubes.tubes(self, Detector, Source, PerRay)
+
     def get_FocalPulse(self, Coatings, Detector, DeltaFT, Polarisation, Size=None, Pixels=64, Centre=None, Shifts=None,
                        Wavelength=None, RefPath=None, Spectrum=None, TimeWindow=None, Times=256, ScratchBytes=None):
         """The space-time VECTOR field of a broadband pulse at focus behind the chain's coatings

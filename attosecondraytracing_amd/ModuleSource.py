@@ -23,6 +23,7 @@ def _device_source(kind, size, S, Axis, n, n_total, Wavelength):
     # the bundle is a pure function of these arguments (the generator is deterministic)
     b.tag_content(("source", int(kind), float(size), np.asarray(S, dtype=float).tobytes(),
                    np.asarray(Axis, dtype=float).tobytes(), int(n), int(n_total), Wavelength))
+    b.source_kind = "plane" if kind == 1 else "point"     # what OpticalChain.get_RayTubes seeds its tubes by
     return b
 
 
@@ -56,6 +57,7 @@ def ExtendedSource(S, Axis, Diameter: float, Divergence: float, NbRays: int, Wav
     b.tag_content(("extended source", float(Diameter), float(Divergence), int(n_src), int(per),
                    np.asarray(S, dtype=float).tobytes(), np.asarray(Axis, dtype=float).tobytes(), Wavelength))
     b.rays_per_source = per       # the mutually incoherent groups of Detector.get_FocalImage
+    b.source_kind = "point"       # per ray: each belongs to one point source of the disk
     return b
 
 

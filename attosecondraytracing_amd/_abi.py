@@ -255,6 +255,33 @@ class ArtPolarisationJob(C.Structure):
     ]
 
 
+ART_TUBE_POINT, ART_TUBE_PLANE = range(2)
+ART_TUBE_MAX_ELEMS = 64
+ART_TUBE_MAX_JOBS = 64
+ART_TUBE_DOUBLES = 16
+
+
+class ArtTubeJob(C.Structure):
+    _fields_ = [
+        ("views", C.c_void_p),
+        ("elems", C.c_void_p),
+        ("quadrics", C.c_void_p),
+        ("n_elems", C.c_int32),
+        ("seed", C.c_int32),
+        ("has_detector", C.c_int32),
+        ("reserved", C.c_int32),
+        ("det", ArtDetectorDesc),
+        ("w", C.c_void_p),
+        ("n", C.c_int64),
+        ("weight", C.c_void_p),
+        ("solid_angle", C.c_void_p),
+        ("area", C.c_void_p),
+        ("kappa1", C.c_void_p),
+        ("kappa2", C.c_void_p),
+        ("axis", C.c_void_p),
+    ]
+
+
 ART_FOCAL_VECTOR_SCRATCH_DEFAULT = 1 << 29
 
 
@@ -340,6 +367,8 @@ PROTOTYPES = {
     "art_polarisation_scratch_doubles": (C.c_int64, [C.POINTER(ArtPolarisationJob), C.c_int32]),
     "art_polarisation": (C.c_int, [C.c_void_p, C.POINTER(ArtPolarisationJob), C.c_int32, C.c_void_p,
                                    C.POINTER(ArtCoating), C.c_int32, C.c_void_p, C.c_void_p]),
+    "art_ray_tubes_scratch_doubles": (C.c_int64, [C.POINTER(ArtTubeJob), C.c_int32]),
+    "art_ray_tubes": (C.c_int, [C.c_void_p, C.POINTER(ArtTubeJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_focal_vector_spectrum_scratch_doubles": (C.c_int64, [C.POINTER(ArtFocalVectorSpectrumDesc)]),
     "art_focal_vector_spectrum": (C.c_int, [C.POINTER(ArtFocalVectorSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p,
                                             C.POINTER(ArtCoating), C.POINTER(ArtCoatingMaterial), C.c_void_p,

@@ -613,6 +613,41 @@ class HipBackend:
                                                self.stream_ptr()), "art_polarisation")
         return out
 
+    def ray_tubes(self, jobs, views, elems, quadrics):
+        """art_ray_tubes for a list of ArtTubeJob (host structs; their `views`, `elems` and `quadrics` are set here) and,
+        per job, the HOST ctypes arrays of its K + 1 views, its K element descriptors and its K quadrics (or None):
+        uploads the tables, enqueues the two launches and returns the DEVICE tensor out[len(jobs), ART_TUBE_DOUBLES].
+        An element the pass does not cover raises NotImplementedError with the library's message."""
+        c = len(jobs)
+        out = torch.empty((c, _abi.ART_TUBE_DOUBLES), dtype=torch.float64, device=self.device)
+        parts = []
+        for v, e, q in zip(views, elems, quadrics):
+            parts += [bytes(v), bytes(e), b"" if q is None else bytes(q)]
+        blob = b"".join(parts)
+        dev = self._upload_table((C.c_char * len(blob)).from_buffer_copy(blob), "ray tube tables")
+        off = 0
+        jhost, jdev = (_abi.ArtTubeJob * c)(), (_abi.ArtTubeJob * c)()
+        for k, (j, v, e, q) in enumerate(zip(jobs, views, elems, quadrics)):
+            jhost[k] = j
+            jdev[k] = j
+            jhost[k].views = jdev[k].views = dev.data_ptr() + off
+            off += C.sizeof(v)
+            jhost[k].elems, jdev[k].elems = C.addressof(e), dev.data_ptr() + off
+            off += C.sizeof(e)
+            if q is not None:
+                jhost[k].quadrics, jdev[k].quadrics = C.addressof(q), dev.data_ptr() + off
+                off += C.sizeof(q)
+        ns = self.fn["art_ray_tubes_scratch_doubles"](jhost, c)
+        if ns == _abi.ART_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.last_error())
+        if ns < 0:
+            raise ArtError(f"art_ray_tubes_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self.scratch("ray tubes", ns, torch.float64)
+        table = self._upload_table(jdev)
+        self.check(self.fn["art_ray_tubes"](table.data_ptr(), jhost, c, scratch.data_ptr(), out.data_ptr(),
+                                            self.stream_ptr()), "art_ray_tubes")
+        return out
+
     def focal_vector_tables(self, vdesc, views, coatings, materials):
         """Uploads the tables of art_focal_vector_spectrum and points vdesc at them (`views`, `materials`, `n_coatings`).
         views: the HOST ctypes array of the chain's K + 1 views; coatings: a list of ArtCoating; materials: float64

@@ -216,9 +216,12 @@ class RayBundle:
         return rays if isinstance(rays, RayBundle) else cls.from_ray_list(rays, backend)
 
     def _share_grouping(self, other):
-        """Bundles over the same slots keep ExtendedSource's rays_per_source (image.py: the incoherent groups)."""
+        """Bundles over the same slots keep ExtendedSource's rays_per_source (image.py: the incoherent groups) and the
+        source_kind ModuleSource recorded ("point" or "plane": tubes.py seeds its ray tubes by it)."""
         if hasattr(self, "rays_per_source"):
             other.rays_per_source = self.rays_per_source
+        if hasattr(self, "source_kind"):
+            other.source_kind = self.source_kind
 
     # ------------------------------------------------------------------ raw access
     @property

@@ -15,6 +15,7 @@
 
 #include "art_device.h"
 #include "art_coating.h"
+#include "art_tubes.h"
 #include "art_scene.h"
 
 // The -DART_ZERN_LDS comparison build keeps a persistent grid whose last pass may leave part of a workgroup idle: no
@@ -2538,6 +2539,109 @@ __global__ __launch_bounds__(kFoldBlock) void k_polarisation_fold(const ArtPolar
   if (threadIdx.x == 0) jb.out[q] = (cnt == 0.0 || (q == 10 && !jb.polarised)) ? 0.0 : v;
 }
 
+// ------------------------------------------------------------------------------------------- ray tubes
+// art_ray_tubes: one pass over a traced chain's history per job (include/art_hip.h; the per-ray math is art_tubes.h).
+// k_ray_tubes: k_polarisation's shape -- grid (tiles of 256 slots, jobs), one ray per lane, the loop over the elements
+// inside.  The slot's alive bytes in all K + 1 views are read first; every other stream of a slot that does not count is
+// requested at an out-of-range offset (no traffic, reads 0, selected away).  Job, views, elements and quadrics are
+// wave-uniform: scalar loads through the constant address space.  Per tile kTubeStats partials (block_reduce_store),
+// folded per job in tile order by k_ray_tubes_fold (fold_range).  A job's tiles depend on its own n: same bytes in any batch.
+constexpr int kTubeStats = 11;  // [0] count [1] sum w [2] sum w |sa| [3] min [4] max |sa| [5] sum w |area| [6..7] sum w kappa
+                                // [8] sum w, [9] count of the rays with finite kappa [10] max relative asymmetry
+constexpr int tube_op(const int q) { return q == 3 ? RMIN : ((q == 4 || q == 10) ? RMAX : RSUM); }
+typedef const ArtElementDesc __attribute__((address_space(4)))* tube_elem_t;
+typedef const ArtQuadricDesc __attribute__((address_space(4)))* tube_quad_t;
+
+__device__ __forceinline__ void tube_ray(const ArtBundleView* views, const int e, const unsigned nb8, const unsigned o8,
+                                         double* P, double* D) {
+  const pol_view_t v = (pol_view_t)views + e;
+  P[0] = ld_f64(rsrc_of(v->ox, nb8), o8);
+  P[1] = ld_f64(rsrc_of(v->oy, nb8), o8);
+  P[2] = ld_f64(rsrc_of(v->oz, nb8), o8);
+  D[0] = ld_f64(rsrc_of(v->dx, nb8), o8);
+  D[1] = ld_f64(rsrc_of(v->dy, nb8), o8);
+  D[2] = ld_f64(rsrc_of(v->dz, nb8), o8);
+}
+
+__global__ __launch_bounds__(kBlock) void k_ray_tubes(const ArtTubeJob* __restrict__ jobs, const int64_t per_job,
+                                                      double* scratch) {
+  const ArtTubeJob& jb = jobs[blockIdx.y];
+  const int64_t n = jb.n;
+  if ((int64_t)blockIdx.x >= pol_tiles(n)) return;     // (the grid covers the largest job)
+  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned nb8 = (unsigned)(n * 8), nb1 = (unsigned)n;   // n <= 2^28 (checked by the host)
+  const int K = jb.n_elems;
+  const ArtBundleView* views = jb.views;
+  bool live = true;                                    // (slots >= n fall outside the descriptor: they read 0)
+  for (int e = 0; e <= K; ++e)
+    live = live && __builtin_amdgcn_raw_buffer_load_b8(rsrc_of(pol_alive(views, e), nb1), (int)i, 0, ART_LD_AUX) != 0;
+  const unsigned o8 = live ? i * 8u : kDropOffset;
+  const double w = jb.w ? ld_f64(rsrc_of(const_cast<double*>(jb.w), nb8), o8) : 1.0;
+  double P[3], D[3];
+  tube_ray(views, 0, nb8, o8, P, D);
+  artt::Tube T;
+  artt::seed(jb.seed, D, T);
+  for (int e = 0; e < K; ++e) {
+    double Pn[3], Dn[3];
+    tube_ray(views, e + 1, nb8, o8, Pn, Dn);
+    artt::Surface s;
+    artt::load_surface((tube_elem_t)jb.elems + e, (tube_quad_t)jb.quadrics + e, s);
+    artt::step(s, D, P, Pn, T);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { P[q] = Pn[q]; D[q] = Dn[q]; }
+  }
+  artt::Readout R;
+  artt::readout(T, D, P, jb.has_detector != 0, jb.det.centre, jb.det.normal, R);
+  const double sa = fabs(R.solid_angle);
+  const double weight = live ? w * sa : 0.0;
+  st_f64(rsrc_of(jb.weight, nb8), i * 8u, weight);     // (slots >= n fall outside the descriptor)
+  // the optional arrays: a NULL one gets a descriptor of no bytes, which drops every store
+  st_f64(rsrc_of(jb.solid_angle, jb.solid_angle ? nb8 : 0u), i * 8u, live ? R.solid_angle : NAN);
+  st_f64(rsrc_of(jb.area, jb.area ? nb8 : 0u), i * 8u, live ? R.area : NAN);
+  st_f64(rsrc_of(jb.kappa1, jb.kappa1 ? nb8 : 0u), i * 8u, live ? R.kappa1 : NAN);
+  st_f64(rsrc_of(jb.kappa2, jb.kappa2 ? nb8 : 0u), i * 8u, live ? R.kappa2 : NAN);
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+    st_f64(rsrc_of(jb.axis ? jb.axis + (int64_t)q * n : nullptr, jb.axis ? nb8 : 0u), i * 8u, live ? R.axis[q] : NAN);
+  const bool fin = live && isfinite(R.kappa1) && isfinite(R.kappa2);
+  const double den = fabs(R.kappa1) + fabs(R.kappa2);
+  double acc[kTubeStats];
+  acc[0] = live ? 1.0 : 0.0;
+  acc[1] = live ? w : 0.0;
+  acc[2] = weight;
+  acc[3] = live ? sa : INFINITY;
+  acc[4] = live ? sa : -INFINITY;
+  acc[5] = live ? w * fabs(R.area) : 0.0;
+  acc[6] = fin ? w * R.kappa1 : 0.0;
+  acc[7] = fin ? w * R.kappa2 : 0.0;
+  acc[8] = fin ? w : 0.0;
+  acc[9] = fin ? 1.0 : 0.0;
+  acc[10] = fin ? (den > 0.0 ? R.asymmetry / den : 0.0) : -INFINITY;
+  block_reduce_store<kTubeStats>(acc, tube_op, scratch + (int64_t)blockIdx.y * per_job + (int64_t)blockIdx.x * kTubeStats);
+}
+
+// grid (ART_TUBE_DOUBLES, jobs): workgroup (q, j) folds statistic q of job j's tiles in tile order
+__global__ __launch_bounds__(kFoldBlock) void k_ray_tubes_fold(const ArtTubeJob* __restrict__ jobs, const int64_t per_job,
+                                                               const double* scratch, double* out) {
+  const int q = blockIdx.x;
+  double* row = out + (int64_t)blockIdx.y * ART_TUBE_DOUBLES;
+  if (q >= kTubeStats) {
+    if (threadIdx.x == 0) row[q] = 0.0;
+    return;
+  }
+  const double* part = scratch + (int64_t)blockIdx.y * per_job;
+  const int64_t tiles = pol_tiles(jobs[blockIdx.y].n);
+  double v = 0.0, other = 1.0;
+  fold_range(part + q, 0, tiles, tube_op(q), &v, kTubeStats);
+  // a minimum or maximum over no ray is 0; a mean is the sum over the sum of the weights
+  const int with = (q == 3 || q == 4) ? 0 : ((q == 6 || q == 7) ? 8 : (q == 10 ? 9 : -1));
+  if (with >= 0) {
+    __syncthreads();
+    fold_range(part + with, 0, tiles, RSUM, &other, kTubeStats);
+  }
+  if (threadIdx.x == 0) row[q] = other == 0.0 ? 0.0 : ((q == 6 || q == 7) ? v / other : v);
+}
+
 // ------------------------------------------------------------------------------------------- vector focal spectrum
 // art_focal_vector_spectrum (include/art_hip.h): art_focal_spectrum's sum with a complex amplitude per (ray, wavenumber,
 // component), the field of art_polarisation carried through coatings whose optical constants depend on the wavenumber.
@@ -4430,6 +4534,68 @@ int art_polarisation(const ArtPolarisationJob* jobs_dev, const ArtPolarisationJo
   hipLaunchKernelGGL(k_polarisation_fold, dim3(ART_POLARISATION_DOUBLES, n_jobs), dim3(kFoldBlock), 0, s, jobs_dev, per_job,
                      (const double*)scratch);
   return launched("art_polarisation launch");
+}
+
+// validates a ray-tube job table (host copies of the elements included); *nmax: the largest slot count
+static int tube_check_jobs(const ArtTubeJob* jobs, int32_t n_jobs, int64_t* nmax) {
+  if (!jobs) return fail(ART_ERR_BAD_ARG, "ray-tube job table is NULL");
+  if (n_jobs < 1 || n_jobs > ART_TUBE_MAX_JOBS) return fail(ART_ERR_BAD_ARG, "n_jobs must be in 1..ART_TUBE_MAX_JOBS");
+  *nmax = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const ArtTubeJob& jb = jobs[j];
+    if (jb.n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+    if (jb.n > kMaxRaysPerLaunchHw) return fail(ART_ERR_UNSUPPORTED, "more than 2^28 rays per chain in one ray-tube call");
+    if (jb.n_elems < 1 || jb.n_elems > ART_TUBE_MAX_ELEMS)
+      return fail(ART_ERR_BAD_ARG, "a ray-tube job must have 1..ART_TUBE_MAX_ELEMS elements");
+    if (jb.seed != ART_TUBE_POINT && jb.seed != ART_TUBE_PLANE) return fail(ART_ERR_BAD_ARG, "unknown ray-tube seed");
+    if (!jb.views || !jb.elems || !jb.weight) return fail(ART_ERR_BAD_ARG, "a ray-tube job's views, elems or weight is NULL");
+    if (jb.has_detector) {
+      double nn = 0.0;
+      bool finite = true;
+      for (int q = 0; q < 3; ++q) {
+        nn += jb.det.normal[q] * jb.det.normal[q];
+        finite = finite && isfinite(jb.det.centre[q]) && isfinite(jb.det.normal[q]);
+      }
+      if (!finite || !(fabs(nn - 1.0) <= 1e-12)) return fail(ART_ERR_BAD_ARG, "a ray-tube job's detector needs a finite centre and a unit normal");
+    }
+    for (int e = 0; e < jb.n_elems; ++e) {
+      const ArtElementDesc& el = jb.elems[e];
+      char msg[96];
+      if (el.kind < 0 || el.kind >= ART_NUM_KINDS) return fail(ART_ERR_BAD_ARG, "unknown optic kind");
+      const char* why = (el.flags & ART_FLAG_GRATING)    ? "is a grating"
+                        : (el.flags & ART_FLAG_FREEFORM) ? "is a freeform"
+                        : (el.n_defects > 0 || el.n_grid > 0 || (el.flags & (ART_FLAG_PERTURBED_NORMAL | ART_FLAG_ZERN_RECURRENCE)))
+                            ? "has defects"
+                            : nullptr;
+      if (why) {
+        snprintf(msg, sizeof msg, "ray tubes: element %d %s", e, why);
+        return fail(ART_ERR_UNSUPPORTED, msg);
+      }
+      if ((el.flags & ART_FLAG_QUADRIC) && !jb.quadrics) return fail(ART_ERR_BAD_ARG, "a quadric element without the quadrics table");
+    }
+    *nmax = jb.n > *nmax ? jb.n : *nmax;
+  }
+  return ART_OK;
+}
+
+int64_t art_ray_tubes_scratch_doubles(const ArtTubeJob* jobs_host, int32_t n_jobs) {
+  int64_t nmax;
+  const int rc = tube_check_jobs(jobs_host, n_jobs, &nmax);
+  return rc ? rc : (int64_t)n_jobs * kTubeStats * pol_tiles(nmax);
+}
+
+int art_ray_tubes(const ArtTubeJob* jobs_dev, const ArtTubeJob* jobs_host, int32_t n_jobs, double* scratch, double* out,
+                  void* stream) {
+  if (!jobs_dev || !scratch || !out) return fail(ART_ERR_BAD_ARG, "NULL argument");
+  int64_t nmax;
+  const int rc = tube_check_jobs(jobs_host, n_jobs, &nmax);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t per_job = kTubeStats * pol_tiles(nmax);
+  hipLaunchKernelGGL(k_ray_tubes, dim3((unsigned)pol_tiles(nmax), n_jobs), dim3(kBlock), 0, s, jobs_dev, per_job, scratch);
+  hipLaunchKernelGGL(k_ray_tubes_fold, dim3(ART_TUBE_DOUBLES, n_jobs), dim3(kFoldBlock), 0, s, jobs_dev, per_job,
+                     (const double*)scratch, out);
+  return launched("art_ray_tubes launch");
 }
 
 // the wavenumber blocks of art_focal_vector_spectrum: slices S of the rays (never from the block: the same bytes for any),

@@ -620,6 +620,67 @@ int art_polarisation(const ArtPolarisationJob* jobs_dev, const ArtPolarisationJo
                      const ArtCoating* coatings_dev, const ArtCoating* coatings_host, int32_t n_coatings, double* scratch,
                      void* stream);
 
+/* Ray tubes of MANY traced chains in one call: differential ray tracing (added under ABI 14: ArtTubeJob, art_ray_tubes,
+ * art_ray_tubes_scratch_doubles).  One streaming pass over a chain's existing history; the tracing kernels are not
+ * involved.  Beside each ray travel the first-order changes dP_j, dD_j (j = a, b) of its point and direction with respect
+ * to two source parameters that span the plane perpendicular to the source direction:
+ *   ART_TUBE_POINT  dP = 0, dD = (u, v): the source measure mu is solid angle;  ART_TUBE_PLANE  dP = (u, v), dD = 0: area.
+ * At every element the hit point P (views[e + 1]'s point), the previous point and the incoming direction D (views[e])
+ * give, with the gradient g and Hessian H of the surface's implicit form at P in the optic frame and n = -g / |g|,
+ *   t = (P - P_prev).D,  a_j = dP_j + t dD_j,  dQ_j = a_j - D (n.a_j) / (n.D),  dn_j = -(H dQ_j - n (n.H dQ_j)) / |g|,
+ *   dD'_j = dD_j - 2 [(dD_j.n + D.dn_j) n + (D.n) dn_j]          (a mask: the plane rule, dD unchanged)
+ * (forms per kind and the derivation: csrc/art_tubes.h).  Behind the last element, D' the final direction, dX_j the
+ * tangents carried onto the detector plane (has_detector) or dQ_j at the last hit point (none):
+ *   solid_angle = D'.(dD_a x dD_b)                  dOmega' / dmu, signed, always finite
+ *   area        = nd.(dX_a x dX_b) (detector) or D'.(dQ_a x dQ_b): mm^2 per unit mu, signed
+ *   kappa1 <= kappa2: the eigenvalues of the symmetric part of the wavefront curvature matrix C = B A^-1 (A = [v_i.dX_j],
+ *   B = [v_i.dD_j], v_i perpendicular to D') in 1 / mm, negative = converging, the focal line at -1 / kappa along the
+ *   ray; axis: the unit eigenvector of kappa1 in the lab frame, [3][n].  At a caustic A is singular: kappa and axis are
+ *   +-inf or NaN there, nothing is clamped.
+ * A ray counts when it is alive in EVERY view.  weight[r] = w[r] |solid_angle| (w NULL: 1), 0 for the others, whose
+ * entries of the optional arrays are NaN.
+ * out (DEVICE, ART_TUBE_DOUBLES doubles per job, written), sums over the counted rays:
+ *   [0] their count  [1] sum w  [2] sum w |solid_angle|  [3] min, [4] max |solid_angle| (0 without rays)  [5] sum w |area|
+ *   [6], [7] the w-weighted means of kappa1, kappa2 over the rays where both are finite (0 without such rays)
+ *   [8] sum w over those rays  [9] their count  [10] max over them of |C_12 - C_21| / (|kappa1| + |kappa2|) (0 where the
+ *   denominator is 0; Malus-Dupin: rounding only)  [11..15] 0
+ * Fixed summation order, no float atomics; a job's slicing depends on its own n only: every job gets the same bytes
+ * whichever jobs share its call.  jobs_dev: a DEVICE copy of jobs_host whose `elems` and `quadrics` point to DEVICE
+ * copies; in jobs_host they point to the HOST originals, read for validation.  The elements are the caller's
+ * descriptors as art_trace_element takes them (fwd, pos, centre, kind, mp are read).
+ * scratch: DEVICE, art_ray_tubes_scratch_doubles(jobs_host, n_jobs).
+ * Limits: 1 <= n_jobs <= ART_TUBE_MAX_JOBS, 0 <= n <= 2^28 (ART_ERR_UNSUPPORTED beyond), 1 <= n_elems <=
+ * ART_TUBE_MAX_ELEMS, a known seed and kind, views, elems, weight, out and scratch non-NULL, quadrics non-NULL where an
+ * element has ART_FLAG_QUADRIC, a unit detector normal: ART_ERR_BAD_ARG otherwise.  ART_ERR_UNSUPPORTED: an element with
+ * defects (n_defects, n_grid > 0 or ART_FLAG_PERTURBED_NORMAL), a grating, a freeform (its Hessian needs the figure's
+ * second derivatives).  Nothing is launched on failure.                                                              */
+#define ART_TUBE_POINT 0
+#define ART_TUBE_PLANE 1
+#define ART_TUBE_MAX_ELEMS 64
+#define ART_TUBE_MAX_JOBS 64
+#define ART_TUBE_DOUBLES 16
+typedef struct ArtTubeJob {
+  const ArtBundleView* views;      /* DEVICE array of n_elems + 1 views: the source, then the bundle after each element */
+  const ArtElementDesc* elems;     /* n_elems descriptors (DEVICE in jobs_dev, HOST in jobs_host)                       */
+  const ArtQuadricDesc* quadrics;  /* n_elems entries, read where ART_FLAG_QUADRIC is set; may be NULL without any      */
+  int32_t n_elems;                 /* K                                                                                 */
+  int32_t seed;                    /* ART_TUBE_POINT | ART_TUBE_PLANE                                                   */
+  int32_t has_detector;            /* 1: area and curvature on det's plane; 0: at the last hit point                    */
+  int32_t reserved;
+  ArtDetectorDesc det;
+  const double* w;                 /* DEVICE weights [n] or NULL (all 1)                                                */
+  int64_t n;                       /* slots of every view                                                               */
+  double* weight;                  /* DEVICE [n], always written                                                        */
+  double* solid_angle;             /* DEVICE [n] or NULL; likewise the next four                                        */
+  double* area;
+  double* kappa1;
+  double* kappa2;
+  double* axis;                    /* DEVICE [3][n] or NULL                                                             */
+} ArtTubeJob;
+int64_t art_ray_tubes_scratch_doubles(const ArtTubeJob* jobs_host, int32_t n_jobs);
+int art_ray_tubes(const ArtTubeJob* jobs_dev, const ArtTubeJob* jobs_host, int32_t n_jobs, double* scratch,
+                  double* out /* DEVICE [n_jobs][ART_TUBE_DOUBLES] */, void* stream);
+
 /* Vector focal fields of a pulse behind dispersive coatings (added under ABI 14: ArtFocalVectorSpectrumDesc,
  * art_focal_vector_spectrum, art_focal_vector_spectrum_scratch_doubles): art_focal_spectrum's sum with the complex
  * vector field of art_polarisation, evaluated per ray AND per wavenumber, as each ray's amplitude.  With
