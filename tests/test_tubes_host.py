@@ -1,7 +1,8 @@
 """CPU: ray tubes (differential ray tracing) -- the long-double restatement of tests/tubes_common.py against its own
 finite-difference truth, the header's per-ray functions (csrc/art_tubes.h compiled with g++) against the restatement, the
-closed forms (Coddington on a toroid's chief ray, the stigmatic ellipsoid and paraboloid, the plane mirror, Malus-Dupin),
-the ABI mirror, the entry point's host-side refusals and the Python layer's argument errors."""
+closed forms (Coddington on a toroid's chief ray and on a convex sphere's, the stigmatic ellipsoid and paraboloid, the
+plane mirror, Malus-Dupin), the admission rule of the added scenes, one quadric described in two optic frames, the ABI
+mirror, the entry point's host-side refusals and the Python layer's argument errors."""
 import ctypes as C
 import os
 import subprocess
@@ -19,7 +20,7 @@ LD = tb.LD
 @pytest.fixture(scope="module")
 def scenes():
     assert tb.HAVE_LD, "numpy.longdouble has no extended precision on this platform"
-    S = tb.scenes()
+    S = {**tb.scenes(), **tb.scenes_more()}
     for sc in S.values():
         sc["hist"], sc["alive"], sc["plan"] = tb.trace_history(sc["els"], *sc["rays"])
         sc["specs"] = [tb.spec_of(oe) for oe in sc["els"]]
@@ -29,19 +30,28 @@ def scenes():
     return S
 
 
+LOSSY = {"h_c3": 673, "h_c2": 490}                               # survivors of the golden chains that lose rays
+
+
 def test_no_ray_is_lost_except_behind_the_mask(scenes):
     for name, sc in scenes.items():
         n = len(sc["rays"][0])
         if name == "e_masked":
             assert n == 1001 and 100 < sc["alive"].sum() < n - 100
+        elif name in LOSSY:
+            assert n == tb.N_RAYS and sc["alive"].sum() == LOSSY[name], (name, int(sc["alive"].sum()))
         else:
             assert n == tb.N_RAYS and sc["alive"].all(), name
         assert sc["alive"][0], name                              # the chief ray
 
 
 # ------------------------------------------------------------------------------- restatement against finite differences
+MORE = ["h_rotated_quadric", "h_hyperboloid", "h_convex_sphere", "h_convex_cylinder", "h_convex_quadric", "h_mixed8", "h_c3",
+        "h_c2"]
+
+
 @pytest.mark.parametrize("name", ["a_toroid", "b_plane", "b_sphere", "b_parabola", "b_ellipsoid", "b_cylinder", "c_kb",
-                                  "d_twisted", "e_masked"])
+                                  "d_twisted", "e_masked"] + MORE)
 def test_restatement_agrees_with_richardson_extrapolated_central_differences(scenes, name):
     """The Jacobian of the final point (on the detector, or on the last surface) and direction with respect to the two
     source parameters: within 10 x the step-halving estimate of the finite differences, per quantity over the bundle."""
@@ -110,27 +120,33 @@ int main(int argc, char** argv) {
 '''
 
 
-def element_row(oe):
+def element_row(oe, spec=None):
+    """The harness' 32 doubles of an element; spec: a tubes_common.reframed description whose frame, centre and
+    coefficients replace the element's own."""
     from attosecondraytracing_amd import ModuleGeometry as mgeo, _abi
     M = oe.type
     fwd, _ = mgeo.frame_maps(oe.normal, oe.majoraxis)
     quad = hasattr(M, "_quadric_coefficients")
     mp = (list(M._abi_params()) + [0.0] * 4)[:4]
     co = list(M._quadric_coefficients()) if quad else [0.0] * 10
+    centre = M.get_centre()
+    if spec is not None:
+        fwd, centre, co = spec["fwd"], spec["centre"], spec["coeff"]
     return ([float(M._abi_kind), float(_abi.ART_FLAG_QUADRIC if quad else 0)] + list(np.asarray(fwd, dtype=float).reshape(9))
-            + list(np.asarray(oe.position, dtype=float)) + list(np.asarray(M.get_centre(), dtype=float)) + mp + co + [0.0])
+            + list(np.asarray(oe.position, dtype=float)) + list(np.asarray(centre, dtype=float)) + [float(v) for v in mp]
+            + [float(v) for v in co] + [0.0])
 
 
 @pytest.fixture(scope="module")
-def header(scenes, tmp_path_factory):
-    """name -> [n, 8] of the header's functions on the scene's fp64 history."""
+def harness(tmp_path_factory):
+    """(name, scene, rows) -> [n, 8] of the header's functions on the scene's fp64 history, the elements as `rows`."""
     td = tmp_path_factory.mktemp("tubes_harness")
     src, exe = td / "h.cpp", td / "h"
     src.write_text(HARNESS)
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-DART_HOST_TWIN", "-ffp-contract=off",
                            "-I", os.path.join(ROOT, "attosecondraytracing_amd", "csrc"), "-o", str(exe), str(src)])
-    out = {}
-    for name, sc in scenes.items():
+
+    def run(name, sc, rows):
         n, K = len(sc["rays"][0]), len(sc["els"])
         det = sc["det"]
         head = [n, K, 0 if sc["source"] == "point" else 1, 0 if det is None else 1] + \
@@ -138,15 +154,20 @@ def header(scenes, tmp_path_factory):
         fin, fout = str(td / (name + ".in")), str(td / (name + ".out"))
         with open(fin, "wb") as f:
             f.write(np.asarray(head, dtype=np.float64).tobytes())
-            for oe in sc["els"]:
-                row = element_row(oe)
+            for row in rows:
                 assert len(row) == 32
                 f.write(np.asarray(row, dtype=np.float64).tobytes())
             for P, D in sc["hist64"]:
                 f.write(np.ascontiguousarray(np.column_stack([P, D]), dtype=np.float64).tobytes())
         subprocess.check_call([str(exe), fin, fout])
-        out[name] = np.fromfile(fout, dtype=np.float64).reshape(n, 8)
-    return out
+        return np.fromfile(fout, dtype=np.float64).reshape(n, 8)
+    return run
+
+
+@pytest.fixture(scope="module")
+def header(scenes, harness):
+    """name -> [n, 8] of the header's functions on the scene's fp64 history."""
+    return {name: harness(name, sc, [element_row(oe) for oe in sc["els"]]) for name, sc in scenes.items()}
 
 
 def as_result(out):
@@ -161,6 +182,54 @@ def test_header_functions_agree_with_the_restatement(scenes, header):
         assert np.abs(np.linalg.norm(got["axis"][a], axis=1) - 1).max() <= 1e-14
         assert (got["kappa"][0][a] <= got["kappa"][1][a]).all()
     assert tb.axes_error(as_result(header["a_toroid"])["axis"], scenes["a_toroid"]["ref"]["axis"], scenes["a_toroid"]["alive"]) <= tb.PARITY
+
+
+@pytest.mark.parametrize("name", MORE)
+def test_added_scene_is_admitted_with_a_tenth_of_the_bar_to_spare(scenes, header, name):
+    """A scene may judge the device at PARITY only if the fp64 header on the CPU, same formulas and same history, stays a
+    factor of ten inside it (and every curvature is well conditioned: check_against_restatement asserts cond < COND_MAX)."""
+    sc = scenes[name]
+    got, ref, a = as_result(header[name]), sc["ref"], sc["alive"]
+    assert (ref["cond"][a] < tb.COND_MAX).all()
+    worst = {key: tb.compare(got[key], ref[key], a, f"{name} {key}", bar=tb.PARITY / 10) for key in ("solid_angle", "area", "kappa")}
+    k1, k2 = (np.nan_to_num(np.asarray(k, dtype=float)) for k in ref["kappa"])
+    apart = a & (k2 - k1 >= tb.AXIS_GAP * (np.abs(k1) + np.abs(k2)))
+    worst["axis"] = tb.axes_error(got["axis"], ref["axis"], apart)
+    print(f"{name}: header against restatement {worst}; axes compared on {int(apart.sum())} of {int(a.sum())} rays")
+    assert worst["axis"] <= tb.PARITY / 10, (name, worst)
+    if name == "h_hyperboloid":                                  # (not the stigmatic pose: its axes are compared)
+        assert 2 * apart.sum() >= a.sum()
+    if name == "h_rotated_quadric":
+        q = sc["specs"][0]["coeff"]
+        assert all(v != 0 for v in q[:6]) and q[6] == 0 and q[7] == 0
+
+
+def test_the_same_quadric_in_another_optic_frame(scenes, harness, header):
+    """h_rotated_quadric's surface described again with its optic frame turned by 50 degrees about (1, 2, 3) and shifted by
+    (3, -2, 5) mm: a quadric with b[0], b[1], c and a centre that no Python class produces.  The history is the same
+    rays; both descriptions agree with the restatement of each, and with one another, at the bar."""
+    sc = scenes["h_rotated_quadric"]
+    spec = sc["specs"][0]
+    moved = tb.reframed(spec)
+    assert all(v != 0 for v in moved["coeff"]) and moved["centre"].all()
+    P = tb.ld(sc["hist64"][1][0][sc["alive"]])                  # the hit points lie on both forms
+    for s in (spec, moved):
+        x = (P - s["pos"]) @ s["fwd"].T + s["centre"]
+        q = s["coeff"]
+        Q = np.array([[q[0], q[3], q[4]], [q[3], q[1], q[5]], [q[4], q[5], q[2]]], dtype=LD)
+        F = tb._dot(x @ Q, x) + 2 * (x @ np.array(q[6:9], dtype=LD)) + q[9]
+        assert np.abs(F).max() <= 1e-12 * np.abs(tb._dot(x @ Q, x)).max()
+    ref2 = tb.run([moved], sc["hist64"], sc["source"], sc["det"], sc["w"], sc["alive"])
+    got = as_result(header["h_rotated_quadric"])
+    got2 = as_result(harness("h_rotated_quadric_moved", sc, [element_row(sc["els"][0], moved)]))
+    a = sc["alive"]
+    tb.check_against_restatement(got, sc["ref"], "own frame")
+    tb.check_against_restatement(got2, ref2, "moved frame")
+    tb.check_against_restatement(got2, sc["ref"], "moved frame, header against the restatement in the own frame")
+    worst = {key: tb.compare(got2[key], got[key], a, "the two descriptions: " + key) for key in ("solid_angle", "area", "kappa")}
+    worst["axis"] = tb.axes_error(got2["axis"], got["axis"], a)
+    print(f"the header on the two descriptions of one quadric: {worst}")
+    assert worst["axis"] <= tb.PARITY
 
 
 def both(scenes, header, name):
@@ -179,6 +248,20 @@ def test_coddington_on_the_toroids_chief_ray(scenes, header):
         f1, f2 = -1 / LD(res["kappa"][0][0]), -1 / LD(res["kappa"][1][0])
         print(f"{who}: chief-ray foci {float(f1):.10f} (sagittal) {float(f2):.10f} (tangential) mm")
         assert abs(f1 - ss) <= 1e-10 * ss and abs(f2 - st) <= 1e-10 * st, who
+
+
+def test_coddington_on_the_convex_spheres_chief_ray(scenes, header):
+    """A sphere that curves away from the light, R = 1000, i = 25 deg, s = 500: 1/s + 1/s_t = -2 / (R cos i),
+    1/s + 1/s_s = -2 cos i / R, both images virtual; on the detector 150 mm on the wavefront's radii are 150 - s_t, 150 - s_s."""
+    s, R, ci = LD(500), LD(1000), np.cos(np.deg2rad(LD(25)))
+    st, ss = 1 / (-2 / (R * ci) - 1 / s), 1 / (-2 * ci / R - 1 / s)
+    assert st < 0 and ss < 0
+    want = sorted([1 / (150 - st), 1 / (150 - ss)])
+    for who, res in both(scenes, header, "h_convex_quadric"):
+        k1, k2 = LD(res["kappa"][0][0]), LD(res["kappa"][1][0])
+        print(f"{who}: chief-ray curvatures {float(k1):.12e} {float(k2):.12e} 1/mm, Coddington {float(want[0]):.12e} {float(want[1]):.12e}")
+        assert abs(k1 - want[0]) <= 1e-10 * want[1] and abs(k2 - want[1]) <= 1e-10 * want[1], who
+        assert (tb.ld(res["kappa"][0])[scenes["h_convex_quadric"]["alive"]] > 0).all(), who     # diverging everywhere
 
 
 def test_ellipsoid_is_stigmatic_for_every_ray(scenes, header):

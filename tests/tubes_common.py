@@ -391,9 +391,7 @@ def scenes():
     els, _, _ = place_chain([mm.MirrorToroidal(900.0, 100.0, big)], [500.0], [70.0], [0.0])
     S["a_toroid"] = mk(els, source_rays("point", 0.01), "point", wt=w(N_RAYS))
     els, p, d = place_chain([mm.MirrorPlane(big)], [300.0], [45.0], [20.0])
-    t = np.cross(d, [0.3, 0.5, 0.8])
-    nd = -(d + 0.2 * t / np.linalg.norm(t))
-    S["b_plane"] = mk(els, source_rays("point", 0.02), "point", det=(p + 150.0 * d, nd / np.linalg.norm(nd)))
+    S["b_plane"] = mk(els, source_rays("point", 0.02), "point", det=tilted_detector(p, d))
     els, _, _ = place_chain([mm.MirrorSpherical(1000.0, big)], [500.0], [10.0], [35.0])
     S["b_sphere"] = mk(els, source_rays("point", 0.02), "point", wt=w(N_RAYS))
     els, p, d = place_chain([mm.MirrorParabolic(100.0, 0.0, ms.SupportRound(30.0))], [200.0], [0.0], [0.0])
@@ -411,6 +409,84 @@ def scenes():
     els, rays, det = twisted(1001, mask=True)
     S["e_masked"] = mk(els, rays, "point", det=det, wt=w(1001))
     return S
+
+
+def tilted_detector(p, d, distance=150.0):
+    """The detector of b_plane: `distance` along the chief ray (p, d), its normal 0.2 off the ray."""
+    t = np.cross(d, [0.3, 0.5, 0.8])
+    nd = -(d + 0.2 * t / np.linalg.norm(t))
+    return p + distance * d, nd / np.linalg.norm(nd)
+
+
+def rotated_conic():
+    """The elliptical conic (400, 250, 30 degrees) with its pole frame turned by 35 degrees about z, Q' = Rz Q Rz^T: a
+    MirrorQuadric all six entries of whose q are non-zero (b = (0, 0, -0.5) is Rz's axis and stays)."""
+    import ART.ModuleMirror as mm
+    import ART.ModuleSupport as ms
+    q = [LD(v) for v in mm.MirrorConic(ms.SupportRound(80.0), 400.0, 250.0, 30.0)._quadric_coefficients()]
+    Q = np.array([[q[0], q[3], q[4]], [q[3], q[1], q[5]], [q[4], q[5], q[2]]], dtype=LD)
+    a = np.deg2rad(LD(35))
+    Rz = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]], dtype=LD)
+    Q = Rz @ Q @ Rz.T
+    M = mm.MirrorQuadric(ms.SupportRound(80.0), (Q + Q.T) / 2, np.array([0, 0, LD(-0.5)]))
+    assert all(abs(v) > 1e-6 * max(np.abs(M._quadric_coefficients()[:6])) for v in M._quadric_coefficients()[:6])
+    return M
+
+
+def scenes_more():
+    """name -> scene, as scenes(): a quadric with every coefficient of q set, a hyperboloid, two convex mirrors, and three
+    golden chains (eight elements of four kinds; two twisted chains that lose rays at a mask and at the toroids' edges)."""
+    import ART.ModuleMirror as mm
+    import ART.ModuleSupport as ms
+    import parity_common as pc
+    from conftest import load_golden
+    big = ms.SupportRectangle(300.0, 100.0)
+    w = lambda n: 0.5 + ((np.arange(n) * 0.6180339887498949) % 1.0)
+    S = {}
+    mk = lambda els, rays, source, det=None, wt=None, **kw: dict(els=els, rays=rays, source=source, det=det, w=wt, **kw)
+    els, p, d = place_chain([rotated_conic()], [400.0], [60.0], [20.0])
+    S["h_rotated_quadric"] = mk(els, source_rays("point", 0.02), "point", det=tilted_detector(p, d), wt=w(N_RAYS))
+    # the hyperboloid 5 degrees off its design incidence of 70: from its focus at 70 degrees it is stigmatic, every ray an
+    # umbilic, and no principal direction could be compared
+    els, p, d = place_chain([mm.MirrorConic(ms.SupportRound(80.0), 400.0, -250.0, 20.0)], [400.0], [65.0], [-25.0])
+    S["h_hyperboloid"] = mk(els, source_rays("point", 0.01), "point", det=tilted_detector(p, d))
+    els, _, _ = place_chain([mm.MirrorSpherical(-1000.0, big)], [500.0], [25.0], [35.0])
+    S["h_convex_sphere"] = mk(els, source_rays("point", 0.02), "point", wt=w(N_RAYS))
+    els, _, _ = place_chain([mm.MirrorCylindrical(-500.0, big)], [400.0], [30.0], [-15.0])
+    S["h_convex_cylinder"] = mk(els, source_rays("point", 0.02), "point")
+    # the two classes above are traced on the sheet of their concave twins (convexity enters the incidence angle alone): a
+    # surface that curves away from the light is this quadric, the sphere of radius 1000 about (0, 0, -1000)
+    ball = mm.MirrorQuadric(ms.SupportRound(80.0), -np.eye(3) / 2000.0, np.array([0.0, 0.0, -0.5]))
+    els, p, d = place_chain([ball], [500.0], [25.0], [35.0])
+    S["h_convex_quadric"] = mk(els, source_rays("point", 0.02), "point", det=tilted_detector(p, d), chief=(p, d))
+    for name, golden in (("h_mixed8", "c4_mixed8"), ("h_c3", "c3_twisted_chain04"), ("h_c2", "c2_fxf_chain05")):
+        scene, a = load_golden(golden)
+        D0 = np.asarray(a["src_vector"], dtype=float)
+        rays = (np.asarray(a["src_point"], dtype=float), D0 / np.linalg.norm(D0, axis=1)[:, None])
+        assert len(D0) == N_RAYS
+        S[name] = mk(pc.build_elements(scene, a), rays, "point", wt=w(N_RAYS) if name == "h_c3" else None)
+    return S
+
+
+def reframed(spec, axis=(1.0, 2.0, 3.0), degrees=50.0, shift=(3.0, -2.0, 5.0)):
+    """The same physical quadric described in another optic frame, x' = R x + c0 (R: `degrees` about `axis`, c0 = `shift`):
+    fwd' = R fwd, centre' = c0 (the spec's own centre is 0), Q' = R Q R^T, b' = R b - Q' c0, and c' from
+    F(x) = F'(R x + c0).  The numbers are rounded to fp64, as a descriptor holds them, and then taken as exact."""
+    assert spec["kind"] == "quadric" and not np.asarray(spec["centre"]).any()
+    k = ld(axis) / np.sqrt(_dot(ld(axis), ld(axis)))
+    a = np.deg2rad(LD(degrees))
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]], dtype=LD)
+    R = np.eye(3, dtype=LD) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
+    q, c0 = spec["coeff"], ld(shift)
+    Q = np.array([[q[0], q[3], q[4]], [q[3], q[1], q[5]], [q[4], q[5], q[2]]], dtype=LD)
+    b = np.array(q[6:9], dtype=LD)
+    Q2 = R @ Q @ R.T
+    Q2 = (Q2 + Q2.T) / 2
+    b2 = R @ b - Q2 @ c0
+    c2 = q[9] + c0 @ Q2 @ c0 - 2 * (R @ b) @ c0
+    fp64 = lambda v: ld(np.asarray(v, dtype=float))
+    coeff = [Q2[0, 0], Q2[1, 1], Q2[2, 2], Q2[0, 1], Q2[0, 2], Q2[1, 2], b2[0], b2[1], b2[2], c2]
+    return dict(spec, fwd=fp64(R @ spec["fwd"]), centre=fp64(c0), coeff=[LD(float(v)) for v in coeff])
 
 
 def compare(got, ref, alive, what, bar=PARITY):
