@@ -176,6 +176,14 @@ def ChromaticFocus(result):
     return _plots.ChromaticFocus(result)
 
 
+def SensitivityChart(result, Quantity="centroid_x", PerUnit=None):
+    """The alignment sensitivities of a chain (the result of OpticalChain.get_Sensitivities) as a bar chart of one quantity
+    (sensitivity.QUANTITIES: centroid, delay, spot and path variance, spread) per degree of freedom, shifts and rotations
+    on axes of their own; PerUnit = (mm, rad) rescales the bars to moves of that size."""
+    from . import _plots
+    return _plots.SensitivityChart(result, Quantity, PerUnit)
+
+
 def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston", "tilt")):
     """The fitted wavefront (Detector.get_Wavefront) on the pupil, in waves, with the terms in `Remove` taken out, and a
     bar chart of the Zernike terms' rms contributions in waves."""

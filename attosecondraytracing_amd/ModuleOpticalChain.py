@@ -169,6 +169,16 @@ class OpticalChain:
         from . import tubes
         return tubes.tubes(self, Detector, Source, PerRay)
 
+    def get_Sensitivities(self, Detector, PerRay=False):
+        """Alignment sensitivities (sensitivity.Sensitivities): the derivative of the detector centroid, the arrival time,
+        the pointing, the spot size and the path spread with respect to the six rigid degrees of freedom of every element
+        (shift_OE / rotate_OE) and of the source (shift_source / tilt_source), in one device pass over get_output_rays()
+        and source_rays -- no re-trace per degree of freedom.  Detector is required; PerRay=True keeps the per-ray dX, dY,
+        dL of every degree of freedom on the device.  First order; the counted rays are the nominal trace's.
+        DeformedMirror, Grating and MirrorFreeform elements raise NotImplementedError."""
+        from . import sensitivity
+        return sensitivity.sensitivity(self, Detector, PerRay)
+
     def get_FocalPulse(self, Coatings, Detector, DeltaFT, Polarisation, Size=None, Pixels=64, Centre=None, Shifts=None,
                        Wavelength=None, RefPath=None, Spectrum=None, TimeWindow=None, Times=256, ScratchBytes=None):
         """The space-time VECTOR field of a broadband pulse at focus behind the chain's coatings

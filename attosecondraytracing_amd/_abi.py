@@ -282,6 +282,27 @@ class ArtTubeJob(C.Structure):
     ]
 
 
+ART_SENS_DOUBLES = 16
+ART_SENS_COLS = 6
+
+
+class ArtSensitivityJob(C.Structure):
+    _fields_ = [
+        ("views", C.c_void_p),
+        ("elems", C.c_void_p),
+        ("quadrics", C.c_void_p),
+        ("n_elems", C.c_int32),
+        ("reserved", C.c_int32),
+        ("n", C.c_int64),
+        ("det", ArtDetectorDesc),
+        ("w", C.c_void_p),
+        ("origin", C.c_double * 3),
+        ("dX", C.c_void_p),
+        ("dY", C.c_void_p),
+        ("dL", C.c_void_p),
+    ]
+
+
 ART_FOCAL_VECTOR_SCRATCH_DEFAULT = 1 << 29
 
 
@@ -369,6 +390,8 @@ PROTOTYPES = {
                                    C.POINTER(ArtCoating), C.c_int32, C.c_void_p, C.c_void_p]),
     "art_ray_tubes_scratch_doubles": (C.c_int64, [C.POINTER(ArtTubeJob), C.c_int32]),
     "art_ray_tubes": (C.c_int, [C.c_void_p, C.POINTER(ArtTubeJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "art_sensitivities_scratch_doubles": (C.c_int64, [C.POINTER(ArtSensitivityJob), C.c_int32]),
+    "art_sensitivities": (C.c_int, [C.c_void_p, C.POINTER(ArtSensitivityJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_focal_vector_spectrum_scratch_doubles": (C.c_int64, [C.POINTER(ArtFocalVectorSpectrumDesc)]),
     "art_focal_vector_spectrum": (C.c_int, [C.POINTER(ArtFocalVectorSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p,
                                             C.POINTER(ArtCoating), C.POINTER(ArtCoatingMaterial), C.c_void_p,

@@ -648,6 +648,41 @@ class HipBackend:
                                             self.stream_ptr()), "art_ray_tubes")
         return out
 
+    def sensitivities(self, jobs, views, elems, quadrics):
+        """art_sensitivities for a list of ArtSensitivityJob, with the tables as ray_tubes takes and uploads them.  Returns
+        the DEVICE tensor of the jobs' tables one after another, [sum of 1 + 6 (K_j + 1), ART_SENS_DOUBLES].  An element
+        the pass does not cover raises NotImplementedError with the library's message."""
+        c = len(jobs)
+        rows = sum(1 + _abi.ART_SENS_COLS * (j.n_elems + 1) for j in jobs)
+        out = torch.empty((rows, _abi.ART_SENS_DOUBLES), dtype=torch.float64, device=self.device)
+        parts = []
+        for v, e, q in zip(views, elems, quadrics):
+            parts += [bytes(v), bytes(e), b"" if q is None else bytes(q)]
+        blob = b"".join(parts)
+        dev = self._upload_table((C.c_char * len(blob)).from_buffer_copy(blob), "sensitivity tables")
+        off = 0
+        jhost, jdev = (_abi.ArtSensitivityJob * c)(), (_abi.ArtSensitivityJob * c)()
+        for k, (j, v, e, q) in enumerate(zip(jobs, views, elems, quadrics)):
+            jhost[k] = j
+            jdev[k] = j
+            jhost[k].views = jdev[k].views = dev.data_ptr() + off
+            off += C.sizeof(v)
+            jhost[k].elems, jdev[k].elems = C.addressof(e), dev.data_ptr() + off
+            off += C.sizeof(e)
+            if q is not None:
+                jhost[k].quadrics, jdev[k].quadrics = C.addressof(q), dev.data_ptr() + off
+                off += C.sizeof(q)
+        ns = self.fn["art_sensitivities_scratch_doubles"](jhost, c)
+        if ns == _abi.ART_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.last_error())
+        if ns < 0:
+            raise ArtError(f"art_sensitivities_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self.scratch("sensitivities", ns, torch.float64)
+        table = self._upload_table(jdev)
+        self.check(self.fn["art_sensitivities"](table.data_ptr(), jhost, c, scratch.data_ptr(), out.data_ptr(),
+                                                self.stream_ptr()), "art_sensitivities")
+        return out
+
     def focal_vector_tables(self, vdesc, views, coatings, materials):
         """Uploads the tables of art_focal_vector_spectrum and points vdesc at them (`views`, `materials`, `n_coatings`).
         views: the HOST ctypes array of the chain's K + 1 views; coatings: a list of ArtCoating; materials: float64

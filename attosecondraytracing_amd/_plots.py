@@ -592,6 +592,29 @@ def ChromaticFocus(result):
     return fig
 
 
+def SensitivityChart(result, Quantity="centroid_x", PerUnit=None):
+    """A sensitivity.Sensitivities as a bar chart: `Quantity` (one of sensitivity.QUANTITIES) per degree of freedom, the
+    shifts (per mm) and the rotations (per rad) on axes of their own.  PerUnit = (mm, rad) rescales the bars to the
+    effect of moves of that size, e.g. (0.01, 1e-6) for 10 um and 1 urad."""
+    plt = _plt()
+    v = np.asarray(result.quantity(Quantity), dtype=float)
+    scale = (1.0, 1.0) if PerUnit is None else (float(PerUnit[0]), float(PerUnit[1]))
+    plt.ion()
+    fig, axes = plt.subplots(2, 1)
+    for ax, unit, k in zip(axes, ("mm", "rad"), scale):
+        pick = [c for c, u in enumerate(result.units) if u == unit]
+        ax.bar(range(len(pick)), v[pick] * k)
+        ax.set_xticks(range(len(pick)))
+        ax.set_xticklabels([f"{who}\n{dof}" for who, dof in (result.names[c] for c in pick)], rotation=90, fontsize=6)
+        ax.set_ylabel(f"{Quantity} per {unit}" if PerUnit is None else f"{Quantity} for {k:g} {unit}")
+        ax.axhline(0.0, color="k", linewidth=0.5)
+    axes[0].set_title(f"Alignment sensitivities, {result.count} rays")
+    fig.tight_layout()
+    fig._art_sensitivities = result
+    plt.show()
+    return fig
+
+
 def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston", "tilt")):
     """The fitted wavefront on the unit pupil in waves (Detector.get_Wavefront, `Remove`d terms taken out) beside a bar
     chart of every term's rms contribution in waves; rms, rms at the best reference point and the Marechal Strehl ratio

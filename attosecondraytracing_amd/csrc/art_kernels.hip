@@ -2642,6 +2642,174 @@ __global__ __launch_bounds__(kFoldBlock) void k_ray_tubes_fold(const ArtTubeJob*
   if (threadIdx.x == 0) row[q] = other == 0.0 ? 0.0 : ((q == 6 || q == 7) ? v / other : v);
 }
 
+// ------------------------------------------------------------------------------------------- alignment sensitivities
+// art_sensitivities: the pose derivatives of a traced chain, one pass over its history per job and group (include/art_hip.h;
+// the per-ray math is art_tubes.h).  k_sensitivities: k_ray_tubes' shape with the groups as a grid dimension -- grid (tiles
+// of 256 slots, groups x parts, jobs), one ray per lane.  Group g (0: the source, g >= 1: element g - 1) starts at its own
+// element, because its columns are zero before it, and reads the rays of the views from there on only; the alive bytes of
+// all K + 1 views are read first.  A workgroup carries kSensPerWg of the group's six columns per lane (6 / kSensPerWg
+// parts per group).  Per tile and part kSensRow0 + 12 kSensPerWg partial sums (block_sum_store) at
+// scratch[job][group x part][tile]; k_sensitivities_fold folds them per entry of the table in tile order (fold_range).
+// Row 0 is formed by every workgroup (its inputs are in registers anyway) and folded from group 0's partials.
+#ifndef ART_SENS_PER_WG
+#define ART_SENS_PER_WG 6          // 6: all columns of a group in one lane; 3: two workgroups per group
+#endif
+constexpr int kSensPerWg = ART_SENS_PER_WG, kSensParts = ART_SENS_COLS / kSensPerWg;
+constexpr int kSensRow0 = 8, kSensPerCol = 12, kSensStats = kSensRow0 + kSensPerCol * kSensPerWg;
+static_assert(kSensPerWg * kSensParts == ART_SENS_COLS && kSensStats <= kBlock, "columns per workgroup");
+
+// A workgroup's SUM of each of NS slots into dst[0 .. NS): wave_reduce24's transpose through a wave-private LDS tile for
+// any number of sums, eight per pass (NS shuffle trees cost more than the transport of the columns they sum: measured,
+// DESIGN.md 5), then the 4 waves in order.  One fixed order: the same bytes on every run.
+template <int NS>
+__device__ __forceinline__ void block_sum_store(const double (&acc)[NS], double* dst) {
+  constexpr int kPasses = (NS + 7) / 8;
+  __shared__ double tile[kBlock / 64][8 * kTileStride];
+  __shared__ double total[kBlock / 64][kPasses * 8];
+  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, stat = l >> 3, part = l & 7;
+#pragma unroll
+  for (int pass = 0; pass < kPasses; ++pass) {
+    // (wave-level barriers: scheduling fences that keep a pass's stores, its row loads and the next pass's stores in order)
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tile[w][j * kTileStride + l] = (pass * 8 + j < NS) ? acc[(pass * 8 + j < NS) ? pass * 8 + j : 0] : 0.0;
+    __builtin_amdgcn_wave_barrier();
+    const double* row = tile[w] + stat * kTileStride + part;
+    double v = row[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) v += row[8 * k];
+    v += dpp_xchg<0xB1>(v);    // quad_perm:[1,0,3,2]  lane ^ 1
+    v += dpp_xchg<0x4E>(v);    // quad_perm:[2,3,0,1]  lane ^ 2
+    v += dpp_xchg<0x141>(v);   // row_half_mirror      lane i <-> 7 - i of its group of 8
+    if (part == 0) total[w][pass * 8 + stat] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    const int k = threadIdx.x;
+    double v = total[0][k];
+    for (int j = 1; j < kBlock / 64; ++j) v += total[j][k];
+    dst[k] = v;
+  }
+}
+
+// the tables of the jobs before job j, in rows of ART_SENS_DOUBLES
+__device__ __forceinline__ int64_t sens_rows_before(const ArtSensitivityJob* jobs, const int j) {
+  int64_t rows = 0;
+  for (int k = 0; k < j; ++k) rows += 1 + ART_SENS_COLS * (jobs[k].n_elems + 1);
+  return rows;
+}
+
+__global__ __launch_bounds__(kBlock) void k_sensitivities(const ArtSensitivityJob* __restrict__ jobs, const int64_t per_job,
+                                                          const int64_t tiles_max, double* scratch) {
+  const ArtSensitivityJob& jb = jobs[blockIdx.z];
+  const int64_t n = jb.n;
+  const int K = jb.n_elems;
+  const int g = blockIdx.y / kSensParts, part = blockIdx.y % kSensParts;
+  if ((int64_t)blockIdx.x >= pol_tiles(n) || g > K) return;     // (the grid covers the largest job)
+  const unsigned i = blockIdx.x * kBlock + threadIdx.x;
+  const unsigned nb8 = (unsigned)(n * 8), nb1 = (unsigned)n;    // n <= 2^28 (checked by the host)
+  const ArtBundleView* views = jb.views;
+  bool live = true;                                             // (slots >= n fall outside the descriptor: they read 0)
+  for (int e = 0; e <= K; ++e)
+    live = live && __builtin_amdgcn_raw_buffer_load_b8(rsrc_of(pol_alive(views, e), nb1), (int)i, 0, ART_LD_AUX) != 0;
+  const unsigned o8 = live ? i * 8u : kDropOffset;
+  const double w = jb.w ? ld_f64(rsrc_of(const_cast<double*>(jb.w), nb8), o8) : 1.0;
+  const int first = g ? g - 1 : 0;
+  double P[3], D[3];
+  tube_ray(views, first, nb8, o8, P, D);
+  artt::Column c[kSensPerWg];
+#pragma unroll
+  for (int k = 0; k < kSensPerWg; ++k) {
+    if (g == 0) artt::seed_source(part * kSensPerWg + k, D, c[k]);
+    else artt::clear(c[k]);
+  }
+  for (int e = first; e < K; ++e) {
+    double Pn[3], Dn[3];
+    tube_ray(views, e + 1, nb8, o8, Pn, Dn);
+    artt::Surface s;
+    artt::load_surface((tube_elem_t)jb.elems + e, (tube_quad_t)jb.quadrics + e, s);
+    artt::Hit h;
+    artt::hit_of(s, D, P, Pn, h);
+    if (g == e + 1) {                                           // (wave-uniform: the group's own element)
+#pragma unroll
+      for (int k = 0; k < kSensPerWg; ++k) {
+        double sv[3], th[3];
+        artt::motion(s, part * kSensPerWg + k, Pn, sv, th);
+        artt::step_moved(s, h, D, sv, th, c[k]);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < kSensPerWg; ++k) artt::step_path(s, h, D, c[k]);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { P[q] = Pn[q]; D[q] = Dn[q]; }
+  }
+  const double path = ld_f64(rsrc_of(((pol_view_t)views + K)->path, nb8), o8);
+  // the nominal read-out about the caller's origin
+  const double toC[3] = {jb.det.centre[0] - P[0], jb.det.centre[1] - P[1], jb.det.centre[2] - P[2]};
+  const double tdet = artt::dot(jb.det.normal, toC) / artt::dot(jb.det.normal, D);
+  const double rel[3] = {fma(tdet, D[0], -toC[0]), fma(tdet, D[1], -toC[1]), fma(tdet, D[2], -toC[2])};
+  double xy[3];
+  artt::rot(jb.det.rot, rel, xy);
+  const double X = xy[0] - jb.origin[0], Y = xy[1] - jb.origin[1], L = (path + tdet) - jb.origin[2];
+  const double ww = live ? w : 0.0;
+  double acc[kSensStats];
+  acc[0] = live ? 1.0 : 0.0;
+  acc[1] = ww;
+  acc[2] = live ? w * X : 0.0;
+  acc[3] = live ? w * Y : 0.0;
+  acc[4] = live ? w * L : 0.0;
+  acc[5] = live ? w * X * X : 0.0;
+  acc[6] = live ? w * Y * Y : 0.0;
+  acc[7] = live ? w * L * L : 0.0;
+  const int64_t col0 = (int64_t)ART_SENS_COLS * g + part * kSensPerWg;
+#pragma unroll
+  for (int k = 0; k < kSensPerWg; ++k) {
+    double dX, dY;
+    artt::readout_column(D, P, jb.det.centre, jb.det.normal, jb.det.rot, c[k], dX, dY);
+    const double dL = c[k].dL;
+    // the optional arrays: a NULL one gets a descriptor of no bytes, which drops every store; slots >= n fall outside
+    const int64_t at = (col0 + k) * n;
+    st_f64(rsrc_of(jb.dX ? jb.dX + at : nullptr, jb.dX ? nb8 : 0u), i * 8u, live ? dX : NAN);
+    st_f64(rsrc_of(jb.dY ? jb.dY + at : nullptr, jb.dY ? nb8 : 0u), i * 8u, live ? dY : NAN);
+    st_f64(rsrc_of(jb.dL ? jb.dL + at : nullptr, jb.dL ? nb8 : 0u), i * 8u, live ? dL : NAN);
+    double* a = acc + kSensRow0 + kSensPerCol * k;
+    a[0] = live ? w * dX : 0.0;
+    a[1] = live ? w * dY : 0.0;
+    a[2] = live ? w * dL : 0.0;
+    a[3] = live ? w * X * dX : 0.0;
+    a[4] = live ? w * Y * dY : 0.0;
+    a[5] = live ? w * L * dL : 0.0;
+    a[6] = live ? w * dX * dX : 0.0;
+    a[7] = live ? w * dY * dY : 0.0;
+    a[8] = live ? w * dL * dL : 0.0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) a[9 + q] = live ? w * c[k].dD[q] : 0.0;
+  }
+  block_sum_store<kSensStats>(acc, scratch + (int64_t)blockIdx.z * per_job +
+                                       ((int64_t)blockIdx.y * tiles_max + blockIdx.x) * kSensStats);
+}
+
+// grid (ART_SENS_DOUBLES, 1 + the largest M, jobs): workgroup (q, r, j) folds entry q of row r of job j's table in tile order
+__global__ __launch_bounds__(kFoldBlock) void k_sensitivities_fold(const ArtSensitivityJob* __restrict__ jobs,
+                                                                   const int64_t per_job, const int64_t tiles_max,
+                                                                   const double* scratch, double* out) {
+  const int q = blockIdx.x, r = blockIdx.y, j = blockIdx.z;
+  if (r > ART_SENS_COLS * (jobs[j].n_elems + 1)) return;
+  double* dst = out + (sens_rows_before(jobs, j) + r) * ART_SENS_DOUBLES + q;
+  if (q >= (r == 0 ? kSensRow0 : kSensPerCol)) {
+    if (threadIdx.x == 0) *dst = 0.0;
+    return;
+  }
+  const int col = r == 0 ? 0 : r - 1;
+  const int y = (col / ART_SENS_COLS) * kSensParts + (col % ART_SENS_COLS) / kSensPerWg;   // (row 0: group 0, part 0)
+  const int slot = r == 0 ? q : kSensRow0 + kSensPerCol * (col % kSensPerWg) + q;
+  double v = 0.0;
+  fold_range(scratch + (int64_t)j * per_job + (int64_t)y * tiles_max * kSensStats + slot, 0, pol_tiles(jobs[j].n), RSUM, &v,
+             kSensStats);
+  if (threadIdx.x == 0) *dst = v;
+}
+
 // ------------------------------------------------------------------------------------------- vector focal spectrum
 // art_focal_vector_spectrum (include/art_hip.h): art_focal_spectrum's sum with a complex amplitude per (ray, wavenumber,
 // component), the field of art_polarisation carried through coatings whose optical constants depend on the wavenumber.
@@ -4536,6 +4704,26 @@ int art_polarisation(const ArtPolarisationJob* jobs_dev, const ArtPolarisationJo
   return launched("art_polarisation launch");
 }
 
+// the elements of a ray-tube or sensitivity job (host copies): kinds the transport of art_tubes.h covers; `who` opens the message
+static int tube_check_elems(const char* who, const ArtElementDesc* elems, const ArtQuadricDesc* quadrics, const int n_elems) {
+  for (int e = 0; e < n_elems; ++e) {
+    const ArtElementDesc& el = elems[e];
+    char msg[96];
+    if (el.kind < 0 || el.kind >= ART_NUM_KINDS) return fail(ART_ERR_BAD_ARG, "unknown optic kind");
+    const char* why = (el.flags & ART_FLAG_GRATING)    ? "is a grating"
+                      : (el.flags & ART_FLAG_FREEFORM) ? "is a freeform"
+                      : (el.n_defects > 0 || el.n_grid > 0 || (el.flags & (ART_FLAG_PERTURBED_NORMAL | ART_FLAG_ZERN_RECURRENCE)))
+                          ? "has defects"
+                          : nullptr;
+    if (why) {
+      snprintf(msg, sizeof msg, "%s: element %d %s", who, e, why);
+      return fail(ART_ERR_UNSUPPORTED, msg);
+    }
+    if ((el.flags & ART_FLAG_QUADRIC) && !quadrics) return fail(ART_ERR_BAD_ARG, "a quadric element without the quadrics table");
+  }
+  return ART_OK;
+}
+
 // validates a ray-tube job table (host copies of the elements included); *nmax: the largest slot count
 static int tube_check_jobs(const ArtTubeJob* jobs, int32_t n_jobs, int64_t* nmax) {
   if (!jobs) return fail(ART_ERR_BAD_ARG, "ray-tube job table is NULL");
@@ -4558,21 +4746,8 @@ static int tube_check_jobs(const ArtTubeJob* jobs, int32_t n_jobs, int64_t* nmax
       }
       if (!finite || !(fabs(nn - 1.0) <= 1e-12)) return fail(ART_ERR_BAD_ARG, "a ray-tube job's detector needs a finite centre and a unit normal");
     }
-    for (int e = 0; e < jb.n_elems; ++e) {
-      const ArtElementDesc& el = jb.elems[e];
-      char msg[96];
-      if (el.kind < 0 || el.kind >= ART_NUM_KINDS) return fail(ART_ERR_BAD_ARG, "unknown optic kind");
-      const char* why = (el.flags & ART_FLAG_GRATING)    ? "is a grating"
-                        : (el.flags & ART_FLAG_FREEFORM) ? "is a freeform"
-                        : (el.n_defects > 0 || el.n_grid > 0 || (el.flags & (ART_FLAG_PERTURBED_NORMAL | ART_FLAG_ZERN_RECURRENCE)))
-                            ? "has defects"
-                            : nullptr;
-      if (why) {
-        snprintf(msg, sizeof msg, "ray tubes: element %d %s", e, why);
-        return fail(ART_ERR_UNSUPPORTED, msg);
-      }
-      if ((el.flags & ART_FLAG_QUADRIC) && !jb.quadrics) return fail(ART_ERR_BAD_ARG, "a quadric element without the quadrics table");
-    }
+    const int bad = tube_check_elems("ray tubes", jb.elems, jb.quadrics, jb.n_elems);
+    if (bad) return bad;
     *nmax = jb.n > *nmax ? jb.n : *nmax;
   }
   return ART_OK;
@@ -4596,6 +4771,64 @@ int art_ray_tubes(const ArtTubeJob* jobs_dev, const ArtTubeJob* jobs_host, int32
   hipLaunchKernelGGL(k_ray_tubes_fold, dim3(ART_TUBE_DOUBLES, n_jobs), dim3(kFoldBlock), 0, s, jobs_dev, per_job,
                      (const double*)scratch, out);
   return launched("art_ray_tubes launch");
+}
+
+// validates a sensitivity job table (host copies of the elements included); *nmax, *kmax: the largest slot and element
+// counts, *rows: the rows of all tables
+static int sens_check_jobs(const ArtSensitivityJob* jobs, int32_t n_jobs, int64_t* nmax, int* kmax, int64_t* rows) {
+  if (!jobs) return fail(ART_ERR_BAD_ARG, "sensitivity job table is NULL");
+  if (n_jobs < 1 || n_jobs > ART_TUBE_MAX_JOBS) return fail(ART_ERR_BAD_ARG, "n_jobs must be in 1..ART_TUBE_MAX_JOBS");
+  *nmax = 0;
+  *kmax = 0;
+  *rows = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const ArtSensitivityJob& jb = jobs[j];
+    if (jb.n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+    if (jb.n > kMaxRaysPerLaunchHw) return fail(ART_ERR_UNSUPPORTED, "more than 2^28 rays per chain in one sensitivity call");
+    if (jb.n_elems < 1 || jb.n_elems > ART_TUBE_MAX_ELEMS)
+      return fail(ART_ERR_BAD_ARG, "a sensitivity job must have 1..ART_TUBE_MAX_ELEMS elements");
+    if (!jb.views || !jb.elems) return fail(ART_ERR_BAD_ARG, "a sensitivity job's views or elems is NULL");
+    double nn = 0.0;
+    bool finite = true;
+    for (int q = 0; q < 3; ++q) {
+      nn += jb.det.normal[q] * jb.det.normal[q];
+      finite = finite && isfinite(jb.det.centre[q]) && isfinite(jb.det.normal[q]) && isfinite(jb.origin[q]);
+    }
+    for (int q = 0; q < 9; ++q) finite = finite && isfinite(jb.det.rot[q]);
+    if (!finite || !(fabs(nn - 1.0) <= 1e-12))
+      return fail(ART_ERR_BAD_ARG, "a sensitivity job needs a detector (finite centre and rot, unit normal) and a finite origin");
+    const int bad = tube_check_elems("sensitivities", jb.elems, jb.quadrics, jb.n_elems);
+    if (bad) return bad;
+    *nmax = jb.n > *nmax ? jb.n : *nmax;
+    *kmax = jb.n_elems > *kmax ? jb.n_elems : *kmax;
+    *rows += 1 + ART_SENS_COLS * (jb.n_elems + 1);
+  }
+  return ART_OK;
+}
+
+int64_t art_sensitivities_scratch_doubles(const ArtSensitivityJob* jobs_host, int32_t n_jobs) {
+  int64_t nmax, rows;
+  int kmax;
+  const int rc = sens_check_jobs(jobs_host, n_jobs, &nmax, &kmax, &rows);
+  return rc ? rc : (int64_t)n_jobs * (kmax + 1) * kSensParts * pol_tiles(nmax) * kSensStats;
+}
+
+int art_sensitivities(const ArtSensitivityJob* jobs_dev, const ArtSensitivityJob* jobs_host, int32_t n_jobs, double* scratch,
+                      double* out, void* stream) {
+  if (!jobs_dev || !scratch || !out) return fail(ART_ERR_BAD_ARG, "NULL argument");
+  int64_t nmax, rows;
+  int kmax;
+  const int rc = sens_check_jobs(jobs_host, n_jobs, &nmax, &kmax, &rows);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t tiles = pol_tiles(nmax);
+  const int groups = (kmax + 1) * kSensParts;
+  const int64_t per_job = (int64_t)groups * tiles * kSensStats;
+  hipLaunchKernelGGL(k_sensitivities, dim3((unsigned)tiles, groups, n_jobs), dim3(kBlock), 0, s, jobs_dev, per_job, tiles,
+                     scratch);
+  hipLaunchKernelGGL(k_sensitivities_fold, dim3(ART_SENS_DOUBLES, 1 + ART_SENS_COLS * (kmax + 1), n_jobs), dim3(kFoldBlock), 0,
+                     s, jobs_dev, per_job, tiles, (const double*)scratch, out);
+  return launched("art_sensitivities launch");
 }
 
 // the wavenumber blocks of art_focal_vector_spectrum: slices S of the rays (never from the block: the same bytes for any),

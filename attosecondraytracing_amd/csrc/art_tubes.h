@@ -270,4 +270,158 @@ ART_HD void readout(const Tube& T, const double* D, const double* P, const bool 
   for (int q = 0; q < 3; ++q) R.axis[q] = e1 * v1[q] + e2 * v2[q];
 }
 
+// ------------------------------------------------------------------------------------------- alignment sensitivities
+// art_sensitivities (include/art_hip.h): the same transport differentiates a ray with respect to a rigid motion of one
+// element or of the source.  A column is the state (dP, dD, dL) of one degree of freedom, dL the change of the path.
+// Element k's surface point at X moves by the field s(X); r_0, r_1, r_2 are the rows of its fwd (major axis,
+// normal x major, normal):
+//   columns 0..2  shift along r_i              s = r_i              theta = 0
+//   columns 3..5  rotation about r_i at pos    s = r_i x (X - pos)  theta = r_i      (per radian)
+// At the element that moves, with a = dP + t dD as in step:
+//   dt = -n . (a - s(P)) / (n . D),  dQ = a + D dt,  dn = dn_surf(dQ - s(P)) + theta x n   (dn_surf: step's rule)
+//   dD' = dD - 2 [(dD . n + D . dn) n + (D . n) dn],  dP' = dQ,  dL += dt
+// (the leg's length changes by D . (dQ - dP_prev) = dt, because D . dD = 0).  Every other element is the same with
+// s = theta = 0: step plus the path term.  The source's columns: 0..2 shifts along lab x, y, z (dP = e_i), 3..5 tilts
+// about them with the points held (dD = e_i x D0).  On the detector (centre C, unit normal nd, rot) the transport onto its
+// plane gives dX_lab and dL += dt; (dX, dY) = (rot dX_lab)[0:2].
+struct Column {
+  double dP[3], dD[3], dL;
+};
+
+// What every column of a ray shares at one element: the unit normal and the Hessian in the LAB frame (Hl = fwd^T H fwd:
+// h00, h11, h22, h01, h02, h12 -- formed once, so that a column needs no rotation there and back), 1 / |g|, the leg t and
+// the two products with the incoming direction
+struct Hit {
+  double n[3], Hl[6], ig, t, Dn, inD;
+};
+
+ART_HD void clear(Column& c) {
+#pragma unroll
+  for (int q = 0; q < 3; ++q) c.dP[q] = c.dD[q] = 0.0;
+  c.dL = 0.0;
+}
+
+// column i (0..5) of the source group; D0 the source direction
+ART_HD void seed_source(const int i, const double* D0, Column& c) {
+  clear(c);
+  const int m = i % 3;                                    // (selects: no indexed access to registers)
+  const double e[3] = {m == 0 ? 1.0 : 0.0, m == 1 ? 1.0 : 0.0, m == 2 ? 1.0 : 0.0};
+  if (i < 3) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) c.dP[q] = e[q];
+  } else {
+    cross(e, D0, c.dD);
+  }
+}
+
+// column i (0..5) of the element s at the lab point P: the motion field sv = s(P) and the rotation vector th
+ART_HD void motion(const Surface& s, const int i, const double* P, double* sv, double* th) {
+  const int m = i % 3;
+  double r[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) r[q] = m == 0 ? s.fwd[q] : (m == 1 ? s.fwd[3 + q] : s.fwd[6 + q]);
+  if (i < 3) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { sv[q] = r[q]; th[q] = 0.0; }
+  } else {
+    const double rel[3] = {P[0] - s.pos[0], P[1] - s.pos[1], P[2] - s.pos[2]};
+    cross(r, rel, sv);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) th[q] = r[q];
+  }
+}
+
+// D the incoming direction, Pprev the previous point, P the hit point, all lab frame (the first lines of step)
+ART_HD void hit_of(const Surface& s, const double* D, const double* Pprev, const double* P, Hit& h) {
+  const double rel[3] = {P[0] - s.pos[0], P[1] - s.pos[1], P[2] - s.pos[2]};
+  double Po[3], g[3], no[3];
+  rot(s.fwd, rel, Po);
+  Po[0] += s.centre[0]; Po[1] += s.centre[1]; Po[2] += s.centre[2];
+  gradient(s, Po, g);
+  h.ig = 1.0 / sqrt(dot(g, g));
+  no[0] = -g[0] * h.ig; no[1] = -g[1] * h.ig; no[2] = -g[2] * h.ig;
+  rot_t(s.fwd, no, h.n);
+  // Hl_ab = f_a . H f_b with f_a the columns of fwd (the lab axes seen in the optic frame)
+  double Hf[3][3];
+#pragma unroll
+  for (int b = 0; b < 3; ++b) {
+    const double f[3] = {s.fwd[b], s.fwd[3 + b], s.fwd[6 + b]};
+    hessian_apply(s, Po, f, Hf[b]);
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const int a = k < 3 ? k : (k == 5 ? 1 : 0), b = k < 3 ? k : (k == 3 ? 1 : 2);
+    h.Hl[k] = s.fwd[a] * Hf[b][0] + s.fwd[3 + a] * Hf[b][1] + s.fwd[6 + a] * Hf[b][2];
+  }
+  const double leg[3] = {P[0] - Pprev[0], P[1] - Pprev[1], P[2] - Pprev[2]};
+  h.t = dot(leg, D);
+  h.Dn = dot(D, h.n);
+  h.inD = 1.0 / h.Dn;
+}
+
+// One column through an element; kMoves: the element moves by (sv, th) = motion(...), else both are ignored
+template <bool kMoves>
+ART_HD void step_column(const Surface& s, const Hit& h, const double* D, const double* sv, const double* th, Column& c) {
+  double a[3], v[3], dQ[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    a[q] = c.dP[q] + h.t * c.dD[q];
+    v[q] = kMoves ? a[q] - sv[q] : a[q];
+  }
+  const double dt = -dot(h.n, v) * h.inD;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    dQ[q] = a[q] + D[q] * dt;
+    v[q] = kMoves ? dQ[q] - sv[q] : dQ[q];
+  }
+  if (!s.mask) {
+    const double Hv[3] = {h.Hl[0] * v[0] + h.Hl[3] * v[1] + h.Hl[4] * v[2], h.Hl[3] * v[0] + h.Hl[1] * v[1] + h.Hl[5] * v[2],
+                          h.Hl[4] * v[0] + h.Hl[5] * v[1] + h.Hl[2] * v[2]};
+    const double nHv = dot(h.n, Hv);
+    double dn[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) dn[q] = -(Hv[q] - h.n[q] * nHv) * h.ig;
+    if (kMoves) {
+      double tn[3];
+      cross(th, h.n, tn);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) dn[q] += tn[q];
+    }
+    const double k = dot(c.dD, h.n) + dot(D, dn);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) c.dD[q] -= 2.0 * (k * h.n[q] + h.Dn * dn[q]);
+  }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) c.dP[q] = dQ[q];
+  c.dL += dt;
+}
+
+// One column through the element that moves by (sv, th) = motion(...)
+ART_HD void step_moved(const Surface& s, const Hit& h, const double* D, const double* sv, const double* th, Column& c) {
+  step_column<true>(s, h, D, sv, th, c);
+}
+
+// One column through an element that stays: step's rule plus the path term
+ART_HD void step_path(const Surface& s, const Hit& h, const double* D, Column& c) {
+  step_column<false>(s, h, D, nullptr, nullptr, c);
+}
+
+// Behind the last element: D the final direction, P the last hit point, the detector (centre C, unit normal nd, rot).
+// dX, dY: the change of the detector coordinates; c.dL gains the last leg's term; c.dP becomes dX_lab, c.dD stays dD'.
+ART_HD void readout_column(const double* D, const double* P, const double* C, const double* nd, const double* rotm,
+                           Column& c, double& dX, double& dY) {
+  const double toC[3] = {C[0] - P[0], C[1] - P[1], C[2] - P[2]};
+  const double inD = 1.0 / dot(nd, D), t = dot(nd, toC) * inD;
+  double a[3], r[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) a[q] = c.dP[q] + t * c.dD[q];
+  const double dt = -dot(nd, a) * inD;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) c.dP[q] = a[q] + D[q] * dt;
+  c.dL += dt;
+  rot(rotm, c.dP, r);
+  dX = r[0];
+  dY = r[1];
+}
+
 }  // namespace artt

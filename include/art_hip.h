@@ -681,6 +681,59 @@ int64_t art_ray_tubes_scratch_doubles(const ArtTubeJob* jobs_host, int32_t n_job
 int art_ray_tubes(const ArtTubeJob* jobs_dev, const ArtTubeJob* jobs_host, int32_t n_jobs, double* scratch,
                   double* out /* DEVICE [n_jobs][ART_TUBE_DOUBLES] */, void* stream);
 
+/* Alignment sensitivities of MANY traced chains in one call (added under ABI 14: ArtSensitivityJob, art_sensitivities,
+ * art_sensitivities_scratch_doubles): the derivative of every ray's detector coordinates, path and final direction with
+ * respect to a rigid motion of each element and of the source, by art_ray_tubes' transport in one streaming pass over
+ * the chain's existing history; nothing is re-traced.  Groups g = 0 (the source) and g = 1..K (element g - 1) of
+ * ART_SENS_COLS = 6 columns each, column c = 6 g + i, M = 6 (K + 1):
+ *   source   i = 0..2 shift along lab x, y, z (dP = e_i, dD = 0); i = 3..5 tilt about lab x, y, z with the points held
+ *            (dP = 0, dD = e_i x D0), per radian
+ *   element  with r_0, r_1, r_2 the rows of its fwd (major axis, normal x major, normal): i = 0..2 shift along r_i, the
+ *            surface point at X moves by s(X) = r_i; i = 3..5 rotation about r_i through pos, s(X) = r_i x (X - pos),
+ *            theta = r_i, per radian (roll, pitch, yaw of the optic as a rigid body)
+ * At the element that moves (t, a, n, dn_surf as for art_ray_tubes):
+ *   dt = -n.(a - s(P)) / (n.D),  dQ = a + D dt,  dn = dn_surf(dQ - s(P)) + theta x n,
+ *   dD' = dD - 2 [(dD.n + D.dn) n + (D.n) dn],  dP' = dQ,  dL += dt
+ * and at every other element the same with s = theta = 0 (a mask: dD unchanged).  On the detector (centre C, unit normal
+ * nd, rot) the transport onto its plane gives dX_lab and dL += dt; (dX, dY) = (rot dX_lab)[0:2].  First order only; the
+ * set of counted rays is the nominal trace's (alive in EVERY view): vignetting that changes with the motion is not
+ * differentiated.  Per ray X, Y = (rot (Q - C))[0:2] - origin[0:2] with Q the hit point on the detector plane, and
+ * L = path of the last view + nd.(C - P) / (nd.D) - origin[2]: the caller passes the weighted means as origin so that
+ * the products below do not cancel.
+ * out (DEVICE, written): the jobs' tables one after another, job j's [1 + M_j][ART_SENS_DOUBLES] behind those of the jobs
+ * before it; sums over the counted rays with the weights w (NULL: 1):
+ *   row 0      [0] count [1] sum w [2] sum w X [3] sum w Y [4] sum w L [5] sum w X^2 [6] sum w Y^2 [7] sum w L^2 [8..15] 0
+ *   row 1 + c  [0] sum w dX [1] sum w dY [2] sum w dL [3] sum w X dX [4] sum w Y dY [5] sum w L dL [6] sum w dX^2
+ *              [7] sum w dY^2 [8] sum w dL^2 [9..11] sum w dD' (lab x, y, z) [12..15] 0
+ * The optional arrays dX, dY, dL (DEVICE [M][n] each, or NULL) receive the per-ray values, NaN for the rays that do not
+ * count.  Fixed summation order, no float atomics; a job's slicing depends on its own n only: every job gets the same
+ * bytes whichever jobs share its call.  jobs_dev / jobs_host and the element tables: as for art_ray_tubes.
+ * scratch: DEVICE, art_sensitivities_scratch_doubles(jobs_host, n_jobs): 80 doubles per job, group and tile of 256
+ * slots, sized by the call's largest K and n (12.5 B per slot at K = 4).
+ * Limits: 1 <= n_jobs <= ART_TUBE_MAX_JOBS, 0 <= n <= 2^28 (ART_ERR_UNSUPPORTED beyond), 1 <= n_elems <=
+ * ART_TUBE_MAX_ELEMS, views, elems, out and scratch non-NULL, quadrics non-NULL where an element has ART_FLAG_QUADRIC, a
+ * finite origin and detector centre, a unit detector normal: ART_ERR_BAD_ARG otherwise.  ART_ERR_UNSUPPORTED: the
+ * elements art_ray_tubes refuses (defects, gratings, freeforms).  Nothing is launched on failure.                     */
+#define ART_SENS_DOUBLES 16
+#define ART_SENS_COLS 6
+typedef struct ArtSensitivityJob {
+  const ArtBundleView* views;      /* DEVICE array of n_elems + 1 views: the source, then the bundle after each element */
+  const ArtElementDesc* elems;     /* n_elems descriptors (DEVICE in jobs_dev, HOST in jobs_host)                       */
+  const ArtQuadricDesc* quadrics;  /* n_elems entries, read where ART_FLAG_QUADRIC is set; may be NULL without any      */
+  int32_t n_elems;                 /* K                                                                                 */
+  int32_t reserved;
+  int64_t n;                       /* slots of every view                                                               */
+  ArtDetectorDesc det;             /* required: centre, unit normal, rot                                                */
+  const double* w;                 /* DEVICE weights [n] or NULL (all 1)                                                */
+  double origin[3];                /* X0, Y0, L0                                                                        */
+  double* dX;                      /* DEVICE [6 (K + 1)][n] or NULL; likewise the next two                              */
+  double* dY;
+  double* dL;
+} ArtSensitivityJob;
+int64_t art_sensitivities_scratch_doubles(const ArtSensitivityJob* jobs_host, int32_t n_jobs);
+int art_sensitivities(const ArtSensitivityJob* jobs_dev, const ArtSensitivityJob* jobs_host, int32_t n_jobs,
+                      double* scratch, double* out, void* stream);
+
 /* Vector focal fields of a pulse behind dispersive coatings (added under ABI 14: ArtFocalVectorSpectrumDesc,
  * art_focal_vector_spectrum, art_focal_vector_spectrum_scratch_doubles): art_focal_spectrum's sum with the complex
  * vector field of art_polarisation, evaluated per ray AND per wavenumber, as each ray's amplitude.  With
