@@ -168,13 +168,20 @@ class Detector:
 
     def _scan_moments(self, RayList, span=0.0):
         """Moment sums from which spot size and duration follow at ANY shift of this detector along its normal
-        (art_detector_scan_moments).  Two passes over the bundle: the first only finds the mean path used to centre
-        the second."""
+        (art_detector_scan_moments).  Two passes over the bundle: the first only finds the means used to centre the
+        second -- the mean path, and the mean hit: the second pass reads X and Y about it (the descriptor's centre is moved
+        IN the detector plane; variances do not depend on the origin, the plane and the kinks stay), so that the sums do
+        not cancel when the spot lies far from Detector.centre."""
         self._iscomplete()
         B = RayBundle.of(RayList)
         be, n, d = B.backend, B.n_slots, self._desc()
         first = be.detector_scan_moments(d, B.view(), B.intensity, n, 0.0)
         co = first[11] / first[0]
+        mx, my = first[1] / first[0], first[6] / first[0]
+        if np.isfinite(mx) and np.isfinite(my):
+            rot = d.rot
+            for k in range(3):                                   # rot^T (mx, my, 0): rows 0 and 1 of rot span the plane
+                d.centre[k] += rot[k] * mx + rot[3 + k] * my
         m = be.detector_scan_moments(d, B.view(), B.intensity, n, co, span)
         # "kinked": some ray's hit changes side of its origin within the span -> its path |t| is not linear there
         return {"m": m, "co": co, "kinked": bool(m[32] > 0)}

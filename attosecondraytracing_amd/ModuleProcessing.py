@@ -852,12 +852,16 @@ def _optimise_many(items, OptFor, Amplitude, Precision, IntensityWeighted, verbo
     per bundle), A_k = Amplitude 0.1^k, k <= Precision; the best position of a level is the centre of the next.
 
     One set of moments serves every level.  The variances it yields, (qq + 2 s qs + s^2 ss) / m0 - mean^2, are quadratics
-    in s evaluated near their minimum: their terms are of the size N X0^2 of the START pose and cancel down to N sigma^2 at
-    the focus, so a variance carries an absolute error of ~1e-16 X0^2 -- against differences between neighbouring positions
-    of the finest level of ~ss (1e-4 A)^2 ~ 1e-8 X0^2 (X0 ~ slope x amplitude): eight orders of room.  Shifting the
-    moments to a level's centre first (q' = q + s0 sq, ...) would bake the same rounding into q', qq'; it is the quadratic
-    itself that cancels.  tests/test_host_shell.py::test_autofocus_of_a_tight_focus checks the chosen positions of a
-    sub-micrometre focus against a position-by-position evaluation.
+    in s evaluated near their minimum.  Their sums are taken about provisional centres INSIDE the spot -- the mean ray's hit
+    for X and Y, the mean ray's path for the optical path (art_analyse_bundles) -- so their terms are of the size
+    N (sqrt V0 + |s| sqrt Vs)^2, V0 the variance at the start pose and Vs the mean square of the slopes, wherever the
+    detector's centre lies, and cancel down to N sigma^2 at the focus.  tests/test_readout_truth_host.py and
+    tests/test_gpu_readout_truth.py hold every variance, on detectors centred up to 100 mm from the spot and shifted by up to
+    5 mm, to 2e-6 of a long-double truth + 16 eps (sqrt V0 + |s| sqrt Vs)^2 (tests/readout_truth_common.py) -- against
+    differences between neighbouring positions of the finest level of ~Vs (1e-4 A)^2.  Shifting the moments to a level's
+    centre first (q' = q + s0 sq, ...) would bake the same rounding into q', qq'; it is the quadratic itself that cancels.
+    tests/test_host_shell.py::test_autofocus_of_a_tight_focus checks the chosen positions of a sub-micrometre focus against
+    a position-by-position evaluation.
 
     announce=False: the "no minimum in the searched range" remark is not printed here; every result gets a fourth entry
     (remark due?, lower end, upper end of the searched range) and the caller of a LIST prints under the chain it belongs to."""

@@ -36,6 +36,7 @@ class BundleAnalysis:
     kink_above = property(lambda self: self.row[54])      # smallest shift > 0
     max_angle = property(lambda self: self.row[55])
     bbox = property(lambda self: self.row[56:62])         # min X, max X, min Y, max Y, min opl, max opl at shift 0
+    cxy = property(lambda self: self.row[62:64].copy())   # the point the X, Y moments are taken about (detector coordinates)
 
     def mean_point(self):
         return self.row[1:4] / self.row[0]

@@ -1285,12 +1285,15 @@ ART_HD void rotation_to_ez(const double* a, double* M) {
 }
 
 // sums9 = count, sum point (3), sum vector (3), sum w, sum path.  Fills the detector (centre, normal, rot), its
-// reference point, the mean direction (unit) and the provisional path centre co.  mode: ArtJobMode (0 autoplace, 1 manual).
+// reference point, the mean direction (unit), the provisional path centre co and the provisional centre cxy of the
+// second moments of (X, Y): the detector coordinates of the MEAN RAY's hit (0 when auto-placing: the detector's centre is
+// that hit).  Variances do not depend on the centre their sums are taken about; sums taken about a point inside the spot
+// do not cancel, however far from the spot the user put Detector.centre.  mode: ArtJobMode (0 autoplace, 1 manual).
 // The sequence of normalisations is the reference's: FindCentralRay's mean vector goes through the Ray.vector setter
 // (ART/ModuleOpticalRay.py:85-90), its negative through the Detector.normal setter (ART/ModuleDetector.py:57-66).
-ART_HD void analysis_place(const double* sums9, int mode, double distance, const double* centre_in,
-                           const double* normal_in, const double* refpoint_in, ArtDetectorDesc& d, double* refpoint,
-                           double* axis, double& co) {
+ART_HD void analysis_place_centred(const double* sums9, int mode, double distance, const double* centre_in,
+                                   const double* normal_in, const double* refpoint_in, ArtDetectorDesc& d, double* refpoint,
+                                   double* axis, double& co, double* cxy) {
   const double cnt = sums9[0];
   const double px = sums9[1] / cnt, py = sums9[2] / cnt, pz = sums9[3] / cnt;
   double vx = sums9[4] / cnt, vy = sums9[5] / cnt, vz = sums9[6] / cnt;
@@ -1313,10 +1316,25 @@ ART_HD void analysis_place(const double* sums9, int mode, double distance, const
     refpoint[0] = px; refpoint[1] = py; refpoint[2] = pz;
   }
   rotation_to_ez(d.normal, d.rot);
-  // the mean ray's distance to the detector plane: within a fraction of a millimetre of the mean of |I - A| over the rays
+  // the mean ray's distance to the detector plane over vl = |mean vector| = <cos(angle to the mean ray)>: the mean of
+  // |I - A| over the rays to second order in their angles (each ray travels distance / cos)
   const double num = dot3(d.normal[0], d.normal[1], d.normal[2], d.centre[0] - px, d.centre[1] - py, d.centre[2] - pz);
   const double den = dot3(vx, vy, vz, d.normal[0], d.normal[1], d.normal[2]);
-  co = sums9[8] / cnt + fabs(num / den);
+  const double t = num / den;
+  co = sums9[8] / cnt + fabs(t) / vl;
+  cxy[0] = 0.0; cxy[1] = 0.0;
+  if (mode == 1) {
+    double rx, ry, rz;
+    mat3_apply(d.rot, fma(t, vx, px) - d.centre[0], fma(t, vy, py) - d.centre[1], fma(t, vz, pz) - d.centre[2], rx, ry, rz);
+    cxy[0] = rx; cxy[1] = ry;
+  }
+}
+// The placement alone, for callers that take no (X, Y) moments (the signature this function had before cxy existed).
+ART_HD void analysis_place(const double* sums9, int mode, double distance, const double* centre_in,
+                           const double* normal_in, const double* refpoint_in, ArtDetectorDesc& d, double* refpoint,
+                           double* axis, double& co) {
+  double cxy[2];
+  analysis_place_centred(sums9, mode, distance, centre_in, normal_in, refpoint_in, d, refpoint, axis, co, cxy);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -3147,7 +3147,7 @@ __global__ __launch_bounds__(64) void k_trace_guides(const GuideArgs ga, double*
 // ------------------------------------------------------------------------------------------- batched analysis
 // art_analyse_bundles: blockIdx.y = job.  Partials per job and workgroup, folded in a fixed order.
 constexpr int kAnaMom = 42;      // 32 moment sums, kink shifts (2), max angle, bounding box + path range (6), pad
-constexpr int kAnaPlace = 24;    // per job: ArtDetectorDesc (15 doubles), axis (3), co, pad
+constexpr int kAnaPlace = 24;    // per job: ArtDetectorDesc (15 doubles), axis (3), co, cx, cy, pad
 constexpr int kAnaBlocks = 1024; // workgroups per job of the moments pass at most
 constexpr int kAnaSumsPad = 16;  // doubles per job of the folded sums (9 used)
 // Workgroups per job of the moments pass: a function of the ray count ALONE, so that a bundle's moments are folded in the
@@ -3233,9 +3233,9 @@ __global__ __launch_bounds__(64) void k_analysis_place(const ArtAnalysisJob* __r
   o[56] = INFINITY; o[57] = -INFINITY; o[58] = INFINITY; o[59] = -INFINITY; o[60] = INFINITY; o[61] = -INFINITY;
   if (jb.mode == ART_JOB_SUMS) return;
   ArtDetectorDesc d;
-  double ref[3], axis[3], co;
+  double ref[3], axis[3], co, cxy[2] = {0.0, 0.0};
   if (s_sum[0] > 0.0) {
-    art::analysis_place(s_sum, jb.mode, jb.distance, jb.centre, jb.normal, jb.refpoint, d, ref, axis, co);
+    art::analysis_place_centred(s_sum, jb.mode, jb.distance, jb.centre, jb.normal, jb.refpoint, d, ref, axis, co, cxy);
   } else {
     for (int k = 0; k < 3; ++k) { d.centre[k] = NAN; d.normal[k] = NAN; ref[k] = NAN; axis[k] = NAN; }
     for (int k = 0; k < 9; ++k) d.rot[k] = NAN;
@@ -3243,9 +3243,11 @@ __global__ __launch_bounds__(64) void k_analysis_place(const ArtAnalysisJob* __r
   }
   for (int k = 0; k < 3; ++k) { o[10 + k] = d.centre[k]; o[13 + k] = d.normal[k]; o[16 + k] = ref[k]; }
   o[19] = co;
+  o[62] = cxy[0]; o[63] = cxy[1];
   for (int k = 0; k < 3; ++k) { pl[k] = d.centre[k]; pl[3 + k] = d.normal[k]; pl[15 + k] = axis[k]; }
   for (int k = 0; k < 9; ++k) pl[6 + k] = d.rot[k];
   pl[18] = co;
+  pl[19] = cxy[0]; pl[20] = cxy[1];
 }
 
 // The moments pass keeps 42 accumulators (84 VGPRs) beside the ray: 128 VGPRs = 4 waves per SIMD, which is also all the
@@ -3262,7 +3264,7 @@ __device__ __forceinline__ void moments_body(const ArtAnalysisJob& jb, const int
   const Axis3 ax = {pl[15], pl[16], pl[17]};
   const double au = sqrt(art::dot3(ax.x, ax.y, ax.z, ax.x, ax.y, ax.z));      // |axis|: once, not per ray
   const double inv_nn = 1.0 / art::dot3(d.normal[0], d.normal[1], d.normal[2], d.normal[0], d.normal[1], d.normal[2]);
-  const double co = pl[18];
+  const double co = pl[18], cx = pl[19], cy = pl[20];      // (workgroup-uniform: scalar registers)
   const ArtBundleView b = jb.b;
   const double* w = jb.w;
   const int64_t stride = (int64_t)nblk * kBlock;
@@ -3298,6 +3300,8 @@ __device__ __forceinline__ void moments_body(const ArtAnalysisJob& jb, const int
     acc[33] = fmin(acc[33], (l && sk > 0.0) ? sk : INFINITY);
     const double t2 = tan2_half_angle_to_axis(ax, au, r.dx, r.dy, r.dz, un);
     acc[34] = fmax(acc[34], l ? t2 : 0.0);
+    // the moments about the mean ray's hit, not about Detector.centre (the bounding box above stays about the centre)
+    q0[0] -= cx; q0[1] -= cy;
     q0[2] -= co;
     sq[2] -= 1.0;
     const double ww = l ? wv : 0.0;

@@ -62,7 +62,7 @@ class SceneProgram:
     Results are bit-identical to `RayTracingCalculation`; the returned bundles are overwritten by the next `run()`."""
 
     def __init__(self, sources, element_lists, IgnoreDefects=True, post=None, capture=True, detectors=None, history=True,
-                 placement_tries=None, readout_lite=False, readout_targets=None, outputs=None):
+                 placement_tries=None, readout_lite=False, readout_targets=None, outputs=None, path_centres=None):
         from . import ModuleProcessing as mp
         from . import _abi
         from .bundle import RayBundle
@@ -89,6 +89,11 @@ class SceneProgram:
         # readout_targets: per chain None or (X, Y, opl) caller-owned tensors the fused read-out writes into -- e.g. the
         # dense sections of a survivor send buffer (sharding.SurvivorGather.acquire: zero-copy gather)
         self._ro_targets = list(readout_targets) if readout_targets is not None else None
+        # path_centres: per chain the provisional centre of the fused read-out's second moment of the path (statistic 18 and
+        # 21, Detector.readout's path_centre): a value near the mean optical path, e.g. that of the aligned setup
+        self._path_centres = [0.0] * self.c if path_centres is None else [float(v) for v in path_centres]
+        if len(self._path_centres) != self.c:
+            raise ValueError("need one path centre per chain")
         self.detectors, self.readouts = None, None
         if detectors is not None and self.n <= self.be.MAX_FUSED_READOUT_RAYS:
             if len(detectors) != self.c:
@@ -227,8 +232,8 @@ class SceneProgram:
             for ci, (d, s, area) in enumerate(zip(self.detectors, self.sources, self._ro_scratch)):
                 d._iscomplete()
                 kw = {} if (self._ro_targets is None or self._ro_targets[ci] is None) else {"targets": self._ro_targets[ci]}
-                self.readouts.append(self.be.new_chain_readout(d._desc(), s.intensity, self.n, scratch=area,
-                                                               lite=self._readout_lite, **kw))
+                self.readouts.append(self.be.new_chain_readout(d._desc(), s.intensity, self.n, (0.0, 0.0, self._path_centres[ci]),
+                                                               scratch=area, lite=self._readout_lite, **kw))
         else:
             for d, ro in zip(self.detectors, self.readouts):
                 d._iscomplete()
@@ -302,7 +307,7 @@ class SceneProgram:
                     b.touch()
             if self.readouts is not None:
                 self.readouts[ci].pop("stats", None)
-                self._mp._attach_readout(outs[-1], self.detectors[ci], 0.0, self.readouts[ci])
+                self._mp._attach_readout(outs[-1], self.detectors[ci], self._path_centres[ci], self.readouts[ci])
 
     def _launch(self):
         if self._stepwise:

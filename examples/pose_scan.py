@@ -41,7 +41,13 @@ aligned = chain.get_output_rays()
 detector = mdet.Detector(np.asarray(chain.optical_elements[-1].position, dtype=float))
 detector.autoplace(aligned[-1], focal)
 
-program = SceneProgram([chain.source_rays], [chain.optical_elements], detectors=[detector])
+# The statistics carry second moments about provisional centres handed in beforehand (include/art_hip.h): X and Y about
+# Detector.centre, which auto-placement put into the spot, the path about `path_centre` -- the aligned setup's mean path.
+# A variance is then sum (q - c)^2 / N - (mean - c)^2 with both terms of the size of the spread itself; about 0 the path's
+# two terms would be 1.7 m squared each and their difference, a few fs squared, would be rounding noise.
+first = detector.readout(aligned[-1], store=False)["stats"]
+path_centre = float(first[1] / first[0])
+program = SceneProgram([chain.source_rays], [chain.optical_elements], detectors=[detector], path_centres=[path_centre])
 light_speed = mdet.LightSpeed
 angles = np.linspace(-max_urad, max_urad, n_poses) * 1e-6
 spot, duration, alive = [], [], []
@@ -51,10 +57,10 @@ for a in angles:
     scanned.rotate_OE(2, "pitch", np.rad2deg(a))            # the reference's own manipulator (degrees)
     program.update([scanned.optical_elements])
     out = program.run()[0]
-    s = detector.readout(out[-1])["stats"]                  # the fused read-out's statistics: 24 doubles to the host
+    s = detector.readout(out[-1], path_centre=path_centre)["stats"]      # the fused read-out's statistics: 24 doubles to the host
     cnt = s[0]
-    var_xy = (s[16] + s[17]) / cnt - (s[6] / cnt) ** 2 - (s[7] / cnt) ** 2
-    var_o = s[18] / cnt - (s[1] / cnt) ** 2
+    var_xy = (s[16] + s[17]) / cnt - (s[6] / cnt) ** 2 - (s[7] / cnt) ** 2      # (about the detector's centre: (0, 0))
+    var_o = s[18] / cnt - (s[1] / cnt - path_centre) ** 2
     spot.append(np.sqrt(max(var_xy, 0.0)))
     duration.append(np.sqrt(max(var_o, 0.0)) / light_speed * 1e15)
     alive.append(cnt / rays)

@@ -76,8 +76,11 @@ if rank == 0:
     delays_fs = (path - path.mean()) / mdet.LightSpeed * 1e15           # Detector.get_Delays, ART/ModuleDetector.py:272-279
     print(f"gathered {number.numel()} survivor records ({sent} B per rank): delay std {float(delays_fs.std()):.4f} fs")
     count, mean_path = s[0], s[1] / s[0]
-    var_x = s[16] / count - (s[6] / count) ** 2
-    var_y = s[17] / count - (s[7] / count) ** 2
+    # statistics 16 and 17 are second moments about (cx, cy) = (0, 0), the detector's centre: sum (q - c)^2 / N - (mean - c)^2.
+    # Auto-placement on the aligned bundle put that centre into the spot, so neither term is larger than the spread itself
+    # (a detector centred elsewhere needs its centres handed to the read-out, or analysis.analyse, which finds its own).
+    var_x = s[16] / count - (s[6] / count - 0.0) ** 2
+    var_y = s[17] / count - (s[7] / count - 0.0) ** 2
     print(f"{world} GPU(s), {n_total} rays: {int(count)} reach the detector ({100 * count / n_total:.2f} %), mean optical "
           f"path {mean_path:.6f} mm, spot std {np.sqrt(var_x + var_y) * 1e3:.3f} um, sample for plots: {tuple(sample.shape)}")
 dist.barrier()

@@ -970,8 +970,12 @@ int art_trace_guides(const ArtElementDesc* elems, int32_t count, double* rays, u
  *   2. the detector: given (mode ART_JOB_MANUAL) or placed like Detector.autoplace -- normal = -(mean vector, normalised),
  *      centre = mean point - normal * distance, refpoint = mean point; its rotation normal -> ez with the reference's
  *      special cases (ModuleGeometry.py:333-343); the provisional path centre co = mean path + the mean ray's distance
- *      to the detector (within a fraction of a millimetre of the mean optical path: second moments about it are well
- *      conditioned, so no pass is spent on finding the exact mean);
+ *      to the detector / |mean vector| (|mean vector| is the rays' mean cosine to the mean ray, so this is their mean
+ *      distance to second order in their angles; within a fraction of a millimetre of the mean optical path in any case),
+ *      and the provisional centre (cx, cy) of X and Y: the detector coordinates of the point where the mean ray meets
+ *      the detector (exactly 0 when auto-placing: the detector's centre IS that point).  Second moments about centres
+ *      inside the spot are well conditioned wherever the caller put the detector's centre, so no pass is spent on
+ *      finding the exact means;
  *   3. ONE pass of read-out moments on that detector: the 32 sums of art_detector_scan_moments (the read-out of every ray
  *      is linear in a shift s of the detector along its normal, so spot size and duration at ANY s follow from them --
  *      a whole autofocus search without touching the bundle again), the bounding box of (X, Y) and the range of the
@@ -983,11 +987,16 @@ int art_trace_guides(const ArtElementDesc* elems, int32_t count, double* rays, u
  * hold the same contents).  out: DEVICE, n_jobs x ART_ANALYSIS_DOUBLES doubles, job-major:
  *   [0] count  [1..3] sum point  [4..6] sum vector  [7] sum w (= count if w is NULL)  [8] sum path  [9] 0
  *   [10..12] detector centre  [13..15] detector normal  [16..18] refpoint (mean point; manual: job.refpoint)  [19] co
- *   [20..51] the 32 moment sums of art_detector_scan_moments (path centred on co)  [52] 0
+ *   [20..51] the 32 moment sums of art_detector_scan_moments, taken of X - cx, Y - cy and opl - co: per weighting (unweighted
+ *            at [20], weighted at [36]) sum w, then for each of the three coordinates q with slope q' = dq/ds (opl: dq/ds - 1)
+ *            sum w q, sum w q', sum w q q, sum w q q', sum w q' q'.  Variances do not depend on the centres; a MEAN read off
+ *            these sums is about them: mean X = cx + [21] / [20], mean opl = co + [31] / [20]                        [52] 0
  *   [53] largest shift s <= 0 and [54] smallest shift s > 0 at which a ray's t changes sign (-inf / +inf if none)
  *   [55] largest angle to the mean vector (rad)
- *   [56] min X [57] max X [58] min Y [59] max Y [60] min opl [61] max opl   (s = 0; +inf / -inf if nothing is alive)
- *   [62..63] 0
+ *   [56] min X [57] max X [58] min Y [59] max Y [60] min opl [61] max opl   (s = 0; +inf / -inf if nothing is alive;
+ *            X and Y about the detector's centre, NOT about (cx, cy))
+ *   [62] cx  [63] cy   (0 for ART_JOB_SUMS and for a job without alive rays; these two slots were reserved and read 0
+ *            before: row size, structs and symbols are unchanged, so ART_ABI_VERSION stays)
  * One call covers bundles of n <= 2^28 slots (ART_ERR_UNSUPPORTED beyond: 32-bit buffer offsets, as in the tracing launches).
  * A job without alive rays gets count 0, NaN detector fields and zero moments.  A manual detector's normal must be a unit
  * vector (| |normal|^2 - 1 | <= 1e-12, ART_ERR_BAD_ARG otherwise); a manual detector parallel to the mean ray (mean vector .

@@ -726,21 +726,22 @@ def find_optimal_distance(D: Detector, B: Bundle, opt_for="intensity", amplitude
     return D, spot, dur
 
 
-def analysis_row(B: Bundle, D: Detector, co: float, axis=None):
+def analysis_row(B: Bundle, D: Detector, co: float, axis=None, cxy=(0.0, 0.0)):
     """What art_analyse_bundles (include/art_hip.h) reports for bundle B on detector D, restated from the REFERENCE's
     definitions only (no kernel code): the sums of FindCentralRay / getETransmission (ART/ModuleProcessing.py:464-482,
     ART/ModuleAnalysisAndPlots.py:62-77), the read-out of ART/ModuleDetector.py:191-279 at the detector and at the detector
     shifted by 1 mm (shiftByDistance, :163-177: every ray's read-out is linear in the shift, so the difference IS the
     slope), the largest Kahan angle to `axis` (default: the mean vector; ART/ModuleProcessing.py:536-566), and the shifts
     at which a hit point passes through its ray's origin (t(s) = n.(C - s n - A) / (u.n) = 0).  `co`: the provisional
-    centre of the path moments -- a free parameter of the sums, taken from the caller.  -> dict of row slots."""
+    centre of the path moments, `cxy`: that of the (X, Y) moments (the bounding box stays about D.centre) -- free
+    parameters of the sums, taken from the caller.  -> dict of row slots."""
     w = B.intensity if B.intensity is not None else np.ones(len(B))
     P0 = detector_points2d(D, B)
     O0 = optical_paths(D, B)
     D1 = detector_shifted(D, 1.0)
     P1 = detector_points2d(D1, B)
     O1 = optical_paths(D1, B)
-    q = [P0[:, 0], P0[:, 1], O0 - co]
+    q = [P0[:, 0] - cxy[0], P0[:, 1] - cxy[1], O0 - co]
     sq = [P1[:, 0] - P0[:, 0], P1[:, 1] - P0[:, 1], (O1 - O0) - 1.0]
     mom = np.zeros(32)
     for base, wt in ((0, np.ones(len(B))), (16, w)):

@@ -236,6 +236,18 @@ int art_cpu_analysis_place(const double* sums9, int32_t mode, double distance, c
   out22[21] = co;
   return 0;
 }
+// the same with the provisional centre of the (X, Y) moments (analysis_place_centred): out = the 22 above, cx, cy
+int art_cpu_analysis_place_centred(const double* sums9, int32_t mode, double distance, const double* centre,
+                                   const double* normal, const double* refpoint, double* out24) {
+  ArtDetectorDesc d;
+  double ref[3], axis[3], co, cxy[2];
+  art::analysis_place_centred(sums9, mode, distance, centre, normal, refpoint, d, ref, axis, co, cxy);
+  for (int k = 0; k < 3; ++k) { out24[k] = d.centre[k]; out24[3 + k] = d.normal[k]; out24[15 + k] = ref[k]; out24[18 + k] = axis[k]; }
+  for (int k = 0; k < 9; ++k) out24[6 + k] = d.rot[k];
+  out24[21] = co;
+  out24[22] = cxy[0]; out24[23] = cxy[1];
+  return 0;
+}
 
 int art_cpu_detector_scan_kink(const ArtDetectorDesc* d, const ArtBundleView* b, int64_t n, double* X, double* Y, double* O,
                                double* sx, double* sy, double* so, double* skink) {

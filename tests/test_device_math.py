@@ -132,10 +132,12 @@ def test_detector_placement_on_the_device_matches_the_host_shell():
     """analysis_place (art_device.h, what art_analyse_bundles runs between its passes): the detector of
     Detector.autoplace (ART/ModuleDetector.py:109-137) from the bundle's sums -- normal, centre, reference point -- and the
     matrix of RotationPoint(., normal, ez) with its special cases (ART/ModuleGeometry.py:333-343), against the host shell's
-    NumPy versions; the provisional path centre is the mean path + the mean ray's distance to the detector."""
+    NumPy versions; the provisional path centre is the mean path + the mean ray's distance to the detector over the length
+    of the mean vector (= the mean cosine to the mean ray: the rays' mean distance to second order); the provisional (X, Y)
+    centre is the mean ray's hit in detector coordinates, 0 when auto-placing."""
     import ART.ModuleGeometry as mgeo
     lib = C.CDLL(twin_backend.build_twin())
-    place = lib.art_cpu_analysis_place
+    place = lib.art_cpu_analysis_place_centred
     place.restype = C.c_int
     place.argtypes = [_abi.c_double_p, C.c_int32, C.c_double, _abi.c_double_p, _abi.c_double_p, _abi.c_double_p, _abi.c_double_p]
     rng = np.random.default_rng(5)
@@ -150,7 +152,7 @@ def test_detector_placement_on_the_device_matches_the_host_shell():
         D = float(rng.uniform(1, 2000))
         mean_path = float(rng.uniform(0, 3000))
         sums = np.concatenate([[cnt], mp_ * cnt, mv * cnt, [cnt * 0.7], [mean_path * cnt]])
-        out = (C.c_double * 22)()
+        out = (C.c_double * 24)()
         zero = (C.c_double * 3)()
         assert place((C.c_double * 9)(*sums), 0, D, zero, zero, zero, out) == 0
         o = np.array(out)
@@ -165,11 +167,18 @@ def test_detector_placement_on_the_device_matches_the_host_shell():
         M = mgeo.rotation_matrix(n, ez)
         worst = max(worst, np.abs(o[6:15].reshape(3, 3) - M).max())
         assert np.abs(o[6:15].reshape(3, 3) @ o[3:6] - (M @ n)).max() <= 2e-15          # (a few ulp of 1)
-        assert abs(o[21] - (mean_path + D)) <= 1e-12 * (mean_path + D)
+        assert abs(o[21] - (mean_path + D / np.linalg.norm(mv))) <= 1e-12 * (mean_path + D)
+        assert o[22] == 0.0 and o[23] == 0.0
     assert worst <= 2e-15, worst          # entries of the rotation: the device's Kahan angle (polynomial atan) then sin / cos of half of it
     # manual mode: pose used bit for bit
     c_, n_, r_ = np.array([1.0, 2.0, 3.0]), _unit(np.array([0.3, -0.2, 0.9])), np.array([4.0, 5.0, 6.0])
-    out = (C.c_double * 22)()
+    out = (C.c_double * 24)()
     assert place((C.c_double * 9)(*sums), 1, 0.0, (C.c_double * 3)(*c_), (C.c_double * 3)(*n_), (C.c_double * 3)(*r_), out) == 0
     o = np.array(out)
     assert np.array_equal(o[0:3], c_) and np.array_equal(o[3:6], n_) and np.array_equal(o[15:18], r_)
+    # ... and the (X, Y) moments are centred where the mean ray meets that plane: rot (I - centre), I = p + t v
+    pt, v = sums[1:4] / cnt, _unit(sums[4:7])
+    hit = pt + ((c_ - pt) @ n_) / (v @ n_) * v
+    want = mgeo.rotation_matrix(n_, ez) @ (hit - c_)
+    assert np.abs(o[22:24] - want[:2]).max() <= 1e-12 * np.linalg.norm(hit - c_) and abs(want[2]) <= 1e-12 * np.linalg.norm(hit - c_)
+    assert abs(o[21] - (mean_path + abs((c_ - pt) @ n_ / (v @ n_)) / np.linalg.norm(sums[4:7] / cnt))) <= 1e-12 * abs(o[21])

@@ -772,9 +772,11 @@ def test_gpu_analysis_rows_match_numpy(hip):
         Do = orc.detector_autoplace(Bo, dist) if mode == _abi.ART_JOB_AUTOPLACE else orc.Detector(man.centre, man.normal, man.refpoint)
         assert np.abs(g[10:13] - Do.centre).max() <= 1e-11 * 2000.0 and np.abs(g[13:16] - Do.normal).max() <= 1e-12
         assert np.abs(g[16:19] - Do.refpoint).max() <= 1e-11 * 2000.0
-        # everything else on the DEVICE's detector and path centre (a provisional centre is a free parameter of the sums)
+        # everything else on the DEVICE's detector and centres (a provisional centre is a free parameter of the sums): the
+        # path about co = g[19], X and Y about the mean ray's hit (g[62], g[63]) -- exactly 0 when auto-placing
         Dg = orc.Detector(g[10:13].copy(), g[13:16].copy(), g[16:19].copy())
-        r = orc.analysis_row(Bo, Dg, g[19])
+        r = orc.analysis_row(Bo, Dg, g[19], cxy=g[62:64])
+        assert (mode != _abi.ART_JOB_AUTOPLACE or not g[62:64].any()) and np.abs(g[62:64]).max() <= 1e-3
         assert abs(g[19] - r["mean_opl"]) <= 0.5                                  # the path centre is near the mean path
         assert np.abs(g[1:4] - r["sum_point"]).max() <= 1e-12 * g[0] * 2000.0 and np.abs(g[4:7] - r["sum_vector"]).max() <= 1e-12 * g[0]
         assert abs(g[7] - r["sum_w"]) <= 1e-12 * r["sum_w"] and abs(g[8] - r["sum_path"]) <= 1e-12 * r["sum_path"]

@@ -195,8 +195,8 @@ class TwinBackend:
 
     def analyse_bundles(self, jobs, n):
         """Layout of art_analyse_bundles (include/art_hip.h): sums and moments reduced with NumPy, the detector placed
-        by the same art_device.h code as on the device (art_cpu_analysis_place)."""
-        place = self.lib.art_cpu_analysis_place
+        by the same art_device.h code as on the device (art_cpu_analysis_place_centred)."""
+        place = self.lib.art_cpu_analysis_place_centred
         place.restype = C.c_int
         place.argtypes = [_abi.c_double_p, C.c_int32, C.c_double, _abi.c_double_p, _abi.c_double_p, _abi.c_double_p,
                           _abi.c_double_p]
@@ -227,10 +227,11 @@ class TwinBackend:
                 o[10:20] = np.nan
                 continue
             sums9 = (C.c_double * 9)(*o[:9])
-            res = (C.c_double * 22)()
+            res = (C.c_double * 24)()
             assert place(sums9, jb.mode, jb.distance, jb.centre, jb.normal, jb.refpoint, res) == 0
             res = np.array(res)
             o[10:13], o[13:16], o[16:19], o[19] = res[0:3], res[3:6], res[15:18], res[21]
+            o[62:64] = res[22:24]
             axis, co = res[18:21], res[21]
             d = _abi.ArtDetectorDesc()
             d.centre[:], d.normal[:], d.rot[:] = list(res[0:3]), list(res[3:6]), list(res[6:15])
@@ -244,6 +245,7 @@ class TwinBackend:
             u, vn = np.linalg.norm(axis), np.linalg.norm(V, axis=1)[:, None]
             o[55] = (2 * np.arctan2(np.linalg.norm(axis[None, :] * vn - V * u, axis=1),
                                     np.linalg.norm(axis[None, :] * vn + V * u, axis=1))).max()
+            X, Y = X - res[22], Y - res[23]        # (after the bounding box: rows 56..59 stay about the centre)
             O = O - co
             so = so - 1.0
             for base, wt in ((0, np.ones_like(w)), (16, w)):
