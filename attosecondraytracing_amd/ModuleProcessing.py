@@ -184,6 +184,33 @@ def _attach_sums(bundle, res):
     bundle._fused_sums = (bundle.version, None if w is None else (w.data_ptr(), w._version), res)
 
 
+def _readout_weights(readouts, ci):
+    """The weight tensor chain `ci`'s fused tail reads (None: none, or no tail)."""
+    return None if readouts is None else readouts[ci]["_keep"][0]
+
+
+def _scene_row_summaries(be, sources, readouts, buf=None, keys=None):
+    """Row summaries of a scene's inputs (include/art_hip.h, art_bundle_row_summary): one per chain, formed over the
+    chain's source bundle and the weights its fused tail reads, in ONE device tensor [chains, bytes] for
+    be.scene_set_row_summaries.  `buf`, `keys`: the tensor and the per-chain keys of an earlier call (a SceneProgram's:
+    a captured graph holds the tensor's address) -- only chains whose source or weights changed since (RayBundle.
+    row_summary_key) are formed again, by launches on the current stream; nothing waits on the host.
+    -> (buf, keys), or (None, None) on a backend without the kernel (the CPU twin: nothing is attached)."""
+    if not hasattr(be, "bundle_row_summary"):
+        return None, None
+    c = len(sources)
+    if buf is None:
+        buf = torch.empty((c, be.row_summary_bytes()), dtype=torch.uint8, device=be.device)
+        keys = [None] * c
+    for ci, s in enumerate(sources):
+        w = _readout_weights(readouts, ci)
+        key = s.row_summary_key(w)
+        if keys[ci] != key:
+            buf[ci].copy_(s.row_summary(w)[1])      # (one bundle in several chains: formed once, cached by the bundle)
+            keys[ci] = key
+    return buf, keys
+
+
 def RayTracingCalculation(source_rays, optical_elements, IgnoreDefects=True, mode=None, history=True, detector=None,
                           path_centre=0.0, readout_lite=False, sums=False):
     """Propagate `source_rays` through `optical_elements` (ART/ModuleProcessing.py:250-313).
@@ -520,8 +547,22 @@ def _RayTracingCalculationMany(source_rays_list, optical_elements_list, IgnoreDe
         ros = [be.new_chain_sums(s_.intensity, n, scratch=area) for s_, area in zip(sources, be.chain_readout_scratch(n, c))]
     host, dev = be.scene_alloc(c, m, transient=True)
     be.scene_pack(descs, [s.view() for s in sources], views, c, m, host, ros)
+    # Row summaries (the launch skips the constant rows of a generated source): forming one costs a pass over the source, more
+    # than ONE trace saves, so a one-shot launch uses them from the second trace of an unchanged source on (a loop over
+    # scenes from one source; a SceneProgram forms them at once).  The tensor lives until the launch is enqueued: freed
+    # earlier, the stream's allocator could hand its block to a kernel that runs in front of the trace.
+    summaries = None
+    if hasattr(be, "bundle_row_summary"):
+        now = [s.row_summary_key(_readout_weights(ros, ci)) for ci, s in enumerate(sources)]
+        again = all(getattr(s, "_scene_traced", None) == k for s, k in zip(sources, now))
+        for s, k in zip(sources, now):
+            s._scene_traced = k
+        if again:
+            summaries = _scene_row_summaries(be, sources, ros)[0]
+            be.scene_set_row_summaries(host, summaries)
     be.scene_upload(host, dev)
     be.trace_scene(dev, host, n, segments=-(-m // 8))
+    del summaries
     for ci, outs in enumerate(grid):
         outs[-1]._keepalive = (keep, scratch)
         if ros is not None and ros[ci].get("sums"):

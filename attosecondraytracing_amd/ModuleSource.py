@@ -20,6 +20,7 @@ def _device_source(kind, size, S, Axis, n, n_total, Wavelength):
     b.number = None  # slot index == Ray.number for these sources
     rot = mgeo.rotation_matrix(_EZ, np.asarray(Axis, dtype=float))
     be.make_source(kind, size, rot, np.asarray(S, dtype=float), 0, n, n_total, b.view())
+    b.touch()     # written through a raw view: torch's counters saw nothing (bundle.row_summary_key)
     # the bundle is a pure function of these arguments (the generator is deterministic)
     b.tag_content(("source", int(kind), float(size), np.asarray(S, dtype=float).tobytes(),
                    np.asarray(Axis, dtype=float).tobytes(), int(n), int(n_total), Wavelength))
@@ -54,6 +55,7 @@ def ExtendedSource(S, Axis, Diameter: float, Divergence: float, NbRays: int, Wav
     rot = mgeo.rotation_matrix(_EZ, np.asarray(Axis, dtype=float))
     be.make_extended_source(Diameter / 2, Divergence, n_src, per, rot, np.asarray(S, dtype=float), 0, n_src * per,
                             b.view())
+    b.touch()
     b.tag_content(("extended source", float(Diameter), float(Divergence), int(n_src), int(per),
                    np.asarray(S, dtype=float).tobytes(), np.asarray(Axis, dtype=float).tobytes(), Wavelength))
     b.rays_per_source = per       # the mutually incoherent groups of Detector.get_FocalImage

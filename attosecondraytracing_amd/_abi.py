@@ -362,6 +362,9 @@ PROTOTYPES = {
     "art_scene_pack": (C.c_int, [C.POINTER(ArtElementDesc), C.c_int32, C.c_int32, C.POINTER(ArtBundleView),
                                  C.POINTER(ArtBundleView), C.POINTER(ArtChainReadout), C.c_void_p]),
     "art_trace_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "art_row_summary_bytes": (C.c_int64, []),
+    "art_bundle_row_summary": (C.c_int, [C.POINTER(ArtBundleView), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "art_scene_set_row_summaries": (C.c_int, [C.c_void_p, C.c_void_p]),
     "art_pack_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ArtBundleView), C.c_void_p]),
     "art_transform_bundle": (C.c_int, [c_double_p, c_double_p, C.c_int32, C.POINTER(ArtBundleView),
                                        C.POINTER(ArtBundleView), C.c_int64, C.c_void_p]),

@@ -302,6 +302,23 @@ class HipBackend:
         self._scene_uploads[host_image.data_ptr()] = ev
         return ev
 
+    # row summaries (include/art_hip.h): which rows of a chain's input hold one value in every slot
+    def row_summary_bytes(self):
+        return int(self.fn["art_row_summary_bytes"]())
+
+    def bundle_row_summary(self, view, w, n, out):
+        """art_bundle_row_summary of the bundle `view` and the weights `w` (tensor or None) into `out` (device uint8
+        tensor of row_summary_bytes()), on the current stream."""
+        self.check(self.fn["art_bundle_row_summary"](C.byref(view), self._ptr(w, n), n, out.data_ptr(), self.stream_ptr()),
+                   "art_bundle_row_summary")
+
+    def scene_set_row_summaries(self, host_image, summaries):
+        """Attach the device array of per-chain summaries (uint8 tensor, n_chains x row_summary_bytes(); None detaches)
+        to a packed host image; scene_pack clears it."""
+        self.check(self.fn["art_scene_set_row_summaries"](host_image.data_ptr(),
+                                                          None if summaries is None else summaries.data_ptr()),
+                   "art_scene_set_row_summaries")
+
     def note_launches(self, n, k=1):
         if self.count_from is not None and n >= self.count_from:
             self.counted_launches += k

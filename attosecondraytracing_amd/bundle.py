@@ -188,6 +188,7 @@ class RayBundle:
             if path0 is not None:
                 p0 = be.from_numpy(np.broadcast_to(np.asarray(path0, dtype=np.float64), (n,)).copy())
             be.pack_rays(be.from_numpy(point), be.from_numpy(vector), p0, n, b.view())
+            b.touch()     # written through a raw view (row_summary_key)
         b.number = None if number is None else be.from_numpy(np.asarray(number, dtype=np.int64))
         b.intensity = None if intensity is None else be.from_numpy(np.asarray(intensity, dtype=np.float64))
         b.wavelength = wavelength
@@ -291,6 +292,33 @@ class RayBundle:
         if self._content is not None and self._content[1] == self.version:
             return self._content[0]
         return ("bundle", self._serial, self.version)
+
+    # ------------------------------------------------------------------ row summary
+    def row_summary_key(self, weights=None):
+        """What a row summary of this bundle (and of `weights`, default its intensity) was formed over: the arrays' address
+        and torch's in-place counters, this bundle's own version -- writers that go through a raw view (library kernels)
+        announce themselves by touch() -- and the weights' address and counter.  The conventions of fused_sums()."""
+        w = self.intensity if weights is None else weights
+        return (self.data.data_ptr(), self.data._version, self.alive.data_ptr(), self.alive._version, self.version,
+                self.n_slots, None if w is None else (w.data_ptr(), w._version))
+
+    def row_summary(self, weights=None):
+        """(key, DEVICE uint8 tensor) -- which of the nine rows a fused trace reads of this bundle (7 fp64 rows, alive, the
+        weights) hold one bit pattern in every slot, and that pattern (art_bundle_row_summary): scene launches skip those
+        rows.  Formed once per content version, by one streaming pass on the current stream into the SAME buffer every
+        time (a captured graph may hold its address); None on a backend without the kernel."""
+        be = self.backend
+        if not hasattr(be, "bundle_row_summary"):
+            return None
+        w = self.intensity if weights is None else weights
+        key = self.row_summary_key(w)
+        hit = getattr(self, "_row_summary", None)
+        if hit is not None and hit[0] == key:
+            return hit
+        buf = hit[1] if hit is not None else torch.empty(be.row_summary_bytes(), dtype=torch.uint8, device=be.device)
+        be.bundle_row_summary(self.view(), w, self.n_slots, buf)
+        self._row_summary = (key, buf, w)      # (the weights stay alive: their address is part of the key)
+        return self._row_summary
 
     def touch(self):
         self.version += 1
@@ -424,6 +452,7 @@ class RayBundle:
         out.path_head = self.path_head
         self._share_grouping(out)
         self.backend.transform_bundle(M, T, rotate_points, self.view(), out.view(), self.n_slots)
+        out.touch()
         return out
 
     def copy(self):

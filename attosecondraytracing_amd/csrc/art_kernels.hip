@@ -833,6 +833,10 @@ __device__ __forceinline__ void tail_partial(const ChainArgs& a, const double to
   }
 }
 
+__device__ __forceinline__ double or_bits(const double v, const uint64_t b) {
+  return __longlong_as_double(__double_as_longlong(v) | (long long)b);
+}
+
 // Whole chain with the ray resident in registers; history written for every element whose view is non-null.
 // `a` lives in kernel arguments (k_trace_chain) or in the device-resident scene table (k_trace_scene): either way
 // its fields are wave-uniform and fetched by scalar loads where they are used.  Rays [first, first + n) of every view.
@@ -840,9 +844,16 @@ __device__ __forceinline__ void tail_partial(const ChainArgs& a, const double to
 // tile-major launches, blockIdx.y / gridDim.y in the chain-interleaved scene launch (k_trace_scene, `transposed`).
 // KIND1 >= 0: a chain of ONE element whose optic kind is known at compile time (the one-element defect chains: C5) -- no
 // run-time switch on the kind, no element loop; ART_KIND_DYN: the general body.
-template <bool DEFECT, int KIND1 = ART_KIND_DYN>
+// SUMMARY (the scene kernels): `sm` is NULL or this chain's row summary (art_scene.h RowSummary, formed by
+// art_bundle_row_summary over a.in and a.ro.w).  A row it proves constant keeps its load instruction but gets a ZERO-LENGTH
+// descriptor -- the range check answers 0 without touching memory, the mechanism the absent weight stream always used -- and
+// its value is the summary's pattern (a select on wave-uniform conditions, see below): mask and patterns arrive by
+// scalar loads.  41 of a point or plane source's 65 B per ray are not read.  A constant `alive` holds for slots below n
+// only: the tail of the last tile and the padding workgroups of a rounded-up grid stay dead.
+template <bool DEFECT, int KIND1 = ART_KIND_DYN, bool SUMMARY = false>
 __device__ __forceinline__ void chain_body(const ChainArgs& a, const int64_t first, const int64_t n, const int xmap,
-                                           double* s_zern, const unsigned bx, const unsigned nbx, const bool keep_in = false) {
+                                           double* s_zern, const unsigned bx, const unsigned nbx, const bool keep_in = false,
+                                           const art::RowSummary* sm = nullptr) {
 #ifdef ART_ZERN_LDS
   if (DEFECT) {
     int off = 0;
@@ -864,7 +875,26 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const int64_t fir
 #endif
   __shared__ double s_part[kBlock / 64][kReadoutSlots];   // wave totals of the fused read-out, combined per workgroup
   const int64_t tile = tile_of(bx, nbx, xmap);
-  const BundleRsrc bi = make_rsrc(a.in, n, first);
+  BundleRsrc bi = make_rsrc(a.in, n, first);
+  unsigned cm = 0;                                   // bit j: row j of the input is constant (wave-uniform)
+  uint64_t cc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // ... and its pattern
+  if (SUMMARY) {
+    // Mask and patterns are read UNCONDITIONALLY, through the constant address space (scalar loads, like the table's):
+    // loads behind `sm != NULL` came out as nine branches with a vector load each, behind the ray's own.  Without a
+    // summary the words are read from the table entry itself -- any readable 88 bytes -- and cm = 0 discards them.
+    typedef const art::RowSummary __attribute__((address_space(4)))* csum_t;
+    const bool have = sm != nullptr;
+    const csum_t q = (csum_t)(have ? (const void*)sm : (const void*)&a);
+    if (have && q->n >= first + n) cm = ~q->differs & 0x1ffu;
+#pragma unroll
+    for (int j = 0; j < 9; ++j) cc[j] = (cm >> j & 1u) ? q->c[j] : 0;      // (0 for a row that is loaded)
+    const unsigned b8 = (unsigned)(n * 8);
+    bi.ox = rsrc_of(a.in.ox + first, (cm & 1u) ? 0u : b8); bi.oy = rsrc_of(a.in.oy + first, (cm & 2u) ? 0u : b8);
+    bi.oz = rsrc_of(a.in.oz + first, (cm & 4u) ? 0u : b8); bi.dx = rsrc_of(a.in.dx + first, (cm & 8u) ? 0u : b8);
+    bi.dy = rsrc_of(a.in.dy + first, (cm & 16u) ? 0u : b8); bi.dz = rsrc_of(a.in.dz + first, (cm & 32u) ? 0u : b8);
+    bi.path = rsrc_of(a.in.path + first, (cm & 64u) ? 0u : b8);
+    bi.alive = rsrc_of(a.in.alive + first, (cm & (1u << art::kRowAlive)) ? 0u : (unsigned)n);
+  }
   const int64_t stride = (int64_t)nbx * kBlock;
   int64_t i0 = tile * kBlock + threadIdx.x;
   do {
@@ -884,9 +914,24 @@ __device__ __forceinline__ void chain_body(const ChainArgs& a, const int64_t fir
     // Weight of the fused read-out: fetched with the ray (a zero-length descriptor without read-out or weights) and
     // parked in LDS until the tail needs it -- held in registers across the chain it costs the 2 VGPRs that push the
     // 5-wave build into scratch, and a scratch reload at the end is a VMEM load behind 36 stores (see the tail).
-    s_w[lane] = ld_f64(rsrc_of(const_cast<double*>(a.ro.w) + first,
-                                      ((a.flags & art::kFlagReadout) && a.ro.w && !a.ro.lite) ? (unsigned)(n * 8) : 0u),
+    double wl = ld_f64(rsrc_of(const_cast<double*>(a.ro.w) + first,
+                               ((a.flags & art::kFlagReadout) && a.ro.w && !a.ro.lite &&
+                                !(SUMMARY && (cm & (1u << art::kRowWeight)))) ? (unsigned)(n * 8) : 0u),
                        (unsigned)i * 8u);
+    if (SUMMARY) {
+      // The select `constant ? pattern : loaded`, bit for bit, in ONE instruction per dword: the range check answered a
+      // constant row's load with 0 and cc[] holds 0 for a loaded row, so OR-ing the two IS the select, with the pattern as
+      // the scalar operand.  (v_cndmask takes one scalar operand on gfx9 -- the lane mask -- so the patterns had to be
+      // copied into VGPRs first: 16 more instructions per ray, which showed where the launch is VALU-bound -- C5, the
+      // lazy-history step: DESIGN.md 5.)  No floating-point operation touches the value.
+      r.ox = or_bits(r.ox, cc[0]); r.oy = or_bits(r.oy, cc[1]); r.oz = or_bits(r.oz, cc[2]);
+      r.dx = or_bits(r.dx, cc[3]); r.dy = or_bits(r.dy, cc[4]); r.dz = or_bits(r.dz, cc[5]);
+      r.path = or_bits(r.path, cc[6]);
+      wl = or_bits(wl, cc[art::kRowWeight]);
+      // (slot < n in 32 bits: a launch covers at most 2^28 slots and its grid fewer than 2^32 work-items)
+      al |= (slot < (unsigned)n) ? (uint8_t)cc[art::kRowAlive] : (uint8_t)0;
+    }
+    s_w[lane] = wl;
     bool ok = al != 0;
     const double* zk = s_zern;
     // do-while (n_elems >= 1, checked on the host): with a zero-trip path the ray loads above would still be in
@@ -1204,7 +1249,8 @@ __device__ __forceinline__ SceneWG scene_wg(const int shape, const int xmap) {
 
 template <bool DEFECT, int WAVES>
 __global__ __launch_bounds__(kBlock, WAVES) void k_trace_scene2(const ChainArgs* __restrict__ tab, const int64_t first,
-                                                                const int64_t n, const int xmap, const int transposed) {
+                                                                const int64_t n, const int xmap, const int transposed,
+                                                                const art::RowSummary*) {   // (summaries: one-ray bodies only)
   const SceneWG w = scene_wg(transposed, xmap);
   if (w.idle) return;
   chain_body2<DEFECT>(tab[w.chain], first, n, w.xmap, w.bx, w.nbx, (transposed & 2) != 0);
@@ -1220,21 +1266,25 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_trace_scene2(const ChainArgs*
 // chain; XCD-grouped (the default), it does not even leave the L2.
 template <bool DEFECT, int WAVES>
 __global__ __launch_bounds__(kBlock, WAVES) void k_trace_scene(const ChainArgs* __restrict__ tab, const int64_t first,
-                                                               const int64_t n, const int xmap, const int transposed) {
+                                                               const int64_t n, const int xmap, const int transposed,
+                                                               const art::RowSummary* __restrict__ sums) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   const SceneWG w = scene_wg(transposed, xmap);   // (ONE copy of the body)
   if (w.idle) return;
-  chain_body<DEFECT>(tab[w.chain], first, n, w.xmap, s_dyn, w.bx, w.nbx, (transposed & 2) != 0);
+  chain_body<DEFECT, ART_KIND_DYN, true>(tab[w.chain], first, n, w.xmap, s_dyn, w.bx, w.nbx, (transposed & 2) != 0,
+                                         sums ? sums + w.chain : nullptr);
 }
 
 // One-element chains WITH defects, the optic's kind a template parameter (round 5, C5: a deformed parabola + read-out).
 template <int KIND1, int WAVES>
 __global__ __launch_bounds__(kBlock, WAVES) void k_trace_scene1(const ChainArgs* __restrict__ tab, const int64_t first,
-                                                                const int64_t n, const int xmap, const int transposed) {
+                                                                const int64_t n, const int xmap, const int transposed,
+                                                                const art::RowSummary* __restrict__ sums) {
   extern __shared__ __attribute__((aligned(16))) double s_dyn[];
   const SceneWG w = scene_wg(transposed, xmap);
   if (w.idle) return;
-  chain_body<true, KIND1>(tab[w.chain], first, n, w.xmap, s_dyn, w.bx, w.nbx, (transposed & 2) != 0);
+  chain_body<true, KIND1, true>(tab[w.chain], first, n, w.xmap, s_dyn, w.bx, w.nbx, (transposed & 2) != 0,
+                                sums ? sums + w.chain : nullptr);
 }
 template <int KIND1, int WAVES>
 __global__ __launch_bounds__(kBlock, WAVES) void k_trace_chain1(const ChainArgs, const int64_t n, const int xmap) {
@@ -1242,6 +1292,53 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_trace_chain1(const ChainArgs,
   typedef const ChainArgs __attribute__((address_space(4)))* kernarg_t;
   chain_body<true, KIND1>(*(const ChainArgs*)(kernarg_t)__builtin_amdgcn_kernarg_segment_ptr(), 0, n, xmap, s_dyn, blockIdx.x,
                           gridDim.x);
+}
+
+// ------------------------------------------------------------------------------------------- row summary
+// art_bundle_row_summary: one streaming pass over the nine per-slot rows a fused trace reads of its input (7 fp64 rows,
+// alive, the read-out's weights) that proves which of them repeat slot 0's BIT PATTERN in every slot (-0.0 differs from
+// +0.0; a row of one NaN pattern is constant).  Every lane ORs the rows it saw differ into one word, the workgroup's word
+// meets in LDS and goes out with ONE integer atomicOr (order-independent: the result is deterministic).  `out` was cleared
+// by the caller's memset; a row without an array, or an empty bundle, is reported as differing.
+__global__ __launch_bounds__(kBlock) void k_row_summary(const ArtBundleView in, const double* __restrict__ w, const int64_t n,
+                                                        art::RowSummary* __restrict__ out) {
+  __shared__ unsigned s_diff;
+  if (threadIdx.x == 0) s_diff = 0;
+  __syncthreads();
+  const double* const rows[8] = {in.ox, in.oy, in.oz, in.dx, in.dy, in.dz, in.path, w};
+  uint64_t c0[8];
+  unsigned diff = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int bit = (j < 7) ? j : art::kRowWeight;
+    const bool has = rows[j] != nullptr && n > 0;
+    c0[j] = has ? (uint64_t)__double_as_longlong(rows[j][0]) : 0;
+    if (!has) diff |= 1u << bit;
+  }
+  const bool has_a = in.alive != nullptr && n > 0;
+  const uint8_t a0 = has_a ? in.alive[0] : (uint8_t)0;
+  if (!has_a) diff |= 1u << art::kRowAlive;
+  const int64_t stride = (int64_t)gridDim.x * kBlock;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int bit = (j < 7) ? j : art::kRowWeight;
+      if (rows[j] != nullptr) diff |= ((uint64_t)__double_as_longlong(ld_nt(rows[j] + i)) != c0[j]) ? 1u << bit : 0u;
+    }
+    if (has_a) diff |= (ld_nt(in.alive + i) != a0) ? 1u << art::kRowAlive : 0u;
+  }
+  if (diff) atomicOr(&s_diff, diff);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_diff) atomicOr(&out->differs, s_diff);
+    if (blockIdx.x == 0) {
+      out->n = n;
+#pragma unroll
+      for (int j = 0; j < 7; ++j) out->c[j] = c0[j];
+      out->c[art::kRowAlive] = a0;
+      out->c[art::kRowWeight] = c0[7];
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------- AoS -> SoA
@@ -3747,6 +3844,12 @@ inline int scene_order(const bool shared_in) {
   if (e && e[0] == 'x') return 4;
   return shared_in ? 4 : 0;
 }
+// ART_ROW_SUMMARY=0: scene launches ignore the row summaries attached to their image (art_scene_set_row_summaries) and load
+// every row, as without them (read per launch: the A/B tools alternate the two inside one process).
+inline bool row_summaries_on() {
+  const char* e = getenv("ART_ROW_SUMMARY");
+  return !(e && e[0] == '0');
+}
 // ... and whether that shared input is loaded with the default cache policy instead of non-temporal loads.  XCD-grouped:
 // always -- the C - 1 re-reads of a tile follow within microseconds in the same L2 (profiles/r05_experiments.md batch r: 10
 // chains x 1e7 rays 3.167 against 3.280 ms, 11 x 1e6 0.299 against 0.314).  In the interleaved 2-D grid the re-reads come
@@ -3835,15 +3938,15 @@ void launch_chain_body(const BodyChoice& c, const ChainArgs& a, const int64_t n,
 }
 // ... in a segment of the scene table (rays [first, first + n) of every chain, grid and shape from art_trace_scene):
 void launch_scene_body(const BodyChoice& c, const dim3 g, const ChainArgs* seg, const int64_t first, const int64_t n,
-                       const int xarg, const int shape, hipStream_t s) {
-  typedef void (*K)(const ChainArgs*, const int64_t, const int64_t, const int, const int);
+                       const int xarg, const int shape, const art::RowSummary* sums, hipStream_t s) {
+  typedef void (*K)(const ChainArgs*, const int64_t, const int64_t, const int, const int, const art::RowSummary*);
   const K special[2][3] = {{k_trace_scene1<ART_PLANE, 4>, k_trace_scene1<ART_SPHERE, 4>, k_trace_scene1<ART_PARABOLA, 4>},
                            {k_trace_scene1<ART_PLANE, 5>, k_trace_scene1<ART_SPHERE, 5>, k_trace_scene1<ART_PARABOLA, 5>}};
   const K k = (c.body == Body::kSpecial) ? special[c.waves - 4][c.kind]
               : (c.body == Body::kDefect) ? k_trace_scene<true, 4>
               : (c.body == Body::kTwoRay) ? k_trace_scene2<false, 4>
               : (c.waves == 6) ? k_trace_scene<false, 6> : k_trace_scene<false, 5>;
-  hipLaunchKernelGGL(k, g, dim3(kBlock), 0, s, seg, first, n, xarg, shape);
+  hipLaunchKernelGGL(k, g, dim3(kBlock), 0, s, seg, first, n, xarg, shape, sums);
 }
 
 }  // namespace
@@ -4137,6 +4240,7 @@ int art_trace_scene(const void* image_dev, const void* image_host, int64_t n, vo
   }
   const BodyChoice c = choose_body((flags & 1) != 0, (flags & art::kFlagMask) != 0 ||
                                    ((flags & art::kFlagSharedIn) != 0 && n_chains > 1 && S == 1), kind1);
+  const art::RowSummary* rowsum = row_summaries_on() ? art::scene_row_summaries(h) : nullptr;
   per_launch(n, [&](const int64_t off, const int64_t cnt) {
     const int xm = xcd_map();
     const int tiles = grid_stream_mapped(c.body == Body::kTwoRay ? (cnt + 1) / 2 : cnt, xm);
@@ -4154,12 +4258,38 @@ int art_trace_scene(const void* image_dev, const void* image_host, int64_t n, vo
       if (tr & 4) tr |= n_chains << 8;
       const dim3 g = (tr & 4) ? dim3((unsigned)(tiles8 * n_chains)) : ((tr & 1) ? dim3(n_chains, tiles) : dim3(tiles, n_chains));
       const int xarg = (tr & 4) ? tiles : xm;      // (XCD-grouped: the true tile count travels in the mapping's parameter)
-      launch_scene_body(c, g, seg, off, cnt, xarg, tr, s);
+      // the summaries describe the scene's inputs: the first segment's (later ones read their own hand-over bundles)
+      launch_scene_body(c, g, seg, off, cnt, xarg, tr, sg == 0 ? rowsum : nullptr, s);
       if (tails && sg == S - 1) launch_fold(sums, seg, n_chains, nullptr, nullptr, sums ? analysis_tiles(cnt) : tiles, s);
     }
     return ART_OK;
   });
   return launched("art_trace_scene launch");
+}
+
+int64_t art_row_summary_bytes(void) { return (int64_t)sizeof(art::RowSummary); }
+
+int art_bundle_row_summary(const ArtBundleView* in, const double* w, int64_t n, void* summary_dev, void* stream) {
+  if (!summary_dev) return fail(ART_ERR_BAD_ARG, "row summary buffer is NULL");
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  ArtBundleView v;
+  memset(&v, 0, sizeof(v));
+  if (in) v = *in;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(summary_dev, 0, sizeof(art::RowSummary), s);
+  if (e != hipSuccess) return fail_hip(e, "art_bundle_row_summary memset");
+  hipLaunchKernelGGL(k_row_summary, dim3(grid_for(n)), dim3(kBlock), 0, s, v, w, n, (art::RowSummary*)summary_dev);
+  return launched("art_bundle_row_summary launch");
+}
+
+int art_scene_set_row_summaries(void* image_host, const void* summaries_dev) {
+  if (!image_host) return fail(ART_ERR_BAD_ARG, "scene image is NULL");
+  art::SceneHeader h;
+  memcpy(&h, image_host, sizeof(h));
+  if (h.magic != art::kSceneMagic) return fail(ART_ERR_BAD_ARG, "host image was not written by art_scene_pack");
+  art::scene_set_row_summaries(h, (const art::RowSummary*)summaries_dev);
+  memcpy(image_host, &h, sizeof(h));
+  return ART_OK;
 }
 
 int art_pack_rays(const double* points, const double* vectors, const double* path0, int64_t n, const ArtBundleView* out,

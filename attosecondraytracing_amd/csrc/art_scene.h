@@ -48,6 +48,29 @@ struct SceneHeader {                           // first 64 bytes of an image
 };
 static_assert(sizeof(SceneHeader) == 64, "scene header is 64 bytes");
 
+// Row summary of a chain's INPUT (art_bundle_row_summary): which of its nine per-slot rows -- ox, oy, oz, dx, dy, dz, path
+// (bits 0-6), alive (bit 7), the read-out's weights (bit 8) -- hold ONE bit pattern in every slot, and that pattern.  A
+// generated source repeats one value n times in most of them (a point source: ox, oy, oz, path, alive and a uniform
+// intensity); the one-ray scene kernels give such a row a zero-length buffer descriptor and take its value from here.
+// Formed and read on the device only.  `n` = the slots it was formed over: a launch uses it only if it covers its range.
+struct RowSummary {
+  uint32_t differs;        // bit j set: row j is NOT proven constant (some slot's pattern differs from slot 0's, or no row)
+  uint32_t pad;
+  int64_t n;
+  uint64_t c[9];           // slot 0's patterns (alive: the byte, zero-extended)
+};
+static_assert(sizeof(RowSummary) == 88, "row summary is 88 bytes");
+constexpr int kRowAlive = 7, kRowWeight = 8;
+// The scene's summaries -- a DEVICE array of n_chains RowSummary, or NULL (none: every row is loaded) -- travel in the
+// header's spare words (reserved[1..2]); scene_pack clears them.
+inline const RowSummary* scene_row_summaries(const SceneHeader& h) {
+  const RowSummary* p;
+  memcpy(&p, &h.reserved[1], sizeof(p));
+  return p;
+}
+inline void scene_set_row_summaries(SceneHeader& h, const RowSummary* p) { memcpy(&h.reserved[1], &p, sizeof(p)); }
+static_assert(sizeof(void*) == 8, "the summaries' pointer fills two spare words of the header");
+
 inline int scene_segments(int n_elems) { return (n_elems + kChainMax - 1) / kChainMax; }
 inline int64_t scene_bytes(int n_chains, int n_elems) {
   return (int64_t)sizeof(SceneHeader) + (int64_t)scene_segments(n_elems) * n_chains * (int64_t)sizeof(ChainArgs);

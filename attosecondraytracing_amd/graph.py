@@ -102,6 +102,7 @@ class SceneProgram:
             self.set_detectors(detectors)
         self.host, self.dev = self.be.scene_alloc(self.c, self.m)
         self._uploaded = None
+        self._summaries, self._summary_keys = None, None
         self._signature = None
         self._stepwise = None
         self.post, self.post_result = post, None
@@ -292,12 +293,25 @@ class SceneProgram:
         if self._uploaded is not None:
             self._uploaded.synchronize()       # the previous copy has read the pinned image
         self.flags = self.be.scene_pack(descs, self._views_in, self._views_out, self.c, self.m, self.host, self.readouts)
+        self._summarise()
+        if self._summaries is not None:
+            self.be.scene_set_row_summaries(self.host, self._summaries)      # (scene_pack cleared the header's pointer)
         self._uploaded = self.be.scene_upload(self.host, self.dev)
         self._keep = keep
         for outs in self.outputs:
             for b in outs:
                 if b is not None:
                     b.touch()
+
+    def _summarise(self):
+        """Row summaries of the sources (include/art_hip.h: the launch skips the rows a generated source repeats one value
+        in), kept in step with them: formed here before the capture, and again -- into the SAME device tensor, whose
+        address the graph holds, by launches on the current stream ahead of the replay, without waiting on the host --
+        whenever a source's arrays or weights changed (RayBundle.row_summary_key: `src.data.copy_(...)`, a new
+        intensity's contents, a library kernel followed by touch()).  The weights are the ones the fused read-outs were
+        built with."""
+        self._summaries, self._summary_keys = self._mp._scene_row_summaries(self.be, self.sources, self.readouts,
+                                                                            self._summaries, self._summary_keys)
 
     def _mark(self):
         """The output arrays have new contents: drop cached survivor lists, re-attach the fused read-outs."""
@@ -326,6 +340,8 @@ class SceneProgram:
             self.post_result = self.post(self.outputs)
 
     def run(self):
+        if not self._stepwise:
+            self._summarise()
         if self.graph is not None:
             self.graph.replay()
             if hasattr(self.be, "note_launches"):

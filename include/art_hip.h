@@ -318,6 +318,32 @@ int art_scene_pack(const ArtElementDesc* elems, int32_t n_chains, int32_t n_elem
                    const ArtBundleView* outs, const ArtChainReadout* readouts, void* image_host);
 int art_trace_scene(const void* image_dev, const void* image_host, int64_t n, void* stream);
 
+/* ROW SUMMARIES: a scene launch need not read the rows of its input that hold ONE value in every slot.  A generated
+ * source repeats a value n times in most of the nine per-slot rows a fused trace reads (a point source: ox, oy, oz,
+ * path, alive and a uniform intensity; a plane source: dx, dy, dz, path, alive, intensity -- 41 of 65 bytes per ray).
+ *   art_row_summary_bytes                      size of one summary (a small device-only record: a mask, the slot count it
+ *                                              was formed over, nine 8-byte patterns);
+ *   art_bundle_row_summary                     one memset + ONE streaming kernel over in's ox..dz, path, alive and w (the
+ *                                              weights the chain's read-out will use, or NULL) that writes the summary
+ *                                              to summary_dev (DEVICE).  A row is constant iff every slot's BIT PATTERN
+ *                                              equals slot 0's: -0.0 differs from +0.0, a row of one NaN pattern is
+ *                                              constant.  n == 0 or a NULL row: not constant.  Deterministic (one
+ *                                              integer atomic OR per workgroup); nothing returns to the host.
+ *   art_scene_set_row_summaries                stores the DEVICE pointer to an array of n_chains summaries -- entry c
+ *                                              formed over ins[c] and readouts[c].w -- in the HOST image's header
+ *                                              (spare words: no layout changes, art_scene_bytes is what it was);
+ *                                              NULL detaches.  art_scene_pack clears it: attach after packing.
+ * art_trace_scene hands the pointer to its one-ray kernels, which give a constant row a zero-length buffer descriptor
+ * (no memory traffic) and take its value from the summary: same results, bit for bit.  A summary is used only if the
+ * slot count it was formed over covers the launch; the two-rays-per-lane bodies (masked chains, shared inputs) and
+ * art_trace_chain ignore summaries.  The caller keeps a summary in step with its bundle: whenever the arrays or the
+ * weights change, art_bundle_row_summary runs again into the same buffer, on the stream, ahead of the next launch (a
+ * captured graph keeps the buffer's address).  ART_ROW_SUMMARY=0 in the environment, read at every launch, makes
+ * art_trace_scene ignore attached summaries.                                                                          */
+int64_t art_row_summary_bytes(void);
+int art_bundle_row_summary(const ArtBundleView* in, const double* w, int64_t n, void* summary_dev, void* stream);
+int art_scene_set_row_summaries(void* image_host, const void* summaries_dev);
+
 /* Bundle from array-of-structs input (the layout a caller holding ART Ray lists / (n,3) NumPy arrays has):
  * points[n][3], vectors[n][3] (DEVICE, row-major) -> SoA view; directions normalised like the Ray.vector setter
  * (ART/ModuleOpticalRay.py:85-90), path = path0[i] (or 0 if NULL), incidence = NaN, alive = 1.                      */
