@@ -184,6 +184,13 @@ def SensitivityChart(result, Quantity="centroid_x", PerUnit=None):
     return _plots.SensitivityChart(result, Quantity, PerUnit)
 
 
+def EncircledEnergyCurve(result):
+    """The encircled-energy curves of a focus (the result of Detector.get_EncircledEnergy with Radii): the enclosed share
+    of the power over the radii, one line per plane, with the requested fractions marked at their radii."""
+    from . import _plots
+    return _plots.EncircledEnergyCurve(result)
+
+
 def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston", "tilt")):
     """The fitted wavefront (Detector.get_Wavefront) on the pupil, in waves, with the terms in `Remove` taken out, and a
     bar chart of the Zernike terms' rms contributions in waves."""

@@ -237,6 +237,17 @@ class Detector:
         from . import histogram
         return histogram.detector_histogram(self, RayList, Axes, Bins, Range)
 
+    def get_EncircledEnergy(self, RayList, Fractions=(0.5, 0.8, 0.9), Radii=None, Metric="radius", Centre=None, Shifts=None):
+        """Encircled energy (quantile.EncircledEnergy) of ALL alive rays, ranked on the device: the radius about Centre
+        that holds each of Fractions of the intensity -- the coordinate of an actual ray, found by an exact weighted
+        radix select -- and, with Radii (sorted, mm), the share of the intensity within each of them.  Metric: "radius"
+        (half-energy width = twice the 0.5 radius), "X" or "Y" (half widths) or "Delay" (the half window in fs, symmetric
+        about Centre).  Centre: (X, Y) on the detector (get_PointList2D's coordinates; "Delay": a delay in fs as
+        get_Delays gives it), default the intensity-weighted centroid of each plane; Shifts as in get_FocalField: all
+        planes in one call.  Geometric rays only."""
+        from . import quantile
+        return quantile.encircled_energy(self, RayList, Fractions, Radii, Metric, Centre, Shifts)
+
     def get_FocalField(self, RayList, Size=None, Pixels=128, Centre=None, Shifts=None, Wavelength=None, RefPath=None):
         """Coherent focal field (focal.FocalField) of ALL alive rays, summed on the device as local plane waves on a
         Pixels grid of Size (mm; scalars or one per axis; default 16 Airy radii) about Centre (detector coordinates;

@@ -169,6 +169,11 @@ class OpticalChain:
         from . import tubes
         return tubes.tubes(self, Detector, Source, PerRay)
 
+    def get_EncircledEnergy(self, Detector, Fractions=(0.5, 0.8, 0.9), Radii=None, Metric="radius", Centre=None, Shifts=None):
+        """Detector.get_EncircledEnergy of the chain's last bundle (quantile.EncircledEnergy): the radii that hold Fractions
+        of the intensity on Detector, exactly, and the share within each of Radii."""
+        return Detector.get_EncircledEnergy(self.get_output_rays()[-1], Fractions, Radii, Metric, Centre, Shifts)
+
     def get_Sensitivities(self, Detector, PerRay=False):
         """Alignment sensitivities (sensitivity.Sensitivities): the derivative of the detector centroid, the arrival time,
         the pointing, the spot size and the path spread with respect to the six rigid degrees of freedom of every element

@@ -340,6 +340,29 @@ class ArtFocalImageDesc(C.Structure):
     ]
 
 
+ART_QKEY_GIVEN, ART_QKEY_RADIUS, ART_QKEY_X, ART_QKEY_Y, ART_QKEY_DELAY = range(5)
+ART_QUANTILE_MAX_FRACTIONS = 16
+ART_QUANTILE_MAX_THRESHOLDS = 256
+ART_QUANTILE_SCRATCH_DEFAULT = 1 << 28
+
+
+class ArtQuantileDesc(C.Structure):
+    _fields_ = [
+        ("key", C.c_int32), ("planes", C.c_int32),
+        ("n_fractions", C.c_int32), ("n_thresholds", C.c_int32),
+        ("wshift", C.c_int32), ("centre_given", C.c_int32),
+        ("scratch_bound", C.c_int64),
+        ("keys", C.c_void_p), ("alive", C.c_void_p),
+        ("thresholds_dev", C.c_void_p), ("thresholds_host", C.c_void_p),
+        ("values", C.c_void_p), ("below", C.c_void_p), ("upto", C.c_void_p), ("totals", C.c_void_p),
+        ("rank_sums", C.c_void_p), ("rank_counts", C.c_void_p), ("centres_out", C.c_void_p),
+        ("fraction", C.c_double * ART_QUANTILE_MAX_FRACTIONS),
+        ("det", ArtDetectorDesc),
+        ("shift", C.c_double * ART_FOCAL_MAX_PLANES),
+        ("centre", (C.c_double * 3) * ART_FOCAL_MAX_PLANES),
+    ]
+
+
 # name -> (restype, argtypes); the loader checks every symbol exists (tests/test_abi.py does too)
 PROTOTYPES = {
     "art_abi_version": (C.c_int, []),
@@ -407,6 +430,9 @@ PROTOTYPES = {
     "art_focal_image_scratch_doubles": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
     "art_focal_image": (C.c_int, [C.POINTER(ArtFocalImageDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "art_quantile_scratch_doubles": (C.c_int64, [C.POINTER(ArtQuantileDesc), C.c_int64]),
+    "art_quantiles": (C.c_int, [C.POINTER(ArtQuantileDesc), C.POINTER(ArtBundleView), C.c_void_p, C.c_int64, C.c_void_p,
+                                C.c_void_p]),
     "art_reduce_scratch_doubles": (C.c_int64, []),
     "art_detector_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

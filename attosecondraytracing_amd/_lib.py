@@ -396,6 +396,40 @@ class HipBackend:
                                             totals.data_ptr(), self.stream_ptr()), "art_histogram")
         return counts, wsums, totals, shift
 
+    def quantiles(self, qdesc, view, w, n, thresholds=None):
+        """art_quantiles on the current stream.  qdesc: ArtQuantileDesc with key, planes, fractions, wshift, keys / alive or
+        det / shift / centre and scratch_bound filled in; thresholds: None or a HOST float64 array [planes, R].  The output
+        tensors are made here.  Returns a dict of DEVICE tensors: values [P, K], below, upto [P, K] (int64), totals [P, 3],
+        rank_sums, rank_counts [P, R] (None without thresholds), centres [P, 4] (metrics; None for given keys).  Nothing is
+        read back."""
+        P, K = qdesc.planes, qdesc.n_fractions
+        R = 0 if thresholds is None else int(thresholds.shape[1])
+        qdesc.n_thresholds = R
+        keep = []
+        if R > 0:
+            th = np.ascontiguousarray(thresholds, dtype=np.float64)
+            th_dev = self.from_numpy(th)
+            qdesc.thresholds_host, qdesc.thresholds_dev = th.ctypes.data, th_dev.data_ptr()
+            keep += [th, th_dev]
+        ints = torch.empty(P * (2 * K + 3 + 2 * R), dtype=torch.int64, device=self.device)
+        below, upto = ints[:P * K].view(P, K), ints[P * K:2 * P * K].view(P, K)
+        totals = ints[2 * P * K:2 * P * K + 3 * P].view(P, 3)
+        o = 2 * P * K + 3 * P
+        rank_sums = ints[o:o + P * R].view(P, R) if R else None
+        rank_counts = ints[o + P * R:o + 2 * P * R].view(P, R) if R else None
+        values = torch.empty((P, K), dtype=torch.float64, device=self.device)
+        metric = qdesc.key != _abi.ART_QKEY_GIVEN
+        centres = torch.empty((P, 4), dtype=torch.float64, device=self.device) if metric else None
+        qdesc.values, qdesc.below, qdesc.upto, qdesc.totals = values.data_ptr(), below.data_ptr(), upto.data_ptr(), totals.data_ptr()
+        qdesc.rank_sums = rank_sums.data_ptr() if R else None
+        qdesc.rank_counts = rank_counts.data_ptr() if R else None
+        qdesc.centres_out = centres.data_ptr() if metric else None
+        scratch = self._scratch_for("quantile", "art_quantile_scratch_doubles", C.byref(qdesc), n)
+        self.check(self.fn["art_quantiles"](C.byref(qdesc), None if view is None else C.byref(view), self._ptr(w, n), n,
+                                            scratch.data_ptr(), self.stream_ptr()), "art_quantiles")
+        return {"values": values, "below": below, "upto": upto, "totals": totals, "rank_sums": rank_sums,
+                "rank_counts": rank_counts, "centres": centres, "_keep": keep}
+
     def focal_field(self, fdesc, view, w, n):
         """art_focal_field on the current stream: a new device complex128 tensor [planes, ny, nx] (scratch reused per
         stream)."""

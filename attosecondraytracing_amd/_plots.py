@@ -615,6 +615,32 @@ def SensitivityChart(result, Quantity="centroid_x", PerUnit=None):
     return fig
 
 
+def EncircledEnergyCurve(result):
+    """A quantile.EncircledEnergy as curves: the enclosed share of the power over `Radii`, one step line per plane, with
+    every requested fraction marked at its radius.  Needs a result made with Radii."""
+    plt = _plt()
+    if result.enclosed is None:
+        raise ValueError("EncircledEnergyCurve needs a result of get_EncircledEnergy(..., Radii=...)")
+    unit = "fs" if result.metric == "Delay" else "mm"
+    plt.ion()
+    fig, ax = plt.subplots()
+    for p, s in enumerate(result.shifts):
+        line, = ax.step(result.Radii, result.enclosed[p], where="post", label=f"shift {s:g} mm")
+        ax.plot(result.radii[p], result.fractions, "o", color=line.get_color())
+    for f in result.fractions:
+        ax.axhline(f, color="k", linewidth=0.5, linestyle=":")
+    ax.set_xlabel({"radius": "radius", "X": "half width in X", "Y": "half width in Y", "Delay": "half window"}[result.metric]
+                  + f" ({unit})")
+    ax.set_ylabel("enclosed share of the power")
+    ax.set_ylim(0.0, 1.05)
+    ax.legend()
+    if result.hew is not None:
+        ax.set_title("HEW " + ", ".join(f"{v:.4g}" for v in result.hew) + f" {unit}")
+    fig._art_encircled = result
+    plt.show()
+    return fig
+
+
 def WavefrontMap(RayListAnalysed, Detector, Order=8, Pixels=128, Remove=("piston", "tilt")):
     """The fitted wavefront on the unit pupil in waves (Detector.get_Wavefront, `Remove`d terms taken out) beside a bar
     chart of every term's rms contribution in waves; rms, rms at the best reference point and the Marechal Strehl ratio

@@ -16,6 +16,7 @@
 #include "art_device.h"
 #include "art_coating.h"
 #include "art_tubes.h"
+#include "art_quantile.h"
 #include "art_scene.h"
 
 // The -DART_ZERN_LDS comparison build keeps a persistent grid whose last pass may leave part of a workgroup idle: no
@@ -4442,6 +4443,180 @@ int art_histogram(const ArtHistogramDesc* h, const ArtBundleView* b, const doubl
     return ART_OK;
   });
   return launched("art_histogram launch");
+}
+
+// ------------------------------------------------------------------------------------------- quantiles
+// The scratch of art_quantiles, in doubles: what the whole call keeps, then what one block of pb planes needs.
+namespace {
+struct QuantileLayout {
+  int64_t state, counts, centres, partials;          // offsets of the call's areas
+  int64_t hist, rank, keys;                          // offsets of the block's areas
+  int64_t total;
+  int pb;                                            // planes per block
+};
+
+int quantile_check(const ArtQuantileDesc* d, int64_t n) {
+  if (!d) return fail(ART_ERR_BAD_ARG, "quantile descriptor is NULL");
+  if (d->key < ART_QKEY_GIVEN || d->key > ART_QKEY_DELAY) return fail(ART_ERR_BAD_ARG, "unknown quantile key source");
+  if (d->planes < 1 || d->planes > ART_FOCAL_MAX_PLANES) return fail(ART_ERR_BAD_ARG, "planes must be in 1..ART_FOCAL_MAX_PLANES");
+  if (d->n_fractions < 1 || d->n_fractions > ART_QUANTILE_MAX_FRACTIONS)
+    return fail(ART_ERR_BAD_ARG, "n_fractions must be in 1..ART_QUANTILE_MAX_FRACTIONS");
+  if (d->n_thresholds < 0 || d->n_thresholds > ART_QUANTILE_MAX_THRESHOLDS)
+    return fail(ART_ERR_BAD_ARG, "n_thresholds must be in 0..ART_QUANTILE_MAX_THRESHOLDS");
+  if (n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+  if (n > kMaxRaysPerLaunchHw) return fail(ART_ERR_UNSUPPORTED, "art_quantiles: more than 2^28 slots");
+  if (d->scratch_bound < 0) return fail(ART_ERR_BAD_ARG, "negative scratch bound");
+  if (d->wshift < -1074 || d->wshift > 1074) return fail(ART_ERR_BAD_ARG, "wshift outside [-1074, 1074]");
+  return ART_OK;
+}
+
+QuantileLayout quantile_layout(const ArtQuantileDesc* d, int64_t n) {
+  QuantileLayout L;
+  const int64_t P = d->planes, K = d->n_fractions, R = d->n_thresholds;
+  const bool metric = d->key != ART_QKEY_GIVEN;
+  int64_t o = 0;
+  L.state = o; o += P * K * (int64_t)(sizeof(artq::SelState) / 8);
+  L.counts = o; o += 2 * P;
+  L.centres = o; o += 4 * P;
+  L.partials = o; o += metric ? P * artq::kMomBlocks * artq::kMomSlots : 0;
+  const int64_t per_plane = K * artq::kBins + 2 * (R + 1) + (metric ? n : 0);
+  const int64_t bound = d->scratch_bound > 0 ? d->scratch_bound : ART_QUANTILE_SCRATCH_DEFAULT;
+  int64_t pb = (bound - o) / per_plane;
+  pb = pb < 1 ? 1 : (pb > P ? P : pb);
+  L.pb = (int)pb;
+  L.hist = o; o += pb * K * artq::kBins;
+  L.rank = o; o += pb * 2 * (R + 1);
+  L.keys = o; o += metric ? pb * n : 0;
+  L.total = o;
+  return L;
+}
+}  // namespace
+
+int64_t art_quantile_scratch_doubles(const ArtQuantileDesc* d, int64_t n) {
+  const int rc = quantile_check(d, n);
+  if (rc) return rc;
+  return quantile_layout(d, n).total;
+}
+
+int art_quantiles(const ArtQuantileDesc* d, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
+                  void* stream) {
+#pragma clang fp contract(off)
+  const int rc = quantile_check(d, n);
+  if (rc) return rc;
+  const int P = d->planes, K = d->n_fractions, R = d->n_thresholds;
+  const bool metric = d->key != ART_QKEY_GIVEN;
+  if (!scratch || !d->totals) return fail(ART_ERR_BAD_ARG, "art_quantiles: scratch and totals must not be NULL");
+  if (!d->values || !d->below || !d->upto) return fail(ART_ERR_BAD_ARG, "art_quantiles: values/below/upto missing");
+  for (int k = 0; k < K; ++k)
+    if (!(d->fraction[k] >= 0.0 && d->fraction[k] <= 1.0)) return fail(ART_ERR_BAD_ARG, "art_quantiles: a fraction is outside [0, 1]");
+  if (R > 0) {
+    if (!d->rank_sums || !d->rank_counts || !d->thresholds_dev || !d->thresholds_host)
+      return fail(ART_ERR_BAD_ARG, "art_quantiles: thresholds or rank outputs missing");
+    for (int p = 0; p < P; ++p)
+      for (int r = 0; r < R; ++r) {
+        const double t = d->thresholds_host[(int64_t)p * R + r];
+        if (t != t || (r > 0 && t < d->thresholds_host[(int64_t)p * R + r - 1]))
+          return fail(ART_ERR_BAD_ARG, "art_quantiles: thresholds must be sorted per plane and not NaN");
+      }
+  }
+  artq::PlaneArg pa;
+  artq::CentreArg ca;
+  memset(&pa, 0, sizeof(pa));
+  memset(&ca, 0, sizeof(ca));
+  if (metric) {
+    const double nn = d->det.normal[0] * d->det.normal[0] + d->det.normal[1] * d->det.normal[1] + d->det.normal[2] * d->det.normal[2];
+    if (!(fabs(nn - 1.0) <= 1e-9)) return fail(ART_ERR_BAD_ARG, "art_quantiles: the detector normal must be a unit vector");
+    pa.det = d->det;
+    for (int p = 0; p < P; ++p) {
+      if (!isfinite(d->shift[p])) return fail(ART_ERR_BAD_ARG, "art_quantiles: a shift is not finite");
+      for (int k = 0; k < 3; ++k) {
+        pa.pc[p][k] = d->det.centre[k] + d->shift[p] * d->det.normal[k];       // (two roundings: the moved detector's centre)
+        if (d->centre_given && !isfinite(d->centre[p][k])) return fail(ART_ERR_BAD_ARG, "art_quantiles: a centre is not finite");
+        ca.c[p][k] = d->centre[p][k];
+      }
+    }
+    if (n > 0 && !view_ok(b)) return fail(ART_ERR_BAD_ARG, "bundle view has a NULL array");
+  } else if (n > 0 && !d->keys) {
+    return fail(ART_ERR_BAD_ARG, "art_quantiles: keys is NULL");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const QuantileLayout L = quantile_layout(d, n);
+  auto* state = reinterpret_cast<artq::SelState*>(scratch + L.state);
+  auto* counts = reinterpret_cast<artq::u64*>(scratch + L.counts);
+  double* centres = scratch + L.centres;
+  auto* hist = reinterpret_cast<artq::u64*>(scratch + L.hist);
+  auto* rank = reinterpret_cast<artq::u64*>(scratch + L.rank);
+  double* staged = scratch + L.keys;
+  hipError_t e = hipMemsetAsync(counts, 0, (size_t)2 * P * sizeof(double), s);
+  if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
+  hipLaunchKernelGGL(artq::k_select_init, dim3((P * K + artq::kBlock - 1) / artq::kBlock), dim3(artq::kBlock), 0, s, state, P * K);
+  const int64_t tiles = (n + (int64_t)artq::kBlock * artq::kUnroll - 1) / ((int64_t)artq::kBlock * artq::kUnroll);
+  const int gx = (int)(tiles < 1 ? 1 : (tiles > artq::kSelBlocks ? artq::kSelBlocks : tiles));
+  if (metric) {
+    const bool sums = !d->centre_given || d->key == ART_QKEY_DELAY;
+    const ArtBundleView bv = n > 0 ? *b : ArtBundleView{};
+    if (sums) {
+      const int64_t want = (n + artq::kBlock - 1) / artq::kBlock;
+      const int nb = (int)(want < 1 ? 1 : (want > artq::kMomBlocks ? artq::kMomBlocks : want));
+      const dim3 grid(nb, (P + artq::kMomPlanes - 1) / artq::kMomPlanes);
+      double* partials = scratch + L.partials;
+      hipLaunchKernelGGL(artq::k_metric_moments, grid, dim3(artq::kBlock), 0, s, pa, P, 0, bv, w, n, centres, partials);
+      hipLaunchKernelGGL(artq::k_metric_centres, dim3(P), dim3(64), 0, s, partials, nb, 0, (int)d->centre_given, ca, centres);
+      if (d->key == ART_QKEY_DELAY && !d->centre_given) {
+        hipLaunchKernelGGL(artq::k_metric_moments, grid, dim3(artq::kBlock), 0, s, pa, P, 1, bv, w, n, centres, partials);
+        hipLaunchKernelGGL(artq::k_metric_centres, dim3(P), dim3(64), 0, s, partials, nb, 1, 0, ca, centres);
+      }
+    } else {
+      hipLaunchKernelGGL(artq::k_metric_centres_given, dim3(1), dim3(64), 0, s, ca, P, centres);
+    }
+    if (d->centres_out) {
+      e = hipMemcpyAsync(d->centres_out, centres, (size_t)4 * P * sizeof(double), hipMemcpyDeviceToDevice, s);
+      if (e != hipSuccess) return fail_hip(e, "hipMemcpyAsync");
+    }
+  }
+  const int root = d->key == ART_QKEY_RADIUS;
+  artq::PickArg fr;
+  for (int k = 0; k < ART_QUANTILE_MAX_FRACTIONS; ++k) fr.fraction[k] = k < K ? d->fraction[k] : 0.0;
+  for (int p0 = 0; p0 < P; p0 += L.pb) {
+    const int pb = (P - p0) < L.pb ? (P - p0) : L.pb;
+    const size_t clear = (size_t)((int64_t)L.pb * K * artq::kBins + (int64_t)L.pb * 2 * (R + 1)) * sizeof(double);
+    e = hipMemsetAsync(hist, 0, clear, s);                               // (hist and rank are adjacent)
+    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync");
+    const double* keys = metric ? staged : d->keys + (int64_t)p0 * n;
+    const uint8_t* alive = metric ? (n > 0 ? b->alive : nullptr) : d->alive;
+    if (metric && n > 0) {
+      const int64_t want = (n + artq::kBlock - 1) / artq::kBlock;
+      const int nb = (int)(want > 4096 ? 4096 : want);
+      hipLaunchKernelGGL(artq::k_stage_keys, dim3(nb), dim3(artq::kBlock), 0, s, pa, (int)d->key, p0, pb, *b, n, centres, staged);
+    }
+    const dim3 grid(gx, pb);
+    for (int pass = 0; pass < artq::kPasses; ++pass) {
+      for (int k0 = 0; k0 < K; k0 += artq::kGroups) {
+        const int G = (K - k0) < artq::kGroups ? (K - k0) : artq::kGroups;
+        const size_t lds = (size_t)G * artq::kBins * sizeof(artq::u64);
+        if (pass == 0) {
+          if (k0 == 0)
+            hipLaunchKernelGGL(artq::k_select_hist<true>, grid, dim3(artq::kBlock), lds, s, keys, alive, w, n, (int)d->wshift, pass,
+                               K, k0, state + (int64_t)p0 * K, hist, counts + 2 * p0);
+        } else {
+          hipLaunchKernelGGL(artq::k_select_hist<false>, grid, dim3(artq::kBlock), lds, s, keys, alive, w, n, (int)d->wshift, pass,
+                             K, k0, state + (int64_t)p0 * K, hist, counts + 2 * p0);
+        }
+      }
+      hipLaunchKernelGGL(artq::k_select_pick, dim3(pb), dim3(artq::kBlock), 0, s, state + (int64_t)p0 * K, hist, counts + 2 * p0, K,
+                         pass, fr, root, d->values + (int64_t)p0 * K, reinterpret_cast<long long*>(d->below) + (int64_t)p0 * K,
+                         reinterpret_cast<long long*>(d->upto) + (int64_t)p0 * K,
+                         reinterpret_cast<long long*>(d->totals) + 3 * p0);
+    }
+    if (R > 0) {
+      hipLaunchKernelGGL(artq::k_rank_bins, grid, dim3(artq::kBlock), 0, s, keys, alive, w, n, (int)d->wshift, R, root,
+                         d->thresholds_dev + (int64_t)p0 * R, rank);
+      hipLaunchKernelGGL(artq::k_rank_finish, dim3(pb), dim3(64), 0, s, rank, R,
+                         reinterpret_cast<long long*>(d->rank_sums) + (int64_t)p0 * R,
+                         reinterpret_cast<long long*>(d->rank_counts) + (int64_t)p0 * R);
+    }
+  }
+  return launched("art_quantiles launch");
 }
 
 // the ranges of a focal grid and its planes

@@ -866,6 +866,79 @@ int64_t art_focal_image_scratch_doubles(int32_t nx, int32_t ny, int32_t planes, 
 int art_focal_image(const ArtFocalImageDesc* d, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
                     double* image, void* stream);
 
+/* Exact weighted quantiles and rank sums of one key per slot and plane (added under ABI 14: ArtQuantileDesc,
+ * art_quantiles, art_quantile_scratch_doubles): "which radius holds 50 % of the intensity", the half-energy width, W90,
+ * encircled-energy curves, medians and percentiles of any per-ray quantity.  The answer is the key of an actual slot.
+ * Keys: one fp64 value per slot and plane, ordered as real numbers with -0 = +0; +-inf are ordinary keys; a NaN key makes
+ * the slot INVALID for that plane: it is counted and otherwise ignored.  Dead slots contribute nothing.
+ * Weights: q_i = (int64) rint(ldexp(w_i, wshift)), art_histogram's rule; w = NULL: q_i = 1; w must be finite and >= 0 (a
+ * negative q counts as 0) and wshift such that no sum overflows int64.  Every sum is a sum of these integers (integer
+ * atomics and integer folds only): the same bytes on every run, whatever the grid and the plane blocking.
+ * Quantile, per plane, W = sum q_i over the valid slots, per fraction f in [0, 1]:
+ *     T = min(W, max(1, (int64) ceil(f * (double) W)))
+ *     value = the smallest key v with  sum_{key <= v} q  >=  T
+ *     below = sum_{key < v} q,   upto = sum_{key <= v} q           (below < T <= upto)
+ * W == 0: value = NaN, below = upto = 0.  totals (per plane): [0] W [1] valid slots [2] invalid slots.
+ * Rank sums, per plane and threshold t (sorted ascending per plane, +-inf allowed):
+ *     rank_sums = sum q_i [key_i <= t],   rank_counts = the number of valid slots with key_i <= t.
+ * The select is a most-significant-digit radix select in six passes (digits of 9 and 5 x 11 bits of the order-preserving
+ * uint64 image of the key), all enqueued on the stream with nothing read back in between (csrc/art_quantile.h).
+ * Key sources:
+ *   ART_QKEY_GIVEN   keys: DEVICE [planes][n]; alive: DEVICE [n] or NULL (every slot alive); b is not read.
+ *   detector metrics of the bundle b on the planes det.centre + shift[p] * det.normal (art_focal_field's convention;
+ *   plane p is read as a detector of its own, exactly as art_detector reads it), with centres (cx, cy, c) per plane:
+ *     ART_QKEY_RADIUS  key = (X - cx)^2 + (Y - cy)^2; values and thresholds are its SQUARE ROOT (mm): a slot is within
+ *                      threshold t iff sqrt(key) <= t
+ *     ART_QKEY_X       |X - cx|        ART_QKEY_Y   |Y - cy|          (mm)
+ *     ART_QKEY_DELAY   |delay - c|, delay = ((opl - L_p) / 299792458000.0) * 1e15 (fs), L_p the mean of opl over the
+ *                      alive slots on plane p, formed on the device
+ *   centre_given = 1: centre[p] = (cx, cy, c) is used as given; 0: the w-weighted centroid of (X, Y, delay) over the alive
+ *   slots of each plane, formed on the device.  centres_out (DEVICE [planes][4] or NULL): cx, cy, c, L_p as used (NaN
+ *   without alive slots; L_p is 0 where no delay is formed).
+ * Outputs (DEVICE, all written): values [planes][n_fractions] (double), below, upto [planes][n_fractions] (int64),
+ * totals [planes][3] (int64), rank_sums, rank_counts [planes][n_thresholds] (int64).
+ * thresholds_dev: DEVICE [planes][n_thresholds], a copy of thresholds_host (HOST, read for validation).
+ * The planes are processed in blocks whose scratch stays within scratch_bound doubles (0: ART_QUANTILE_SCRATCH_DEFAULT; at
+ * least one plane per block whatever the bound); the result does not depend on it.
+ * scratch: DEVICE, art_quantile_scratch_doubles(d, n) doubles (negative: the error code of a bad descriptor).
+ * Limits: 0 <= n <= 2^28 (ART_ERR_UNSUPPORTED beyond), 1 <= planes <= ART_FOCAL_MAX_PLANES, 1 <= n_fractions <= ART_QUANTILE_MAX_FRACTIONS = 16,
+ * 0 <= n_thresholds <= ART_QUANTILE_MAX_THRESHOLDS = 256, fractions in [0, 1], thresholds sorted and not NaN, wshift in
+ * [-1074, 1074], finite shifts and given centres, a unit detector normal, scratch_bound >= 0, values, below, upto, totals
+ * and scratch non-NULL, the rank outputs and both threshold arrays non-NULL when n_thresholds > 0, keys (GIVEN) or a
+ * whole bundle view (metrics) when n > 0: ART_ERR_BAD_ARG otherwise, with nothing launched.  Geometric rays only: the encircled energy of a diffraction image is not this. */
+enum ArtQuantileKey { ART_QKEY_GIVEN = 0, ART_QKEY_RADIUS = 1, ART_QKEY_X = 2, ART_QKEY_Y = 3, ART_QKEY_DELAY = 4 };
+#define ART_QUANTILE_MAX_FRACTIONS 16
+#define ART_QUANTILE_MAX_THRESHOLDS 256
+#define ART_QUANTILE_SCRATCH_DEFAULT ((int64_t)1 << 28)   /* doubles: 2 GiB */
+/* (declared by its tag: C callers write `struct ArtQuantileDesc`) */
+struct ArtQuantileDesc {
+  int32_t key;                 /* ArtQuantileKey                                                                     */
+  int32_t planes;
+  int32_t n_fractions;
+  int32_t n_thresholds;
+  int32_t wshift;              /* the fixed-point shift of the weights                                               */
+  int32_t centre_given;        /* metrics: 1 = centre[] is used, 0 = the weighted centroid is formed on the device   */
+  int64_t scratch_bound;       /* doubles; 0: ART_QUANTILE_SCRATCH_DEFAULT                                           */
+  const double* keys;          /* GIVEN: DEVICE [planes][n]                                                          */
+  const uint8_t* alive;        /* GIVEN: DEVICE [n] or NULL                                                          */
+  const double* thresholds_dev;   /* DEVICE [planes][n_thresholds]                                                   */
+  const double* thresholds_host;  /* HOST, the same values                                                           */
+  double* values;              /* DEVICE outputs, see above                                                          */
+  int64_t* below;
+  int64_t* upto;
+  int64_t* totals;
+  int64_t* rank_sums;
+  int64_t* rank_counts;
+  double* centres_out;
+  double fraction[ART_QUANTILE_MAX_FRACTIONS];
+  ArtDetectorDesc det;         /* metrics                                                                            */
+  double shift[ART_FOCAL_MAX_PLANES];
+  double centre[ART_FOCAL_MAX_PLANES][3];
+};
+int64_t art_quantile_scratch_doubles(const struct ArtQuantileDesc* d, int64_t n);
+int art_quantiles(const struct ArtQuantileDesc* d, const ArtBundleView* b, const double* w, int64_t n, double* scratch,
+                  void* stream);
+
 /* Masked reductions over alive rays, deterministic (fixed two-level tree, no float atomics).
  * out16 (DEVICE, 16 doubles):
  *   [0] count  [1] sum opl  [2] min X [3] max X [4] min Y [5] max Y  [6] sum X [7] sum Y
