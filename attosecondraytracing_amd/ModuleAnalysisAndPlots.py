@@ -184,6 +184,14 @@ def SensitivityChart(result, Quantity="centroid_x", PerUnit=None):
     return _plots.SensitivityChart(result, Quantity, PerUnit)
 
 
+def CompensationChart(result, After=None):
+    """A compensator solve (the result of OpticalChain.get_Compensation) as bar charts: the singular values of the solved
+    matrix, and the variances of X, Y and the path before, predicted and -- with After, the variances of a re-trace --
+    after the moves."""
+    from . import _plots
+    return _plots.CompensationChart(result, After)
+
+
 def EncircledEnergyCurve(result):
     """The encircled-energy curves of a focus (the result of Detector.get_EncircledEnergy with Radii): the enclosed share
     of the power over the radii, one line per plane, with the requested fractions marked at their radii."""

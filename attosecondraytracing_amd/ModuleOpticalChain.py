@@ -184,6 +184,25 @@ class OpticalChain:
         from . import sensitivity
         return sensitivity.sensitivity(self, Detector, PerRay)
 
+    def get_Compensation(self, Detector, DOFs, Weights=(1, 1, 0), Rcond=1e-9, HoldCentroid=False):
+        """The compensator solve (alignment.Compensation): which moves of the few adjusters in DOFs make the spot on
+        Detector smallest, and how small -- from the covariances between their columns of get_Sensitivities, formed in one
+        device pass over get_output_rays() and source_rays, and a truncated SVD on the host.  DOFs: a list of at most 8 of
+        (k, "pitch"), ("source", "tilt_x") ... as in get_Sensitivities, or ("detector", "shift_normal").  Weights: of the
+        variances of X, Y and the path in the objective, (0, 0, 1) minimises the duration; Rcond: singular values below
+        Rcond x the largest are not moved along; HoldCentroid: only moves that leave the centroid in place.  First order;
+        DeformedMirror, Grating and MirrorFreeform elements raise NotImplementedError."""
+        from . import alignment
+        return alignment.compensation(self, Detector, DOFs, Weights, Rcond, HoldCentroid)
+
+    def align(self, Detector, DOFs, Weights=(1, 1, 0), Iterations=5, Tolerance=1e-9, Rcond=1e-9, HoldCentroid=False):
+        """Gauss-Newton alignment on re-traces: get_Compensation, its moves applied to a copy, a re-trace, and again, at
+        most Iterations times.  A step whose re-traced objective grows is halved (at most 4 times); the loop stops when the
+        relative decrease falls below Tolerance.  Returns (chain, detector, alignment.AlignmentReport); this chain and
+        Detector are never changed."""
+        from . import alignment
+        return alignment.align(self, Detector, DOFs, Weights, Iterations, Tolerance, Rcond, HoldCentroid)
+
     def get_FocalPulse(self, Coatings, Detector, DeltaFT, Polarisation, Size=None, Pixels=64, Centre=None, Shifts=None,
                        Wavelength=None, RefPath=None, Spectrum=None, TimeWindow=None, Times=256, ScratchBytes=None):
         """The space-time VECTOR field of a broadband pulse at focus behind the chain's coatings

@@ -303,6 +303,31 @@ class ArtSensitivityJob(C.Structure):
     ]
 
 
+ART_ALIGN_MAX_DOFS = 8
+ART_ALIGN_PILOT = 1024
+ART_ALIGN_DOF_DETECTOR = -1
+ART_ALIGN_CENTRES = 8
+ART_ALIGN_MEANS = 32
+ART_ALIGN_CROSS = 56
+ART_ALIGN_PAIRS = 80
+ART_ALIGN_DOUBLES = 192
+
+
+class ArtAlignmentJob(C.Structure):
+    _fields_ = [
+        ("views", C.c_void_p),
+        ("elems", C.c_void_p),
+        ("quadrics", C.c_void_p),
+        ("n_elems", C.c_int32),
+        ("n_dofs", C.c_int32),
+        ("n", C.c_int64),
+        ("det", ArtDetectorDesc),
+        ("w", C.c_void_p),
+        ("origin", C.c_double * 3),
+        ("dofs", C.c_int32 * ART_ALIGN_MAX_DOFS),
+    ]
+
+
 ART_FOCAL_VECTOR_SCRATCH_DEFAULT = 1 << 29
 
 
@@ -418,6 +443,8 @@ PROTOTYPES = {
     "art_ray_tubes": (C.c_int, [C.c_void_p, C.POINTER(ArtTubeJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_sensitivities_scratch_doubles": (C.c_int64, [C.POINTER(ArtSensitivityJob), C.c_int32]),
     "art_sensitivities": (C.c_int, [C.c_void_p, C.POINTER(ArtSensitivityJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "art_alignment_sums_scratch_doubles": (C.c_int64, [C.POINTER(ArtAlignmentJob), C.c_int32]),
+    "art_alignment_sums": (C.c_int, [C.c_void_p, C.POINTER(ArtAlignmentJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "art_focal_vector_spectrum_scratch_doubles": (C.c_int64, [C.POINTER(ArtFocalVectorSpectrumDesc)]),
     "art_focal_vector_spectrum": (C.c_int, [C.POINTER(ArtFocalVectorSpectrumDesc), C.POINTER(ArtBundleView), C.c_void_p,
                                             C.POINTER(ArtCoating), C.POINTER(ArtCoatingMaterial), C.c_void_p,

@@ -734,6 +734,43 @@ class HipBackend:
                                                 self.stream_ptr()), "art_sensitivities")
         return out
 
+    def alignment_sums(self, jobs, views, elems, quadrics, out=None):
+        """art_alignment_sums for a list of ArtAlignmentJob, with the tables as sensitivities takes and uploads them.
+        Returns the DEVICE tensor [len(jobs), ART_ALIGN_DOUBLES] (`out`, when the caller brings one).  An element the pass
+        does not cover raises NotImplementedError with the library's message."""
+        c = len(jobs)
+        if out is None:
+            out = torch.empty((c, _abi.ART_ALIGN_DOUBLES), dtype=torch.float64, device=self.device)
+        if out.shape != (c, _abi.ART_ALIGN_DOUBLES) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 tensor [jobs, ART_ALIGN_DOUBLES]")
+        parts = []
+        for v, e, q in zip(views, elems, quadrics):
+            parts += [bytes(v), bytes(e), b"" if q is None else bytes(q)]
+        blob = b"".join(parts)
+        dev = self._upload_table((C.c_char * len(blob)).from_buffer_copy(blob), "alignment tables")
+        off = 0
+        jhost, jdev = (_abi.ArtAlignmentJob * c)(), (_abi.ArtAlignmentJob * c)()
+        for k, (j, v, e, q) in enumerate(zip(jobs, views, elems, quadrics)):
+            jhost[k] = j
+            jdev[k] = j
+            jhost[k].views = jdev[k].views = dev.data_ptr() + off
+            off += C.sizeof(v)
+            jhost[k].elems, jdev[k].elems = C.addressof(e), dev.data_ptr() + off
+            off += C.sizeof(e)
+            if q is not None:
+                jhost[k].quadrics, jdev[k].quadrics = C.addressof(q), dev.data_ptr() + off
+                off += C.sizeof(q)
+        ns = self.fn["art_alignment_sums_scratch_doubles"](jhost, c)
+        if ns == _abi.ART_ERR_UNSUPPORTED:
+            raise NotImplementedError(self.last_error())
+        if ns < 0:
+            raise ArtError(f"art_alignment_sums_scratch_doubles failed with code {ns}: {self.last_error()}")
+        scratch = self.scratch("alignment_sums", ns, torch.float64)
+        table = self._upload_table(jdev)
+        self.check(self.fn["art_alignment_sums"](table.data_ptr(), jhost, c, scratch.data_ptr(), out.data_ptr(),
+                                                 self.stream_ptr()), "art_alignment_sums")
+        return out
+
     def focal_vector_tables(self, vdesc, views, coatings, materials):
         """Uploads the tables of art_focal_vector_spectrum and points vdesc at them (`views`, `materials`, `n_coatings`).
         views: the HOST ctypes array of the chain's K + 1 views; coatings: a list of ArtCoating; materials: float64

@@ -615,6 +615,39 @@ def SensitivityChart(result, Quantity="centroid_x", PerUnit=None):
     return fig
 
 
+def CompensationChart(result, After=None):
+    """An alignment.Compensation as two bar charts: the singular values of the solved matrix (log scale; the ones below
+    the truncation are the directions the adjusters cannot or need not move along) and the variances of X, Y and the path
+    before, as the solve predicts them and -- with After = the [3] variances of a re-trace, e.g. the last entry of an
+    AlignmentReport's `variance` -- after the moves."""
+    plt = _plt()
+    plt.ion()
+    fig, axes = plt.subplots(2, 1)
+    sv = np.asarray(result.singular_values, dtype=float)
+    axes[0].bar(range(len(sv)), sv)
+    if (sv > 0).any():
+        axes[0].set_yscale("log")
+    axes[0].set_xticks(range(len(sv)))
+    axes[0].set_ylabel("singular values")
+    axes[0].set_title(f"Compensation over {len(result.names)} degrees of freedom, rank {result.rank}, {result.count} rays")
+    series = [("before", result.variance), ("predicted", result.variance_predicted)]
+    if After is not None:
+        series.append(("re-traced", np.asarray(After, dtype=float).reshape(3)))
+    width = 0.8 / len(series)
+    for k, (label, v) in enumerate(series):
+        axes[1].bar(np.arange(3) + k * width, np.asarray(v, dtype=float), width, label=label)
+    axes[1].set_xticks(np.arange(3) + 0.4 - width / 2)
+    axes[1].set_xticklabels(["X", "Y", "path"])
+    if (np.asarray(result.variance) > 0).any():
+        axes[1].set_yscale("log")
+    axes[1].set_ylabel("variance (mm$^2$)")
+    axes[1].legend()
+    fig.tight_layout()
+    fig._art_compensation = result
+    plt.show()
+    return fig
+
+
 def EncircledEnergyCurve(result):
     """A quantile.EncircledEnergy as curves: the enclosed share of the power over `Radii`, one step line per plane, with
     every requested fraction marked at its radius.  Needs a result made with Radii."""

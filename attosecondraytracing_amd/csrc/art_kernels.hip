@@ -2908,6 +2908,219 @@ __global__ __launch_bounds__(kFoldBlock) void k_sensitivities_fold(const ArtSens
   if (threadIdx.x == 0) *dst = v;
 }
 
+// ------------------------------------------------------------------------------------------- compensator sums
+// art_alignment_sums (include/art_hip.h): the Gram matrix of a CHOSEN handful of the columns above, in k_sensitivities'
+// shape -- grid (tiles of 256 slots, jobs), one ray per lane -- but with all C <= 8 columns of a job in ONE lane, because a
+// product needs both of its columns there.  The kernels are compiled for NC = 2, 4, 6, 8 columns; a job runs in the one
+// for NC = C rounded up to even, whichever jobs share its call (a workgroup of another NC returns at once), with its
+// spare column idle.  Which column moves at which element comes from the job: wave-uniform branches on scalar loads
+// around columns at fixed places (artt::step_selected).  k_alignment_pilot runs the same lane over the first
+// min(n, ART_ALIGN_PILOT) slots (at most 4 tiles) and leaves per tile sum w and sum w dQ_a behind the scratch of the main
+// pass; align_centre adds them in tile order and divides: the centres.  k_alignment_sums stages them in LDS, subtracts
+// them and stores per tile 8 + 3 (2 NC + NC (NC + 1) / 2) partial sums (block_sum_store, a chunk per coordinate so that
+// they are never live at once); k_alignment_fold folds them per entry in tile order and records the centres.
+constexpr int kAlignIdle = 6 * 4096;      // the id of a spare column: a group no chain has
+constexpr int align_bucket(const int c) { return (c + 1) / 2 * 2; }
+constexpr int align_per_q(const int nc) { return 2 * nc + nc * (nc + 1) / 2; }
+constexpr int align_stats(const int nc) { return kSensRow0 + 3 * align_per_q(nc); }
+
+template <int NC>
+struct AlignRay {
+  bool live;
+  double w, X, Y, L, d[3][NC];            // d[q][a]: dX, dY, dL of the column at place a
+};
+
+template <int NC>
+__device__ __forceinline__ void align_ray(const ArtAlignmentJob& jb, const unsigned i, AlignRay<NC>& r) {
+  const int64_t n = jb.n;
+  const int K = jb.n_elems, C = jb.n_dofs;
+  const unsigned nb8 = (unsigned)(n * 8), nb1 = (unsigned)n;    // n <= 2^28 (checked by the host)
+  const ArtBundleView* views = jb.views;
+  bool live = true;                                             // (slots >= n fall outside the descriptor: they read 0)
+  for (int e = 0; e <= K; ++e)
+    live = live && __builtin_amdgcn_raw_buffer_load_b8(rsrc_of(pol_alive(views, e), nb1), (int)i, 0, ART_LD_AUX) != 0;
+  const unsigned o8 = live ? i * 8u : kDropOffset;
+  r.live = live;
+  r.w = jb.w ? ld_f64(rsrc_of(const_cast<double*>(jb.w), nb8), o8) : 1.0;
+  int id[NC];
+  int first = K;
+#pragma unroll
+  for (int a = 0; a < NC; ++a) {
+    id[a] = a < C ? jb.dofs[a] : kAlignIdle;
+    const int f = a < C ? artt::dof_first(id[a], K) : K;
+    first = f < first ? f : first;
+  }
+  double P[3], D[3];
+  tube_ray(views, first, nb8, o8, P, D);
+  artt::Column c[NC];
+#pragma unroll
+  for (int a = 0; a < NC; ++a) {
+    artt::seed_selected(id[a], D, c[a]);                        // (a source column makes first 0)
+    // a seed is the same in every lane (a unit vector, zeros), and 8 columns of them in scalar registers up to their own
+    // elements would not fit: they start in vector registers
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      asm volatile("" : "+v"(c[a].dP[q]));
+      asm volatile("" : "+v"(c[a].dD[q]));
+    }
+    asm volatile("" : "+v"(c[a].dL));
+  }
+  for (int e = first; e < K; ++e) {
+    double Pn[3], Dn[3];
+    tube_ray(views, e + 1, nb8, o8, Pn, Dn);
+    artt::Surface s;
+    artt::load_surface((tube_elem_t)jb.elems + e, (tube_quad_t)jb.quadrics + e, s);
+    artt::Hit h;
+    artt::hit_of(s, D, P, Pn, h);
+#pragma unroll
+    for (int a = 0; a < NC; ++a) {
+      int ida = id[a];                                          // (opaque: the branches' conditions are formed here, per
+      asm volatile("" : "+s"(ida));                             //  element, not kept for all columns around the loop)
+      artt::step_selected(s, h, D, Pn, ida, e, c[a]);
+    }
+#pragma unroll
+    for (int q = 0; q < 3; ++q) { P[q] = Pn[q]; D[q] = Dn[q]; }
+  }
+  const double path = ld_f64(rsrc_of(((pol_view_t)views + K)->path, nb8), o8);
+  // the nominal read-out about the caller's origin (k_sensitivities' lines)
+  const double toC[3] = {jb.det.centre[0] - P[0], jb.det.centre[1] - P[1], jb.det.centre[2] - P[2]};
+  const double tdet = artt::dot(jb.det.normal, toC) / artt::dot(jb.det.normal, D);
+  const double rel[3] = {fma(tdet, D[0], -toC[0]), fma(tdet, D[1], -toC[1]), fma(tdet, D[2], -toC[2])};
+  double xy[3];
+  artt::rot(jb.det.rot, rel, xy);
+  r.X = xy[0] - jb.origin[0];
+  r.Y = xy[1] - jb.origin[1];
+  r.L = (path + tdet) - jb.origin[2];
+#pragma unroll
+  for (int a = 0; a < NC; ++a) {
+    artt::readout_selected(id[a], D, P, jb.det.centre, jb.det.normal, jb.det.rot, c[a], r.d[0][a], r.d[1][a]);
+    r.d[2][a] = c[a].dL;
+  }
+}
+
+// grid (tiles of the prefix, jobs): per tile sum w and the 3 NC sums w dQ_a of the first min(n, ART_ALIGN_PILOT) slots, at
+// pilot[job][tile][kAlignPilotStats]
+constexpr int kAlignPilotTiles = ART_ALIGN_PILOT / kBlock, kAlignPilotStats = 1 + 3 * ART_ALIGN_MAX_DOFS;
+__host__ __device__ inline int64_t align_pilot_tiles(const int64_t n) { return pol_tiles(n < ART_ALIGN_PILOT ? n : ART_ALIGN_PILOT); }
+
+template <int NC>
+__global__ __launch_bounds__(kBlock) void k_alignment_pilot(const ArtAlignmentJob* __restrict__ jobs, double* pilot) {
+  const ArtAlignmentJob& jb = jobs[blockIdx.y];
+  if (align_bucket(jb.n_dofs) != NC || (int64_t)blockIdx.x >= align_pilot_tiles(jb.n)) return;
+  AlignRay<NC> r;
+  align_ray<NC>(jb, blockIdx.x * kBlock + threadIdx.x, r);     // (the last tile's slots >= n are not alive)
+  double acc[1 + 3 * NC];
+  acc[0] = r.live ? r.w : 0.0;
+#pragma unroll
+  for (int q = 0; q < 3; ++q)
+#pragma unroll
+    for (int a = 0; a < NC; ++a) acc[1 + q * NC + a] = r.live ? r.w * r.d[q][a] : 0.0;
+  block_sum_store<1 + 3 * NC>(acc, pilot + ((int64_t)blockIdx.y * kAlignPilotTiles + blockIdx.x) * kAlignPilotStats);
+}
+
+// centre_a^Q of a job from its pilot partials (k_alignment_pilot<nc>'s), in tile order: 0 for a place >= C and when no ray of
+// the prefix counts.  The main pass and the fold both call it: the table records exactly what was subtracted.
+__device__ __forceinline__ double align_centre(const double* part, const int tiles, const int nc, const int C, const int q,
+                                               const int a) {
+  if (a >= C) return 0.0;
+  double sw = 0.0, v = 0.0;
+  for (int t = 0; t < tiles; ++t) {
+    sw += part[t * kAlignPilotStats];
+    v += part[t * kAlignPilotStats + 1 + q * nc + a];
+  }
+  return sw > 0.0 ? v / sw : 0.0;
+}
+
+template <int NC>
+__global__ __launch_bounds__(kBlock) void k_alignment_sums(const ArtAlignmentJob* __restrict__ jobs, const int64_t per_job,
+                                                           double* scratch, const double* pilot) {
+  const ArtAlignmentJob& jb = jobs[blockIdx.y];
+  if (align_bucket(jb.n_dofs) != NC || (int64_t)blockIdx.x >= pol_tiles(jb.n)) return;   // (the grid covers the largest job)
+  __shared__ double cen[3 * ART_ALIGN_MAX_DOFS];            // (LDS, not 48 scalar registers)
+  if (threadIdx.x < 3 * ART_ALIGN_MAX_DOFS)
+    cen[threadIdx.x] = align_centre(pilot + (int64_t)blockIdx.y * kAlignPilotTiles * kAlignPilotStats, (int)align_pilot_tiles(jb.n),
+                                    NC, jb.n_dofs, threadIdx.x / ART_ALIGN_MAX_DOFS, threadIdx.x % ART_ALIGN_MAX_DOFS);
+  __syncthreads();
+  AlignRay<NC> r;
+  align_ray<NC>(jb, blockIdx.x * kBlock + threadIdx.x, r);
+  const bool live = r.live;
+  const double ww = live ? r.w : 0.0;
+  double* dst = scratch + (int64_t)blockIdx.y * per_job + (int64_t)blockIdx.x * align_stats(NC);
+  const double Q[3] = {live ? r.X : 0.0, live ? r.Y : 0.0, live ? r.L : 0.0};
+  {
+    double acc[kSensRow0];
+    acc[0] = live ? 1.0 : 0.0;
+    acc[1] = ww;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      acc[2 + q] = ww * Q[q];
+      acc[5 + q] = ww * Q[q] * Q[q];
+    }
+    block_sum_store<kSensRow0>(acc, dst);
+  }
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    constexpr int kPerQ = align_per_q(NC);
+    double d[NC], acc[kPerQ];
+#pragma unroll
+    for (int a = 0; a < NC; ++a) {
+      d[a] = live ? r.d[q][a] - cen[ART_ALIGN_MAX_DOFS * q + a] : 0.0;
+      acc[a] = ww * d[a];
+      acc[NC + a] = ww * Q[q] * d[a];
+    }
+    int p = 2 * NC;
+#pragma unroll
+    for (int a = 0; a < NC; ++a)
+#pragma unroll
+      for (int b = a; b < NC; ++b) acc[p++] = ww * d[a] * d[b];
+    if (q) __syncthreads();               // (the previous chunk's totals have been read)
+    block_sum_store<kPerQ>(acc, dst + kSensRow0 + q * kPerQ);
+  }
+}
+
+// grid (ART_ALIGN_DOUBLES, jobs): workgroup (x, j) folds entry x of job j's block in tile order
+__global__ __launch_bounds__(kFoldBlock) void k_alignment_fold(const ArtAlignmentJob* __restrict__ jobs, const int64_t per_job,
+                                                               const double* scratch, const double* pilot, double* out) {
+  const int x = blockIdx.x, j = blockIdx.y;
+  const int C = jobs[j].n_dofs, nc = align_bucket(C), per_q = align_per_q(nc);
+  if (x >= ART_ALIGN_CENTRES && x < ART_ALIGN_MEANS) {
+    const int k = x - ART_ALIGN_CENTRES;
+    if (threadIdx.x == 0)
+      out[(int64_t)j * ART_ALIGN_DOUBLES + x] = align_centre(pilot + (int64_t)j * kAlignPilotTiles * kAlignPilotStats,
+                                                             (int)align_pilot_tiles(jobs[j].n), nc, C, k / ART_ALIGN_MAX_DOFS,
+                                                             k % ART_ALIGN_MAX_DOFS);
+    return;
+  }
+  int slot = -1;
+  if (x < kSensRow0) {
+    slot = x;
+  } else if (x < ART_ALIGN_PAIRS) {
+    const int k = x - ART_ALIGN_MEANS, kind = k / (3 * ART_ALIGN_MAX_DOFS), q = k / ART_ALIGN_MAX_DOFS % 3, a = k % ART_ALIGN_MAX_DOFS;
+    if (a < C) slot = kSensRow0 + q * per_q + kind * nc + a;
+  } else if (x < ART_ALIGN_PAIRS + 3 * 36) {
+    const int k = x - ART_ALIGN_PAIRS, q = k / 36;
+    int a = 0, p = k % 36;
+    for (; p >= ART_ALIGN_MAX_DOFS - a; ++a) p -= ART_ALIGN_MAX_DOFS - a;   // row a of the table holds b = a .. 7
+    if (a + p < C) slot = kSensRow0 + q * per_q + 2 * nc + a * (2 * nc + 1 - a) / 2 + p;
+  }
+  double v = 0.0;
+  if (slot >= 0) fold_range(scratch + (int64_t)j * per_job + slot, 0, pol_tiles(jobs[j].n), RSUM, &v, align_stats(nc));
+  if (threadIdx.x == 0) out[(int64_t)j * ART_ALIGN_DOUBLES + x] = v;
+}
+
+// the pilot or the main pass for NC columns, when bit NC / 2 - 1 of `buckets` says that a job of the call runs in it
+template <int NC>
+static void align_launch(const bool first, const unsigned buckets, const ArtAlignmentJob* jobs_dev, const int32_t n_jobs,
+                         const int64_t tiles, const int64_t per_job, double* scratch, double* pilot, hipStream_t s) {
+  if (!(buckets & (1u << (NC / 2 - 1)))) return;
+  if (first)
+    hipLaunchKernelGGL(k_alignment_pilot<NC>, dim3((unsigned)align_pilot_tiles(tiles * kBlock), n_jobs), dim3(kBlock), 0, s,
+                       jobs_dev, pilot);
+  else
+    hipLaunchKernelGGL(k_alignment_sums<NC>, dim3((unsigned)tiles, n_jobs), dim3(kBlock), 0, s, jobs_dev, per_job, scratch,
+                       (const double*)pilot);
+}
+
 // ------------------------------------------------------------------------------------------- vector focal spectrum
 // art_focal_vector_spectrum (include/art_hip.h): art_focal_spectrum's sum with a complex amplitude per (ray, wavenumber,
 // component), the field of art_polarisation carried through coatings whose optical constants depend on the wavenumber.
@@ -5138,6 +5351,79 @@ int art_sensitivities(const ArtSensitivityJob* jobs_dev, const ArtSensitivityJob
   hipLaunchKernelGGL(k_sensitivities_fold, dim3(ART_SENS_DOUBLES, 1 + ART_SENS_COLS * (kmax + 1), n_jobs), dim3(kFoldBlock), 0,
                      s, jobs_dev, per_job, tiles, (const double*)scratch, out);
   return launched("art_sensitivities launch");
+}
+
+// validates a compensator job table (host copies of the elements included); *nmax: the largest slot count, *buckets: bit
+// NC / 2 - 1 is set when a job runs in the kernels for NC columns
+static int align_check_jobs(const ArtAlignmentJob* jobs, int32_t n_jobs, int64_t* nmax, unsigned* buckets) {
+  if (!jobs) return fail(ART_ERR_BAD_ARG, "alignment job table is NULL");
+  if (n_jobs < 1 || n_jobs > ART_TUBE_MAX_JOBS) return fail(ART_ERR_BAD_ARG, "n_jobs must be in 1..ART_TUBE_MAX_JOBS");
+  *nmax = 0;
+  *buckets = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const ArtAlignmentJob& jb = jobs[j];
+    if (jb.n < 0) return fail(ART_ERR_BAD_ARG, "negative ray count");
+    if (jb.n > kMaxRaysPerLaunchHw) return fail(ART_ERR_UNSUPPORTED, "more than 2^28 rays per chain in one alignment call");
+    if (jb.n_elems < 1 || jb.n_elems > ART_TUBE_MAX_ELEMS)
+      return fail(ART_ERR_BAD_ARG, "an alignment job must have 1..ART_TUBE_MAX_ELEMS elements");
+    if (jb.n_dofs < 1 || jb.n_dofs > ART_ALIGN_MAX_DOFS)
+      return fail(ART_ERR_BAD_ARG, "an alignment job must have 1..ART_ALIGN_MAX_DOFS degrees of freedom");
+    for (int a = 0; a < jb.n_dofs; ++a) {
+      if (jb.dofs[a] < ART_ALIGN_DOF_DETECTOR || jb.dofs[a] >= ART_SENS_COLS * (jb.n_elems + 1))
+        return fail(ART_ERR_BAD_ARG, "an alignment job's degree of freedom is out of range: -1 or 0 .. 6 (K + 1) - 1");
+      for (int b = 0; b < a; ++b)
+        if (jb.dofs[b] == jb.dofs[a]) return fail(ART_ERR_BAD_ARG, "an alignment job names a degree of freedom twice (duplicate id)");
+    }
+    if (!jb.views || !jb.elems) return fail(ART_ERR_BAD_ARG, "an alignment job's views or elems is NULL");
+    double nn = 0.0;
+    bool finite = true;
+    for (int q = 0; q < 3; ++q) {
+      nn += jb.det.normal[q] * jb.det.normal[q];
+      finite = finite && isfinite(jb.det.centre[q]) && isfinite(jb.det.normal[q]) && isfinite(jb.origin[q]);
+    }
+    for (int q = 0; q < 9; ++q) finite = finite && isfinite(jb.det.rot[q]);
+    if (!finite || !(fabs(nn - 1.0) <= 1e-12))
+      return fail(ART_ERR_BAD_ARG, "an alignment job needs a detector (finite centre and rot, unit normal) and a finite origin");
+    const int bad = tube_check_elems("alignment sums", jb.elems, jb.quadrics, jb.n_elems);
+    if (bad) return bad;
+    *nmax = jb.n > *nmax ? jb.n : *nmax;
+    *buckets |= 1u << (align_bucket(jb.n_dofs) / 2 - 1);
+  }
+  return ART_OK;
+}
+
+// the partial sums per tile of the call's widest kernel
+static int align_stride(const unsigned buckets) {
+  return align_stats(buckets & 8 ? 8 : (buckets & 4 ? 6 : (buckets & 2 ? 4 : 2)));
+}
+
+int64_t art_alignment_sums_scratch_doubles(const ArtAlignmentJob* jobs_host, int32_t n_jobs) {
+  int64_t nmax;
+  unsigned buckets;
+  const int rc = align_check_jobs(jobs_host, n_jobs, &nmax, &buckets);
+  return rc ? rc : (int64_t)n_jobs * (pol_tiles(nmax) * align_stride(buckets) + kAlignPilotTiles * kAlignPilotStats);
+}
+
+int art_alignment_sums(const ArtAlignmentJob* jobs_dev, const ArtAlignmentJob* jobs_host, int32_t n_jobs, double* scratch,
+                       double* out, void* stream) {
+  if (!jobs_dev || !scratch || !out) return fail(ART_ERR_BAD_ARG, "NULL argument");
+  int64_t nmax;
+  unsigned buckets;
+  const int rc = align_check_jobs(jobs_host, n_jobs, &nmax, &buckets);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t tiles = pol_tiles(nmax), per_job = tiles * align_stride(buckets);
+  double* pilot = scratch + (int64_t)n_jobs * per_job;         // (behind the tiles' partial sums)
+  for (int pass = 0; pass < 2; ++pass) {                       // every job's pilot sums, then the sums about their means
+    const bool first = pass == 0;
+    align_launch<2>(first, buckets, jobs_dev, n_jobs, tiles, per_job, scratch, pilot, s);
+    align_launch<4>(first, buckets, jobs_dev, n_jobs, tiles, per_job, scratch, pilot, s);
+    align_launch<6>(first, buckets, jobs_dev, n_jobs, tiles, per_job, scratch, pilot, s);
+    align_launch<8>(first, buckets, jobs_dev, n_jobs, tiles, per_job, scratch, pilot, s);
+  }
+  hipLaunchKernelGGL(k_alignment_fold, dim3(ART_ALIGN_DOUBLES, n_jobs), dim3(kFoldBlock), 0, s, jobs_dev, per_job,
+                     (const double*)scratch, (const double*)pilot, out);
+  return launched("art_alignment_sums launch");
 }
 
 // the wavenumber blocks of art_focal_vector_spectrum: slices S of the rays (never from the block: the same bytes for any),

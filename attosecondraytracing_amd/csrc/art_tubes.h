@@ -424,4 +424,66 @@ ART_HD void readout_column(const double* D, const double* P, const double* C, co
   dY = r[1];
 }
 
+// ------------------------------------------------------------------------------------------- compensator sums
+// art_alignment_sums (include/art_hip.h) carries a CHOSEN handful of the columns above in one lane.  A column id is
+// art_sensitivities' c = 6 g + i, or -1 (ART_ALIGN_DOF_DETECTOR): the detector shifted along its normal by u with
+// Detector.shiftByDistance's sign, C' = C - u nd.  That column is closed form, dP = dD = 0 up to the read-out: the hit
+// moves along the ray by -u / (nd . D), so about the moved centre
+//   dX_lab = nd - D / (nd . D),  dL = -1 / (nd . D)        (exactly linear in u)
+ART_HD void detector_column(const double* D, const double* nd, const double* rotm, Column& c, double& dX, double& dY) {
+  const double inD = 1.0 / dot(nd, D);
+  double r[3];
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    c.dP[q] = nd[q] - D[q] * inD;
+    c.dD[q] = 0.0;
+  }
+  c.dL = -inD;
+  rot(rotm, c.dP, r);
+  dX = r[0];
+  dY = r[1];
+}
+
+// the group of a column id: 0 the source, g >= 1 element g - 1, -1 the detector
+ART_HD int dof_group(const int id) { return id < 0 ? -1 : id / 6; }
+
+// the first element a lane that carries column `id` has to visit (K: none, the last view alone serves the detector)
+ART_HD int dof_first(const int id, const int K) {
+  const int g = dof_group(id);
+  return g < 0 ? K : (g ? g - 1 : 0);
+}
+
+// column `id` at the source view (D0: the source direction there; read only by a source column)
+ART_HD void seed_selected(const int id, const double* D0, Column& c) {
+  clear(c);
+  if (dof_group(id) == 0) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k)                  // (a constant column per branch, as in step_selected)
+      if (id == k) seed_source(k, D0, c);
+  }
+}
+
+// column `id` through element e (its surface s, the hit h at the lab point P): it moves there, it passes (the source or
+// an earlier element moved), or it is still clear (a later element, the detector) and stays so
+ART_HD void step_selected(const Surface& s, const Hit& h, const double* D, const double* P, const int id, const int e,
+                          Column& c) {
+  const int g = dof_group(id);
+  if (g == e + 1) {
+    double sv[3], th[3];
+    const int i = id % 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k)                  // (a constant column per branch: no indexed access to the surface)
+      if (i == k) motion(s, k, P, sv, th);
+    step_moved(s, h, D, sv, th, c);
+  } else if (g >= 0 && g <= e) {
+    step_path(s, h, D, c);
+  }
+}
+
+ART_HD void readout_selected(const int id, const double* D, const double* P, const double* C, const double* nd,
+                             const double* rotm, Column& c, double& dX, double& dY) {
+  if (id < 0) detector_column(D, nd, rotm, c, dX, dY);
+  else readout_column(D, P, C, nd, rotm, c, dX, dY);
+}
+
 }  // namespace artt

@@ -760,6 +760,57 @@ int64_t art_sensitivities_scratch_doubles(const ArtSensitivityJob* jobs_host, in
 int art_sensitivities(const ArtSensitivityJob* jobs_dev, const ArtSensitivityJob* jobs_host, int32_t n_jobs,
                       double* scratch, double* out, void* stream);
 
+/* Compensator sums of MANY traced chains in one call (added under ABI 14: ArtAlignmentJob, art_alignment_sums,
+ * art_alignment_sums_scratch_doubles): the products BETWEEN a chosen handful of art_sensitivities' columns, per ray, from
+ * which a least-squares solve finds the moves of a few adjusters that make the spot (or the path spread) smallest.
+ * dofs[0 .. n_dofs): column ids in art_sensitivities' numbering, c = 6 g + i, in the caller's order, or
+ * ART_ALIGN_DOF_DETECTOR: the detector shifted along its normal, per mm, centre' = centre - u normal (the sign of
+ * Detector.shiftByDistance): dX_lab = normal - D' / (normal.D'), dL = -1 / (normal.D'), exactly linear in u.
+ * All columns of a job travel in ONE lane (a product needs both of its columns there); the lane starts at the earliest
+ * element among the chosen groups, and a column of a later group stays clear until its own element.  X, Y, L, the
+ * counted rays (alive in EVERY view) and the transport are art_sensitivities'.
+ * Centring: a pitch moves the whole spot, |mean dX| >> its spread, so products of uncentred columns would cancel.  A pilot
+ * launch on the same stream forms the weighted means of every column over the first min(n, ART_ALIGN_PILOT) slots
+ * (zeros when no ray counts there) and leaves them in the table; the main pass sums d'Q_a = dQ_a - centre_a^Q.  Nothing
+ * is read back in between.  The covariances do not depend on the centres; the true means are centre + sum w d'Q / sum w.
+ * out (DEVICE, written): ART_ALIGN_DOUBLES doubles per job, with Q = X, Y, L for q = 0, 1, 2 and a, b the places in dofs:
+ *   [0..8)                             row 0 of art_sensitivities: count, sum w, sum w X, Y, L, sum w X^2, Y^2, L^2
+ *   [ART_ALIGN_CENTRES + 8 q + a]      centre_a^Q, the pilot's mean of dQ_a
+ *   [ART_ALIGN_MEANS + 8 q + a]        sum w d'Q_a
+ *   [ART_ALIGN_CROSS + 8 q + a]        sum w Q d'Q_a
+ *   [ART_ALIGN_PAIRS + 36 q + p]       sum w d'Q_a d'Q_b for a <= b, p = a (17 - a) / 2 + (b - a)
+ * Entries of places >= n_dofs and [188..192) are 0.  Fixed summation order, no float atomics; a job's slicing and its
+ * kernel depend on its own n and n_dofs only: every job gets the same bytes whichever jobs share its call.
+ * jobs_dev / jobs_host and the element tables: as for art_ray_tubes.
+ * scratch: DEVICE, art_alignment_sums_scratch_doubles(jobs_host, n_jobs): at most 164 doubles per job and tile of 256
+ * slots (5.1 B per slot).
+ * Limits: those of art_sensitivities, and 1 <= n_dofs <= ART_ALIGN_MAX_DOFS, every id in [-1, 6 (K + 1)) and none twice:
+ * ART_ERR_BAD_ARG otherwise.  Nothing is launched on failure.                                                          */
+#define ART_ALIGN_MAX_DOFS 8
+#define ART_ALIGN_PILOT 1024
+#define ART_ALIGN_DOF_DETECTOR (-1)
+#define ART_ALIGN_CENTRES 8
+#define ART_ALIGN_MEANS 32
+#define ART_ALIGN_CROSS 56
+#define ART_ALIGN_PAIRS 80
+#define ART_ALIGN_DOUBLES 192
+/* (declared by its tag, as ArtQuantileDesc is: C callers write `struct ArtAlignmentJob`) */
+struct ArtAlignmentJob {
+  const ArtBundleView* views;      /* DEVICE array of n_elems + 1 views: the source, then the bundle after each element */
+  const ArtElementDesc* elems;     /* n_elems descriptors (DEVICE in jobs_dev, HOST in jobs_host)                       */
+  const ArtQuadricDesc* quadrics;  /* n_elems entries, read where ART_FLAG_QUADRIC is set; may be NULL without any      */
+  int32_t n_elems;                 /* K                                                                                 */
+  int32_t n_dofs;                  /* C                                                                                 */
+  int64_t n;                       /* slots of every view                                                               */
+  ArtDetectorDesc det;             /* required: centre, unit normal, rot                                                */
+  const double* w;                 /* DEVICE weights [n] or NULL (all 1)                                                */
+  double origin[3];                /* X0, Y0, L0                                                                        */
+  int32_t dofs[ART_ALIGN_MAX_DOFS];
+};
+int64_t art_alignment_sums_scratch_doubles(const struct ArtAlignmentJob* jobs_host, int32_t n_jobs);
+int art_alignment_sums(const struct ArtAlignmentJob* jobs_dev, const struct ArtAlignmentJob* jobs_host, int32_t n_jobs,
+                       double* scratch, double* out /* DEVICE [n_jobs][ART_ALIGN_DOUBLES] */, void* stream);
+
 /* Vector focal fields of a pulse behind dispersive coatings (added under ABI 14: ArtFocalVectorSpectrumDesc,
  * art_focal_vector_spectrum, art_focal_vector_spectrum_scratch_doubles): art_focal_spectrum's sum with the complex
  * vector field of art_polarisation, evaluated per ray AND per wavenumber, as each ray's amplitude.  With
